@@ -2,7 +2,7 @@
 """Headline benchmark: Mrays/s (primary + secondary) of the wavefront path tracer on the 10M-triangle synthetic scene
 (BASELINE.json config 5: 2309 baked copies of rounded_cube, 4096x4096 film, PathIntegrator(5, 1.0), env-map light).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
   N > 1: either under a launcher (python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P
   bench.py --gpus N ...) or plainly -- then bench.py starts its N ranks itself as a child process (fountain_amd/launch.py) and relays
   rank 0's line.  A launcher whose WORLD_SIZE differs from --gpus is an error (exit code 2).
@@ -42,6 +42,9 @@ def main():
     ap.add_argument("--scaling", default=os.environ.get("FTN_BENCH_SCALING", "weak"), choices=["weak", "strong"],
                     help="weak (default): every GPU renders --spp-per-gpu samples of its tiles per step, the job's work grows with N; strong: a step is --spp-per-gpu samples of the WHOLE film whatever N is, each GPU renders its 1/N of the tiles")
     ap.add_argument("--no-count-step", action="store_true", help="skip the untimed counting step (tools/make_traffic_json.py: every dispatch of the run then belongs to the timed steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one handed back (the film, a fixed seeded sample of it when large, and the "
+                         "step's ray counters) as DIR/<name>.npy, so that two builds can be compared output for output")
     ap.add_argument("--launch-check", action="store_true", help="start the ranks, form the process group, print the result line's n_gpus -- no rendering (CPU test of the launcher)")
     args = ap.parse_args()
 
@@ -142,6 +145,7 @@ def main():
     t0 = time.perf_counter()
     rays = 0
     tot = {"trace_ms": 0.0, "trace_launches": 0, "any_ms": 0.0, "any_launches": 0, "shade_ms": 0.0, "shade_launches": 0, "sort_ms": 0.0, "kernel_ms": 0.0, "camera_samples": 0}
+    st = None
     for i in range(args.steps):
         st = step(args.warmup + i)
         rays += st["rays_closest"] + st["rays_any"]
@@ -165,6 +169,9 @@ def main():
     # per-rank spread: where a scaling loss comes from (a slow rank, or the reduce)
     per_rank = rank_spread({"device_ms_per_step": tot["kernel_ms"] / max(args.steps, 1), "render_wall_ms": t_render * 1e3, "merge_ms": t_merge * 1e3},
                            device="cpu" if host_merge else dev)
+
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, dev_film, st)      # after the clock stopped: not part of the timed region
 
     if rank == 0:
         mrays = rays / elapsed / 1e6
@@ -190,6 +197,34 @@ def main():
         print(json.dumps(out), flush=True)
     if use_dist:
         dist.destroy_process_group()
+
+
+DUMP_MAX_PIXELS = 1 << 20              # 16 MB of film pixels at most (the 4096^2 film is 256 MB)
+DUMP_SEED = 20240601
+LAST_STEP_COUNTERS = ("rays_closest", "rays_any", "mis_rays_any_hit", "camera_samples", "spill_samples")
+
+
+def dump_outputs(out_dir, film, st):
+    """--dump-outputs DIR: what the timed path handed its caller in the last timed step, for comparing two builds.
+      * film_pixels.npy (float32, [n, 4]: xyz + filter weight sum): the resident film after the last timed step (and the reduce over
+        the ranks).  The steps accumulate into the one film, so it holds the sum of all the timed steps.  A film of at most
+        DUMP_MAX_PIXELS pixels is written whole; a larger one as a fixed sample of DUMP_MAX_PIXELS pixels, the same for every run
+        with the same film size;
+      * film_pixel_index.npy (float64, [n]): the flat pixel index (y * width + x) of each row of film_pixels.npy;
+      * last_step_counts.npy (float64): the last step's counters named in LAST_STEP_COUNTERS (zeros with --steps 0).
+    Timings are left out: they are not outputs.  `film` is an [h, w, 4] float32 torch tensor on any device."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    flat = film.reshape(-1, 4)
+    n = flat.shape[0]
+    if n <= DUMP_MAX_PIXELS:
+        idx = np.arange(n, dtype=np.int64)
+    else:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=DUMP_MAX_PIXELS, replace=False))
+    px = flat.index_select(0, torch.from_numpy(idx).to(flat.device)).cpu().numpy().astype(np.float32)
+    np.save(os.path.join(out_dir, "film_pixels.npy"), px)
+    np.save(os.path.join(out_dir, "film_pixel_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(out_dir, "last_step_counts.npy"), np.array([float(st[k]) if st is not None else 0.0 for k in LAST_STEP_COUNTERS], dtype=np.float64))
 
 
 def per_gpu_workload(args):

@@ -38,5 +38,5 @@ if rank == 0:
     whole = Film(orc, res)
     si.render_parallel(scene, whole, smp, n_threads=2)
     np.savez(out_path, merged=merged.numpy(), whole=whole.pixels, world=world)
-dist.barrier()
+dist.all_reduce(torch.zeros(1))          # barrier on a host tensor (dist.barrier() probes for a GPU)
 dist.destroy_process_group()

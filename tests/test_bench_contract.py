@@ -73,3 +73,45 @@ def test_step_and_workload_helpers():
     tj = json.load(open(os.path.join(ROOT, "profiles", bench.PROFILE_ROUND, "traffic.json")))
     if tj["source_hash"] != bench.source_hash():          # (bench.py then leaves the HBM-side figures out of its line and says so: no silent staleness)
         pytest.skip("profiles/r03/traffic.json was taken on other kernel sources: rerun tools/make_traffic_json.py on the GPU box")
+
+
+def _load_bench():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    return bench
+
+
+def test_dump_outputs(tmp_path):
+    """--dump-outputs: a small film is written whole, a large one as the same fixed sample on every run; float32 / float64 only,
+    64 MB at most for the benchmark's 4096 x 4096 film."""
+    import numpy as np
+    import torch
+    bench = _load_bench()
+    st = {k: 1000 + i for i, k in enumerate(bench.LAST_STEP_COUNTERS)}
+    small = torch.arange(8 * 6 * 4, dtype=torch.float32).reshape(8, 6, 4)
+    bench.dump_outputs(str(tmp_path / "small"), small, st)
+    px = np.load(tmp_path / "small" / "film_pixels.npy")
+    assert px.dtype == np.float32 and np.array_equal(px, small.numpy().reshape(-1, 4))
+    assert np.array_equal(np.load(tmp_path / "small" / "film_pixel_index.npy"), np.arange(48, dtype=np.float64))
+    c = np.load(tmp_path / "small" / "last_step_counts.npy")
+    assert c.dtype == np.float64 and list(c) == [float(st[k]) for k in bench.LAST_STEP_COUNTERS]
+
+    big = torch.rand((4096, 4096, 4), generator=torch.Generator().manual_seed(1))
+    runs = []
+    for name in ("a", "b"):
+        d = tmp_path / name
+        bench.dump_outputs(str(d), big, None)
+        files = sorted(d.iterdir())
+        assert [f.name for f in files] == ["film_pixel_index.npy", "film_pixels.npy", "last_step_counts.npy"]
+        assert sum(f.stat().st_size for f in files) <= 64 << 20
+        arrs = {f.stem: np.load(f) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrs.values())
+        runs.append(arrs)
+    idx = runs[0]["film_pixel_index"]
+    assert len(idx) == bench.DUMP_MAX_PIXELS and np.all(np.diff(idx) > 0) and idx[-1] < 4096 * 4096
+    for k in runs[0]:
+        assert np.array_equal(runs[0][k], runs[1][k]), k
+    assert np.array_equal(runs[0]["film_pixels"], big.numpy().reshape(-1, 4)[idx.astype(np.int64)])
+    assert not runs[0]["last_step_counts"].any()

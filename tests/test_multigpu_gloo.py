@@ -8,6 +8,9 @@ import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+# for the CPU jobs below: torch answers the launcher's accelerator probe from an empty device list without starting the HIP runtime,
+# so that neither the launcher nor its ranks open the device on a GPU machine
+CPU_ONLY = {"HIP_VISIBLE_DEVICES": "", "PYTORCH_NVML_BASED_CUDA_CHECK": "1"}
 
 
 @pytest.mark.parametrize("world", [2, 3, 8])
@@ -16,7 +19,7 @@ def test_sharded_render_equals_whole(tmp_path, world):
     port = 29500 + (os.getpid() + world) % 500
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "tests", "_gloo_worker.py"), out]
-    env = dict(os.environ, OMP_NUM_THREADS="1")
+    env = dict(os.environ, OMP_NUM_THREADS="1", **CPU_ONLY)
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     d = np.load(out)
@@ -91,7 +94,7 @@ def test_render_cli_under_torchrun(tmp_path):
 
 
 def _run(cmd, env=None, timeout=300):
-    return subprocess.run(cmd, env=dict(os.environ, OMP_NUM_THREADS="1", **(env or {})), capture_output=True, text=True, timeout=timeout, cwd=ROOT)
+    return subprocess.run(cmd, env=dict(os.environ, OMP_NUM_THREADS="1", **CPU_ONLY, **(env or {})), capture_output=True, text=True, timeout=timeout, cwd=ROOT)
 
 
 @pytest.mark.parametrize("n", [2, 8])
@@ -101,7 +104,7 @@ def test_bench_starts_its_own_ranks(n):
     carries the real run."""
     import json
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--launch-check"], env=dict(env, OMP_NUM_THREADS="1"),
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--launch-check"], env=dict(env, OMP_NUM_THREADS="1", **CPU_ONLY),
                        capture_output=True, text=True, timeout=300, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -120,7 +123,7 @@ def test_bench_rank_failure_is_an_error():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     r = subprocess.run([sys.executable, "-c", "import sys; sys.path.insert(0, %r); from fountain_amd.launch import spawn_ranks; "
                         "sys.exit(spawn_ranks(2, ['--no-such-flag'], script=%r))" % (ROOT, os.path.join(ROOT, "bench.py"))],
-                       env=env, capture_output=True, text=True, timeout=300, cwd=ROOT)
+                       env=dict(env, **CPU_ONLY), capture_output=True, text=True, timeout=300, cwd=ROOT)
     assert r.returncode != 0
 
 
@@ -130,7 +133,7 @@ def test_spawn_ranks_deadline_stops_hung_ranks(tmp_path):
     hang.write_text("import os, sys, time\nopen(os.path.join(%r, 'pid%%s' %% os.environ['RANK']), 'w').write(str(os.getpid()))\nprint('started', flush=True)\ntime.sleep(600)\n" % str(tmp_path))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     r = subprocess.run([sys.executable, "-c", "import sys; sys.path.insert(0, %r); from fountain_amd.launch import spawn_ranks; "
-                        "sys.exit(spawn_ranks(2, [], script=%r, timeout=20))" % (ROOT, str(hang))], env=env, capture_output=True, text=True, timeout=200, cwd=ROOT)
+                        "sys.exit(spawn_ranks(2, [], script=%r, timeout=20))" % (ROOT, str(hang))], env=dict(env, **CPU_ONLY), capture_output=True, text=True, timeout=200, cwd=ROOT)
     assert r.returncode == 124, (r.returncode, r.stderr[-1500:])
     import time
     time.sleep(1.0)
