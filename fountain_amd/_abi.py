@@ -151,6 +151,17 @@ class ftn_gbuffer_pixel(C.Structure):
 
 FTN_GBUFFER_ABI_VERSION = 1  # include/fountain_hip_gbuffer.h (an extension with a version of its own; FTN_ABI_VERSION is unchanged)
 
+
+class ftn_denoise_params(C.Structure):
+    """include/fountain_hip_denoise.h: parameters of the a-trous denoiser (ftn_denoise_params_default fills the defaults)."""
+    _fields_ = [("levels", C.c_int32), ("flags", c_u32), ("sigma_color", c_f), ("sigma_normal", c_f), ("sigma_plane", c_f),
+                ("albedo_eps", c_f), ("color_eps", c_f), ("reserved", c_u32)]
+
+
+FTN_DENOISE_DEMODULATE = 1
+FTN_DENOISE_MAX_LEVELS = 10
+FTN_DENOISE_ABI_VERSION = 1  # include/fountain_hip_denoise.h (an extension with a version of its own)
+
 FTN_ABI_VERSION = 3          # include/fountain_hip.h; Backend() refuses a product library that reports another one
 
 # Expected sizes (bytes) -- asserted against the header by the C side's static_asserts and tests/test_abi.py
@@ -159,7 +170,7 @@ SIZES = {
     "ftn_sphere": 288, "ftn_material": 48, "ftn_light": 160, "ftn_envmap": 16, "ftn_camera_desc": 296,
     "ftn_film_desc": 32, "ftn_sampler_desc": 24, "ftn_integrator_desc": 16, "ftn_tile_range": 16,
     "ftn_render_options": 16, "ftn_stats": 152, "ftn_scene_memory": 96, "ftn_texture": 48, "ftn_image": 24, "ftn_material_textures": 32,
-    "ftn_gbuffer_pixel": 48,
+    "ftn_gbuffer_pixel": 48, "ftn_denoise_params": 32,
 }
 
 # Every function the header declares (name -> None); used by the symbol-export test.
@@ -182,4 +193,11 @@ DECLARED_FUNCTIONS = [
 # fountain_hip.h alone: the reference has no G-buffer, so these have no orc_* twin).
 GBUFFER_FUNCTIONS = [
     "ftn_render_gbuffer", "ftn_render_gbuffer_device", "ftn_gbuffer_resolve", "ftn_gbuffer_resolve_device", "ftn_gbuffer_abi_version",
+]
+
+# Every function the extension header include/fountain_hip_denoise.h declares (kept apart from the two lists above: the reference has
+# no denoiser, so these have no orc_* twin either).
+DENOISE_FUNCTIONS = [
+    "ftn_denoise_params_default", "ftn_denoise", "ftn_denoise_workspace_size", "ftn_denoise_device", "ftn_denoise_cpu",
+    "ftn_denoise_abi_version",
 ]

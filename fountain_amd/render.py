@@ -8,7 +8,9 @@ reduce (RCCL when every rank has its own GPU, gloo with --dist-backend gloo); ra
 per-tile RandomSampler stream (one lane per 16x16 tile: for validation, slow); the default re-seeds per (pixel, sample) so that
 samples run in parallel (samplers).  --gbuffer also writes the first-hit G-buffer of the same camera samples
 (fountain_amd/gbuffer.py) beside the image: <name>_albedo.exr, <name>_normal.exr, <name>_position.exr and <name>_depth.exr (camera-space
-depth repeated in R, G and B); it needs the default sampler and one GPU.
+depth repeated in R, G and B); it needs the default sampler and one GPU.  --denoise then renders that G-buffer (also without
+--gbuffer) and writes <name>_denoised.exr: the image filtered by the edge-avoiding a-trous denoiser (fountain_amd/denoise.py, default
+parameters); the image itself is written unchanged.  It has the same needs as --gbuffer.
 """
 import argparse
 import sys
@@ -30,13 +32,15 @@ def main(argv=None):
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"])
     ap.add_argument("--gpus", type=int, default=None, help="render on N GPUs of this node: film tiles r, r+N, ... per rank, one reduce at the end")
     ap.add_argument("--gbuffer", action="store_true", help="also write the first-hit albedo / normal / position / depth buffers as <name>_<buffer>.exr")
+    ap.add_argument("--denoise", action="store_true", help="also write <name>_denoised.exr, the image denoised with the first-hit G-buffer of its camera samples")
     opts = ap.parse_args(argv)
-    if opts.gbuffer and opts.exact_stream:
-        print("error: --gbuffer needs the default sampler: with --exact-stream a sample's camera ray depends on everything its tile drew before it", file=sys.stderr)
-        return 2
-    if opts.gbuffer and opts.gpus is not None:
-        print("error: --gbuffer renders on one GPU: leave out --gpus", file=sys.stderr)
-        return 2
+    for flag, on in (("--gbuffer", opts.gbuffer), ("--denoise", opts.denoise)):
+        if on and opts.exact_stream:
+            print("error: %s needs the default sampler: with --exact-stream a sample's camera ray depends on everything its tile drew before it" % flag, file=sys.stderr)
+            return 2
+        if on and opts.gpus is not None:
+            print("error: %s renders on one GPU: leave out --gpus" % flag, file=sys.stderr)
+            return 2
     import os
     from .launch import spawn_ranks, world_from_env
     env_world = world_from_env()
@@ -44,8 +48,8 @@ def main(argv=None):
         # started plainly: start the N ranks as a child process (before anything here has touched HIP) and hand back its exit code
         return spawn_ranks(opts.gpus, sys.argv[1:] if argv is None else list(argv), module="fountain_amd.render")
     world, rank = (env_world[0], env_world[1]) if env_world is not None else (1, 0)
-    if opts.gbuffer and world > 1:
-        print("error: --gbuffer renders on one GPU, not under a launcher of %d ranks" % world, file=sys.stderr)
+    if (opts.gbuffer or opts.denoise) and world > 1:
+        print("error: %s renders on one GPU, not under a launcher of %d ranks" % ("--gbuffer" if opts.gbuffer else "--denoise", world), file=sys.stderr)
         return 2
     if opts.gpus is not None and opts.gpus != world:
         print("error: --gpus %d but the launcher started WORLD_SIZE %d ranks" % (opts.gpus, world), file=sys.stderr)
@@ -92,8 +96,10 @@ def main(argv=None):
     print("Completed rendering in %.3f s (%.1f Mrays/s%s)" % (dt, rays / dt / 1e6, " on rank 0 of %d" % world if world > 1 else ""), file=sys.stderr)
     img, (w, h) = film.into_spectrum_buffer()
     write_exr(filename, img, be)
-    if opts.gbuffer:
-        write_gbuffer(be, scene, parsed.camera, film, sampler, filename, opts.gpu)
+    if opts.gbuffer or opts.denoise:
+        gb = write_gbuffer(be, scene, parsed.camera, film, sampler, filename, opts.gpu, write=opts.gbuffer)
+        if opts.denoise:
+            write_denoised(be, img, gb, filename, opts.gpu)
     return 0
 
 
@@ -103,16 +109,35 @@ def gbuffer_paths(filename):
     return {k: "%s_%s.exr" % (base, k) for k in ("albedo", "normal", "position", "depth")}
 
 
-def write_gbuffer(be, scene, camera, film, sampler, filename, device):
-    """The first-hit G-buffer of the beauty's camera samples (same film, sampler and tiles), resolved and written beside the image."""
+def denoised_path(filename):
+    """out.exr -> out_denoised.exr"""
+    base = filename[:-4] if filename.endswith(".exr") else filename
+    return "%s_denoised.exr" % base
+
+
+def write_gbuffer(be, scene, camera, film, sampler, filename, device, write=True):
+    """The first-hit G-buffer of the beauty's camera samples (same film, sampler and tiles), resolved and (with `write`) written beside
+    the image.  Returns the 12 resolved floats per pixel, [H, W, 12]."""
     import numpy as np
-    from .gbuffer import render_gbuffer
+    from .gbuffer import CHANNELS, render_gbuffer
     res, _, st = render_gbuffer(be, None, camera, tuple(film.desc.full_resolution), sampler, scene=scene, film=film, device=device)
-    paths = gbuffer_paths(filename)
-    for k in ("albedo", "normal", "position"):
-        write_exr(paths[k], res[k], be)
-    write_exr(paths["depth"], np.repeat(res["depth"], 3, axis=-1), be)
-    print("G-buffer: %s (%.1f ms on the GPU)" % (", ".join(paths[k] for k in ("albedo", "normal", "position", "depth")), st["kernel_ms"]), file=sys.stderr)
+    if write:
+        paths = gbuffer_paths(filename)
+        for k in ("albedo", "normal", "position"):
+            write_exr(paths[k], res[k], be)
+        write_exr(paths["depth"], np.repeat(res["depth"], 3, axis=-1), be)
+        print("G-buffer: %s (%.1f ms on the GPU)" % (", ".join(paths[k] for k in ("albedo", "normal", "position", "depth")), st["kernel_ms"]), file=sys.stderr)
+    return np.concatenate([res[k] for k in CHANNELS], axis=-1)
+
+
+def write_denoised(be, img, gb12, filename, device):
+    """The resolved image denoised with its G-buffer (default parameters), written as <name>_denoised.exr."""
+    from .denoise import denoise
+    t0 = time.time()
+    out = denoise(be, img, gb12, device=device)
+    path = denoised_path(filename)
+    write_exr(path, out, be)
+    print("denoised: %s (%.1f ms)" % (path, (time.time() - t0) * 1e3), file=sys.stderr)
 
 
 if __name__ == "__main__":
