@@ -255,6 +255,32 @@ void orc_kat_camera_ray(const ftn_camera_desc* cam, const float sample5[5], floa
     Float w; RayDifferential rd = c.generate_ray_differential(cs, &w);
     out[0] = rd.ray.origin.x; out[1] = rd.ray.origin.y; out[2] = rd.ray.origin.z; out[3] = rd.ray.dir.x; out[4] = rd.ray.dir.y; out[5] = rd.ray.dir.z;
 }
+// the camera ray of a sample as render_tile hands it to the integrator (mod.rs:252-254: generate_ray_differential, then
+// scale_differentials(1 / sqrt(spp))) and, with hit12 = {p, n, dpdu, dpdv} of a surface, compute_tex_differentials there
+// (interaction.rs:124-173).  out = o[3] d[3] rx_origin[3] rx_dir[3] ry_origin[3] ry_dir[3] dudx dvdx dudy dvdy (zeros without hit12)
+void orc_kat_camera_ray_differential(const ftn_camera_desc* cam, const float sample5[5], uint32_t spp, const float* hit12, float out[22]) {
+    Camera c; c.camera_to_world = from_abi(&cam->camera_to_world); c.raster_to_camera = from_abi(&cam->raster_to_camera);
+    c.shutter_open = cam->shutter_open; c.shutter_close = cam->shutter_close; c.lens_radius = cam->lens_radius; c.focal_dist = cam->focal_dist;
+    c.dx_camera = Vec3(cam->dx_camera[0], cam->dx_camera[1], cam->dx_camera[2]); c.dy_camera = Vec3(cam->dy_camera[0], cam->dy_camera[1], cam->dy_camera[2]);
+    CameraSample cs; cs.p_film = Vec2(sample5[0], sample5[1]); cs.p_lens = Vec2(sample5[2], sample5[3]); cs.time = sample5[4];
+    Float w; RayDifferential rd = c.generate_ray_differential(cs, &w);
+    rd.scale_differentials(1.0f / sqrtf((Float)spp));
+    Vec3 v[] = {rd.ray.origin, rd.ray.dir, rd.diff.rx_origin, rd.diff.rx_dir, rd.diff.ry_origin, rd.diff.ry_dir};
+    for (int k = 0; k < 6; k++) for (int i = 0; i < 3; i++) out[3 * k + i] = v[k][i];
+    SurfaceInteraction si;
+    if (hit12) {
+        si.hit.p = Vec3(hit12[0], hit12[1], hit12[2]); si.hit.n = Vec3(hit12[3], hit12[4], hit12[5]);
+        si.geom.dpdu = Vec3(hit12[6], hit12[7], hit12[8]); si.geom.dpdv = Vec3(hit12[9], hit12[10], hit12[11]);
+        si.compute_tex_differentials(rd);
+    }
+    out[18] = si.tex_diffs.dudx; out[19] = si.tex_diffs.dvdx; out[20] = si.tex_diffs.dudy; out[21] = si.tex_diffs.dvdy;
+}
+// SurfaceHit::spawn_ray (interaction.rs:22-30) from p, p_err, n along d: out = the ray's 8 floats (o, d, t_max, time 0)
+void orc_kat_spawn_ray(const float p[3], const float p_err[3], const float n[3], const float d[3], float out8[8]) {
+    SurfaceHit h; h.p = Vec3(p[0], p[1], p[2]); h.p_err = Vec3(p_err[0], p_err[1], p_err[2]); h.n = Vec3(n[0], n[1], n[2]); h.time = 0.0f;
+    Ray r = h.spawn_ray(Vec3(d[0], d[1], d[2]));
+    out8[0] = r.origin.x; out8[1] = r.origin.y; out8[2] = r.origin.z; out8[3] = r.dir.x; out8[4] = r.dir.y; out8[5] = r.dir.z; out8[6] = r.t_max; out8[7] = r.time;
+}
 // Transform::tf_err_to_err for points / vectors (transform.rs:411-437): out = t[3] err[3]
 void orc_kat_tf_err(const ftn_transform* t, const float p[3], const float e[3], int is_point, float out[6]) {
     Vec3 err; Vec3 r = is_point ? tf_point_err_to_err(from_abi(t), Vec3(p[0], p[1], p[2]), Vec3(e[0], e[1], e[2]), &err)

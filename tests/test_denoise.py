@@ -1,7 +1,8 @@
 """The a-trous denoiser on the GPU (include/fountain_hip_denoise.h, fountain_amd/denoise.py): the device path equals the host twin bit
 for bit on synthetic inputs, on a rendered Cornell box and on a textured scene with environment misses, through ftn_denoise and
-through ftn_denoise_device on a torch stream; a 4096^2 image; the quality against a converged render; inputs untouched; repeated calls;
-the CLI."""
+through ftn_denoise_device on a torch stream; a 4096^2 image and sizes that take both grid-stride loops round twice; levels = 0 on the
+device; a captured graph; the rendered images against the float64 restatement; subnormal weights; the quality against a converged
+render; inputs untouched; repeated calls; the CLI."""
 import os
 
 import numpy as np
@@ -134,7 +135,86 @@ def test_4096_square(gpu):
     assert np.array_equal(bits(got), bits(D.denoise_cpu(gpu, rgb, gb)))
 
 
-# ------------------------------------------------------------------ 3. quality
+@pytest.mark.parametrize("h,w", [(4112, 4112), (1, 1048592), (1048592, 1)])
+def test_grid_stride_loops(gpu, h, w):
+    """k_dn_atrous runs at most 65536 workgroups of one 16 x 16 tile and k_dn_prepare at most 65536 of 256 pixels: 4112^2 (66049
+    tiles, more than 2^24 pixels) and a row or column of 1048592 pixels (65537 tiles) need a second trip round both loops"""
+    rgb, gb, _ = R.synthetic(h, w, seed=h + 3 * w)
+    p = dict(levels=2)
+    got = D.denoise(gpu, rgb, gb, p)
+    assert np.array_equal(bits(got), bits(D.denoise_cpu(gpu, rgb, gb, p)))
+    assert np.isfinite(got).all() and not np.array_equal(bits(got), bits(rgb))
+
+
+def test_zero_levels_on_the_device(gpu):
+    """levels = 0 copies rgb bit for bit, NaN and infinities included, through ftn_denoise and through ftn_denoise_device"""
+    import torch
+    rgb, gb, _ = R.synthetic(37, 53, seed=9)
+    rgb.reshape(-1)[::7] = np.nan
+    rgb.reshape(-1)[3::11] = -np.inf
+    rgb.reshape(-1)[5::13] = np.inf
+    for flags in (0, 1):
+        p = dict(levels=0, flags=flags)
+        assert np.array_equal(bits(D.denoise(gpu, rgb, gb, p)), bits(rgb))
+        t_rgb, t_gb = torch.from_numpy(rgb).cuda(), torch.from_numpy(gb).cuda()
+        out = torch.full_like(t_rgb, 7.0)
+        D.denoise_torch(gpu, t_rgb, t_gb, out, params=p)
+        torch.cuda.synchronize()
+        assert np.array_equal(bits(out.cpu().numpy()), bits(rgb))
+
+
+def test_graph_capture(gpu, yard4):
+    """ftn_denoise_device captured in a torch.cuda.graph (one stream, a workspace allocated before the capture), replayed twice with
+    new inputs copied into the captured buffers"""
+    import torch
+    rgb, gb = yard4
+    rng = np.random.default_rng(2)
+    inputs = [(rgb, gb), ((rgb * rng.uniform(0.5, 2.0, rgb.shape)).astype(np.float32), gb)]
+    t_rgb, t_gb = torch.from_numpy(rgb).cuda(), torch.from_numpy(gb).cuda()
+    out = torch.zeros_like(t_rgb)
+    ws = torch.empty(D.workspace_bytes(gpu, rgb.shape[1], rgb.shape[0]), dtype=torch.uint8, device="cuda")
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        D.denoise_torch(gpu, t_rgb, t_gb, out, workspace=ws)           # warm-up before the capture
+    torch.cuda.current_stream().wait_stream(s)
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        D.denoise_torch(gpu, t_rgb, t_gb, out, workspace=ws)
+    for r, f in inputs:
+        t_rgb.copy_(torch.from_numpy(r))
+        t_gb.copy_(torch.from_numpy(f))
+        out.fill_(float("nan"))
+        g.replay()
+        torch.cuda.synchronize()
+        assert np.array_equal(bits(out.cpu().numpy()), bits(D.denoise_cpu(gpu, r, f)))
+
+
+# ------------------------------------------------------------------ 3. against the float64 restatement
+@pytest.mark.parametrize("which", ["cornell", "yard"])
+@pytest.mark.parametrize("levels,flags", LEVELS)
+def test_rendered_device_against_float64(gpu, cornell4, yard4, which, levels, flags):
+    """the device on rendered buffers (sky misses with depth inf, partly covered pixels, fireflies) against tests/_denoise_ref.py: the
+    non-finite pattern equal, the rest within the first-order binary32 bound the restatement derives"""
+    rgb, gb = {"cornell": cornell4, "yard": yard4}[which]
+    got = D.denoise(gpu, rgb, gb, dict(levels=levels, flags=flags)).astype(np.float64)
+    want, err = R.reference_bound(rgb, gb, levels=levels, flags=flags)
+    assert np.array_equal(np.isfinite(got), np.isfinite(want))
+    fin = np.isfinite(want)
+    assert (np.abs(got[fin] - want[fin]) <= err[fin]).all(), "worst error / bound %.3g" % (np.abs(got[fin] - want[fin]) / err[fin]).max()
+
+
+@pytest.mark.parametrize("t_target,above", [(95.0, False), (104.0, False), (104.0, True)])
+def test_subnormal_weights_on_the_device(gpu, t_target, above):
+    """the one-tap images of test_denoise_cpu.py on the device: a subnormal weight (t about 95) survives, t = 104 and beyond weigh 0"""
+    rgb, gb, p, t, want = R.one_tap(t_target, above)
+    got = D.denoise(gpu, rgb, gb, p)
+    assert np.array_equal(bits(got[0, 2]), bits(np.full(3, want, np.float32)))
+    assert np.array_equal(bits(got), bits(D.denoise_cpu(gpu, rgb, gb, p)))
+
+
+# ------------------------------------------------------------------ 4. quality
 def test_quality_against_a_converged_render(gpu, cornell4):
     rgb, gb = cornell4
     b, cam, res = scenes.cornell(gpu, res=128)
@@ -145,7 +225,7 @@ def test_quality_against_a_converged_render(gpu, cornell4):
     assert den <= 0.5 * noisy
 
 
-# ------------------------------------------------------------------ 4. CLI
+# ------------------------------------------------------------------ 5. CLI
 def test_cli_denoise(gpu, tmp_path):
     from fountain_amd import render
     from fountain_amd.api import PbrtScene, read_exr

@@ -1,7 +1,7 @@
 """The host twin of the a-trous denoiser (ftn_denoise_cpu, include/fountain_hip_denoise.h) against an independent float64 numpy
 restatement of the filter's text (tests/_denoise_ref.py), and its properties at default parameters: an exact copy at 0 levels, fixed
 points, edges kept, albedo edges carried through demodulation, noise reduced, no dependence on the host thread count, non-finite
-inputs.  CPU only."""
+inputs, subnormal weights.  CPU only."""
 import os
 
 import numpy as np
@@ -125,3 +125,17 @@ def test_non_finite_inputs(ftn):
         bad = ~np.isfinite(rgb).all(-1)
         assert np.isfinite(out[~bad]).all()
         assert np.array_equal(bits(out[10, 10, 1:]), bits(D.denoise_cpu(ftn, rgb, gb, dict(flags=flags, levels=1))[10, 10, 1:]))
+
+
+@pytest.mark.parametrize("t_target,above", [(95.0, False), (104.0, False), (104.0, True)])
+def test_subnormal_weights_on_the_twin(ftn, t_target, above):
+    """one tap whose weight exp(-t) is a binary32 subnormal (t about 95), the last t the filter keeps (104) and the first it drops: the
+    black centre pixel takes exactly the header's binary32 value, a subnormal for t = 95 that flushing denormals would zero"""
+    rgb, gb, p, t, want = R.one_tap(t_target, above)
+    assert (t > 104.0) == above and abs(t - t_target) < 1e-3 * t_target
+    got = D.denoise_cpu(ftn, rgb, gb, p)
+    assert np.array_equal(bits(got[0, 2]), bits(np.full(3, want, np.float32)))
+    if t_target < 100:
+        assert 0 < want < np.finfo(np.float32).tiny
+    ref, err = R.reference_bound(rgb, gb, **p)
+    assert (np.abs(got - ref) <= err).all()

@@ -1,14 +1,18 @@
 """First-hit G-buffers on the GPU (include/fountain_hip_gbuffer.h, fountain_amd/gbuffer.py): an independent reconstruction from the
-oracle's camera rays and intersections, bit for bit; the same camera samples as the beauty; null-material pass-through; sample-range
-splits and the device path; image textures; refusals; a config-5-sized scene; the CLI."""
+oracle's camera rays and intersections (tests/_gbuffer_ref.py), bit for bit, with box filters wider than a pixel, crops and tile
+strides; the same camera samples as the beauty; spill sums shared with the beauty on one scene handle; several wavefront passes;
+null-material pass-through; sample-range splits and the device path; image textures through the camera differentials; the resolve
+step; refusals; a config-5-sized scene; the CLI."""
 import ctypes as C
 import os
 
 import numpy as np
 import pytest
 
-from fountain_amd import FountainError, PathIntegrator, RandomSampler, SceneBuilder, PerspectiveCamera, Film, scenes, _abi as A
+from fountain_amd import FountainError, PathIntegrator, RandomSampler, SamplerIntegrator, SceneBuilder, PerspectiveCamera, Film, scenes, _abi as A
 from fountain_amd import gbuffer as G
+
+import _gbuffer_ref as GR
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -16,17 +20,7 @@ AUTO, MEGA, WAVE = A.FTN_PIPELINE_AUTO, A.FTN_PIPELINE_MEGAKERNEL, A.FTN_PIPELIN
 F32 = np.float32
 
 
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def selected_tiles(film, tiles):
-    """list_tiles (bounds.rs:85-97) over the film's sample bounds, then the tile range's selection"""
-    sb = film.sample_bounds()
-    every = [(x, y, min(x + 16, sb[2]), min(y + 16, sb[3])) for y in range(sb[1], sb[3], 16) for x in range(sb[0], sb[2], 16)]
-    first, stride, count = tiles if tiles is not None else (0, 1, 0)
-    sel = every[first::stride]
-    return sel[:count] if count else sel
+bits = GR.bits
 
 
 # ------------------------------------------------------------------ 1. independent reconstruction
@@ -52,104 +46,34 @@ def _hall(be):
     return b, cam, (72, 56)
 
 
-def _albedo(orc, b, desc, mat, uv):
-    """the table of include/fountain_hip_gbuffer.h, in f32; textured parameters from the hit's uv (checkerboard / uv need no differentials)"""
-    m = desc.materials[mat]
-    a, bb = np.array(m.a[:], F32), np.array(m.b[:], F32)
-    ta = b.material_textures[mat][0]
-    if ta >= 0:
-        a = _tex_eval(b, ta, uv)
-    pos = lambda v: np.where(v < 0, F32(0), v).astype(F32)
-    if m.type in (A.FTN_MAT_MATTE, A.FTN_MAT_MIRROR):
-        return pos(a)
-    if m.type == A.FTN_MAT_PLASTIC:
-        return (a + bb).astype(F32)
-    if m.type == A.FTN_MAT_GLASS:
-        return (pos(a) + pos(bb)).astype(F32)
-    out = (C.c_float * 3)()
-    orc.lib.orc_kat_fresnel_conductor(C.c_float(1.0), (C.c_float * 3)(*a), (C.c_float * 3)(*bb), out)
-    return np.array(out[:], F32)
-
-
-def _tex_eval(b, idx, uv):
-    t = b.textures[idx]
-    if t.kind == A.FTN_TEX_CONSTANT:
-        return np.array(t.value[:], F32)
-    s = F32(F32(t.su) * uv[0]) + F32(t.du)
-    tt = F32(F32(t.sv) * uv[1]) + F32(t.dv)
-    if t.kind == A.FTN_TEX_UV:
-        return np.array([s - np.floor(s), tt - np.floor(tt), 0.0], F32)
-    assert t.kind == A.FTN_TEX_CHECKERBOARD
-    return _tex_eval(b, t.tex1 if (int(np.floor(s)) + int(np.floor(tt))) % 2 == 0 else t.tex2, uv)
-
-
-def reconstruct(gpu, orc, make, spp, seed, crop, tiles):
-    """film.rs:133-160 in f32 over the samples ftn_render takes, rays from orc_kat_camera_ray, hits from the oracle's BVH"""
-    b, cam, res = make(orc)
-    sc = b.create_scene()
-    film = Film(orc, res, crop)
-    desc, (_, order) = sc.desc, sc.nodes()
-    c2w_inv = A.ftn_transform()
-    c2w_inv.m[:] = cam.desc.camera_to_world.inv[:]
-    c2w_inv.inv[:] = cam.desc.camera_to_world.m[:]
-    u5, o6, p3 = (C.c_float * 5)(), (C.c_float * 6)(), (C.c_float * 3)()
-    samples, rays = [], []
-    for (x0, y0, x1, y1) in selected_tiles(film, tiles):
-        for py in range(y0, y1):
-            for px in range(x0, x1):
-                for s in range(spp):
-                    orc.lib.orc_kat_indexed_f32(C.c_uint64(seed), C.c_int32(px), C.c_int32(py), C.c_uint32(s), u5, C.c_size_t(5))
-                    u = np.array(u5[:], F32)
-                    pf = (F32(px) + u[0], F32(py) + u[1])
-                    orc.lib.orc_kat_camera_ray(C.byref(cam.desc), (C.c_float * 5)(pf[0], pf[1], u[2], u[3], u[4]), o6)
-                    rays.append(list(o6[:]) + [np.inf, 0.0])
-                    samples.append((px, py, pf[0], pf[1]))
-    rays = np.array(rays, F32)
-    _, prim, _, _ = sc.intersect(rays, stats=False)
-    full = sc.intersect_full(rays)
-    c = film.desc.crop
-    acc = np.zeros((film.height, film.width, 12), F32)
-    spilled = np.zeros((film.height, film.width), bool)
-    n_spill = 0
-    for i, (px, py, pfx, pfy) in enumerate(samples):
-        rec = np.zeros(10, F32)
-        hit = prim[i] >= 0
-        if hit:
-            mat = desc.prims[int(order[prim[i]])].material
-            assert mat >= 0, "no null materials in these scenes"
-            gpu.call("transform_point", C.byref(c2w_inv), (C.c_float * 3)(*full[i, 0:3]), p3)
-            rec = np.concatenate([_albedo(orc, b, desc, mat, full[i, 9:11]), full[i, 20:23], full[i, 0:3], [p3[2]]]).astype(F32)
-        pdx, pdy = F32(pfx - F32(0.5)), F32(pfy - F32(0.5))
-        x0, y0 = int(np.ceil(pdx - F32(0.5))), int(np.ceil(pdy - F32(0.5)))
-        x1, y1 = int(np.floor(pdx + F32(0.5))) + 1, int(np.floor(pdy + F32(0.5))) + 1
-        x0, y0, x1, y1 = max(x0, c[0]), max(y0, c[1]), min(x1, c[2]), min(y1, c[3])
-        touched = [(x, y) for y in range(y0, y1) for x in range(x0, x1)]
-        if len(touched) != 1:
-            n_spill += 1
-        for (x, y) in touched:
-            a = acc[y - c[1], x - c[0]]
-            if hit:
-                a[:10] += rec * F32(1.0)
-                a[10] += F32(1.0)
-            a[11] += F32(1.0)
-            if len(touched) != 1:
-                spilled[y - c[1], x - c[0]] = True
-    return acc, spilled, n_spill, len(samples)
-
-
 @pytest.mark.parametrize("which", ["cornell", "hall"])
 def test_independent_reconstruction(gpu, orc_det, which):
     make = {"cornell": lambda be: scenes.cornell(be, res=48), "hall": _hall}[which]
     spp, seed, crop, tiles = 3, 12345, (0.1, 0.15, 0.95, 0.9), (1, 2, 0)
-    want, spilled, n_spill, n = reconstruct(gpu, orc_det, make, spp, seed, crop, tiles)
+    ref = GR.reconstruct(gpu, orc_det, make, spp, seed, crop, tiles)
     b, cam, res = make(gpu)
     res_g, raw, st = G.render_gbuffer(gpu, b, cam, res, RandomSampler(spp, seed, indexed=True), tiles=tiles, crop=crop)
-    assert st["camera_samples"] == n and st["spill_samples"] == n_spill and st["rays_closest"] == n
-    diff = (bits(raw) != bits(want)).any(axis=-1)
-    assert not (diff & ~spilled).any(), "%s: %d pixels differ outside spill pixels" % (which, int((diff & ~spilled).sum()))
-    assert np.allclose(raw, want, rtol=2e-6, atol=1e-6)
+    assert st["camera_samples"] == ref["n"] and st["spill_samples"] == ref["n_spill"] and st["rays_closest"] == ref["n"]
+    GR.assert_matches(raw, ref, which)
+    assert np.allclose(raw, ref["acc"], rtol=2e-6, atol=1e-6)
     assert (raw[..., 10] > 0).any()
     assert len({tuple(v) for v in res_g["albedo"][raw[..., 10] > 0].reshape(-1, 3).tolist()}) > 4
+
+
+@pytest.mark.parametrize("radius", [(1.25, 1.25), (1.5, 0.75), (0.5, 0.5)])
+@pytest.mark.parametrize("crop,tiles", [((0.1, 0.15, 0.95, 0.9), (1, 2, 0)), ((0.0, 0.0, 1.0, 1.0), (0, 3, 5))])
+def test_reconstruction_with_wide_filters(gpu, orc_det, radius, crop, tiles):
+    """footprints clipped to get_film_tile's pixel bounds (p1y with the reference's - radius) and the crop: weights bit-equal
+    everywhere, values bit-equal where no sample of another pixel landed and within the reordering bound of a float sum elsewhere"""
+    spp, seed = 2, 4242
+    ref = GR.reconstruct(gpu, orc_det, _hall, spp, seed, crop, tiles, radius=radius)
+    b, cam, res = _hall(gpu)
+    _, raw, st = G.render_gbuffer(gpu, None, cam, res, RandomSampler(spp, seed, indexed=True), tiles=tiles, scene=b.create_scene(),
+                                  film=GR.film(gpu, res, crop, radius))
+    assert st["camera_samples"] == ref["n"] and st["spill_samples"] == ref["n_spill"] and st["rays_closest"] == ref["rays"]
+    if radius[0] > 0.5:
+        assert ref["n_spill"] > 0.9 * ref["n"] and ref["foreign"].mean() > 0.3
+    GR.assert_matches(raw, ref, "radius %r" % (radius,))
 
 
 # ------------------------------------------------------------------ 2. the beauty's samples
@@ -163,6 +87,21 @@ def test_weights_equal_the_beauty(gpu, pipeline):
     assert np.array_equal(bits(raw[..., 11]), bits(px[..., 3]))
     assert st["camera_samples"] == st_b["camera_samples"] and st["spill_samples"] == st_b["spill_samples"]
     assert st["kernel_ms"] > 0 and 0 < st["trace_ms"] <= st["kernel_ms"]
+
+
+@pytest.mark.parametrize("radius", [(1.25, 1.25), (1.5, 0.75)])
+@pytest.mark.parametrize("pipeline", [AUTO, WAVE])
+def test_weights_equal_the_beauty_with_wide_filters(gpu, pipeline, radius):
+    """nearly every sample spills: the whole-number weights still equal the beauty's filter_weight_sum bit for bit"""
+    spp, crop, tiles = 5, (0.05, 0.1, 0.8, 0.97), (0, 2, 0)
+    smp = RandomSampler(spp, 77, indexed=True)
+    b, cam, res = scenes.cornell(gpu, res=64)
+    scene = b.create_scene()
+    film = GR.film(gpu, res, crop, radius)
+    st_b = SamplerIntegrator(cam, PathIntegrator(3, 1.0)).render_parallel(scene, film, smp, tiles=tiles, pipeline=pipeline)
+    _, raw, st = G.render_gbuffer(gpu, None, cam, res, smp, tiles=tiles, scene=scene, pipeline=pipeline, film=GR.film(gpu, res, crop, radius))
+    assert np.array_equal(bits(raw[..., 11]), bits(film.pixels[..., 3]))
+    assert st["camera_samples"] == st_b["camera_samples"] and st["spill_samples"] == st_b["spill_samples"] > 0.9 * st["camera_samples"]
 
 
 # ------------------------------------------------------------------ 3. null materials
@@ -218,6 +157,74 @@ def test_sample_splits_and_device_path(gpu):
     assert np.array_equal(bits(out.cpu().numpy()), bits(want))
 
 
+def test_shared_spill_accumulators(gpu, orc_det):
+    """the G-buffer's spill sums live in the scene's beauty accumulators, cleared lazily: on one scene handle, G-buffer and beauty calls
+    with wide and default filters in turn each equal their own reference, so nothing one call leaves there reaches the next"""
+    spp, seed, crop, wide = 2, 31, (0.1, 0.05, 0.9, 0.95), (1.25, 1.25)
+    refs = {r: GR.reconstruct(gpu, orc_det, _hall, spp, seed, crop, None, radius=r) for r in (wide, (0.5, 0.5))}
+    b, cam, res = _hall(gpu)
+    bo, camo, _ = _hall(orc_det)
+    scene, scene_o = b.create_scene(), bo.create_scene()
+    smp = RandomSampler(spp, seed, indexed=True)
+    integ = PathIntegrator(3, 1.0)
+    steps = ["gbuffer wide", "beauty default", "gbuffer default", "beauty wide", "gbuffer default", "beauty wide", "gbuffer wide",
+             "gbuffer wide"]
+    for i, step in enumerate(steps):
+        kind, which = step.split()
+        radius = wide if which == "wide" else (0.5, 0.5)
+        what = "step %d (%s)" % (i, step)
+        if kind == "gbuffer":
+            _, raw, st = G.render_gbuffer(gpu, None, cam, res, smp, scene=scene, film=GR.film(gpu, res, crop, radius))
+            assert st["spill_samples"] == refs[radius]["n_spill"], what
+            GR.assert_matches(raw, refs[radius], what)
+        else:
+            f, fo = GR.film(gpu, res, crop, radius), GR.film(orc_det, res, crop, radius)
+            st = SamplerIntegrator(cam, integ).render_parallel(scene, f, smp, pipeline=WAVE)
+            SamplerIntegrator(camo, integ).render_parallel(scene_o, fo, smp)
+            assert np.array_equal(bits(f.pixels[..., 3]), bits(fo.pixels[..., 3])), what
+            if which == "default":
+                assert st["spill_samples"] == 0 and np.array_equal(bits(f.pixels), bits(fo.pixels)), what
+            else:
+                assert np.allclose(f.pixels, fo.pixels, rtol=1e-5, atol=1e-6), what
+
+
+def test_several_passes(gpu, monkeypatch):
+    """FTN_WF_PATHS_M=1 on a 256^2 film (256 tiles of 256 slots): passes of 16 samples, so 37 spp runs as 16 + 16 + 5 (the last with
+    a chunk remainder below GB_ACC_CHUNK), and a range starting at sample 5 as 16 + 16 from an offset; every way gives the bits of one
+    default pass"""
+    spp, seed = 37, 8
+    b, cam, res = scenes.cornell(gpu, res=256)
+    scene = b.create_scene()
+    _, one, st1 = G.render_gbuffer(gpu, None, cam, res, RandomSampler(spp, seed, indexed=True), scene=scene)
+    assert st1["camera_samples"] == spp * 256 * 256
+    # a sample whose jitter is exactly 0 also lands on the pixel to its left or above: such pixels (weight above spp) get it through
+    # the spill sums, which every call adds at its end, so a split call may round them differently
+    foreign = one[..., 11] != spp
+    assert foreign.sum() <= 4 * st1["spill_samples"]
+
+    def same(got, what, split):
+        assert np.array_equal(bits(got[..., 10:]), bits(one[..., 10:])), what
+        if split:
+            assert np.array_equal(bits(got[~foreign]), bits(one[~foreign])), what
+            assert np.allclose(got, one, rtol=2e-6, atol=1e-6), what
+        else:
+            assert np.array_equal(bits(got), bits(one)), what
+
+    monkeypatch.setenv("FTN_WF_PATHS_M", "1")
+    _, passes, st = G.render_gbuffer(gpu, None, cam, res, RandomSampler(spp, seed, indexed=True), scene=scene)
+    assert st["camera_samples"] == st1["camera_samples"] and st["rays_closest"] == st1["rays_closest"]
+    assert st["spill_samples"] == st1["spill_samples"]
+    same(passes, "passes of 16 + 16 + 5", False)
+    for k in (5, 16, 21):
+        _, two, _ = G.render_gbuffer(gpu, None, cam, res, RandomSampler(spp, seed, indexed=True, first_sample=0, sample_count=k), scene=scene)
+        G.render_gbuffer(gpu, None, cam, res, RandomSampler(spp, seed, indexed=True, first_sample=k, sample_count=spp - k), scene=scene, raw=two)
+        same(two, "split at %d" % k, True)
+    monkeypatch.delenv("FTN_WF_PATHS_M")
+    _, two, _ = G.render_gbuffer(gpu, None, cam, res, RandomSampler(spp, seed, indexed=True, first_sample=0, sample_count=5), scene=scene)
+    G.render_gbuffer(gpu, None, cam, res, RandomSampler(spp, seed, indexed=True, first_sample=5, sample_count=spp - 5), scene=scene, raw=two)
+    same(two, "split at 5, one pass each", True)
+
+
 # ------------------------------------------------------------------ 5. image textures
 def test_constant_image_texture(gpu):
     col = np.array([0.3, 0.55, 0.8], F32)
@@ -231,6 +238,42 @@ def test_constant_image_texture(gpu):
     assert (raw[..., 10] == 1.0).all()
     ulp = np.spacing(col)
     assert (np.abs(r["albedo"] - col) <= 2 * ulp).all(), np.abs(r["albedo"] - col).max(axis=(0, 1)) / ulp
+
+
+@pytest.mark.parametrize("radius,tiles", [((0.5, 0.5), None), ((1.25, 1.25), (1, 2, 0))])
+def test_image_textured_albedo(gpu, orc_det, radius, tiles):
+    """a non-constant image map on a grazing floor (MIP levels from the finest to coarse ones) and an image-textured quad under a
+    null-material layer (the camera differentials pass through unchanged): the albedo follows the oracle's texture lookup with the
+    camera differentials scaled by 1 / sqrt(spp)"""
+    spp, seed, crop = 4, 606, (0.0, 0.0, 1.0, 1.0)
+    ref = GR.reconstruct(gpu, orc_det, GR.textured_floor, spp, seed, crop, tiles, radius=radius)
+    assert ref["rays"] > ref["n"] + 100                                        # samples passed through the null layer
+    w = np.log2(np.array(ref["tex_width"]))
+    assert w.max() - w.min() > 4, (w.min(), w.max())                          # footprints span several MIP levels
+    b, cam, res = GR.textured_floor(gpu)
+    _, raw, st = G.render_gbuffer(gpu, None, cam, res, RandomSampler(spp, seed, indexed=True), tiles=tiles, scene=b.create_scene(),
+                                  film=GR.film(gpu, res, crop, radius))
+    assert st["camera_samples"] == ref["n"] and st["rays_closest"] == ref["rays"] and st["spill_samples"] == ref["n_spill"]
+    GR.assert_matches(raw, ref, "image textures, radius %r" % (radius,))
+
+
+def test_resolve_on_rendered_buffers(gpu):
+    """ftn_gbuffer_resolve and ftn_gbuffer_resolve_device against the float32 restatement, bit for bit: sky misses (H = 0), partial
+    coverage under a wide filter, pixels of unselected tiles (W = 0)"""
+    import torch
+    b, cam, res = GR.textured_floor(gpu)
+    _, raw, _ = G.render_gbuffer(gpu, None, cam, res, RandomSampler(3, 2, indexed=True), tiles=(0, 2, 0), scene=b.create_scene(),
+                                 film=GR.film(gpu, res, (0.0, 0.0, 1.0, 1.0), (1.25, 1.25)))
+    h, w = raw[..., 10], raw[..., 11]
+    assert (w == 0).any() and ((h == 0) & (w > 0)).any() and ((h > 0) & (h < w)).any() and ((h > 0) & (h == w)).any()
+    want = GR.resolve_ref(raw)
+    host = G.resolve(gpu, raw)
+    assert np.array_equal(bits(np.concatenate([host[k] for k in G.CHANNELS], axis=-1)), bits(want))
+    t = torch.from_numpy(raw).cuda()
+    out = torch.full_like(t, float("nan"))
+    G.resolve_torch(gpu, t, out)
+    torch.cuda.synchronize()
+    assert np.array_equal(bits(out.cpu().numpy()), bits(want))
 
 
 # ------------------------------------------------------------------ 6. refusals
