@@ -162,6 +162,14 @@ FTN_DENOISE_DEMODULATE = 1
 FTN_DENOISE_MAX_LEVELS = 10
 FTN_DENOISE_ABI_VERSION = 1  # include/fountain_hip_denoise.h (an extension with a version of its own)
 
+
+class ftn_moment_pixel(C.Structure):
+    """include/fountain_hip_moments.h: per-pixel sums of the squares of the samples' radiance (box filter weight 1)."""
+    _fields_ = [("sq", c_f * 3), ("sq_y", c_f)]
+
+
+FTN_MOMENTS_ABI_VERSION = 1  # include/fountain_hip_moments.h (an extension with a version of its own)
+
 FTN_ABI_VERSION = 3          # include/fountain_hip.h; Backend() refuses a product library that reports another one
 
 # Expected sizes (bytes) -- asserted against the header by the C side's static_asserts and tests/test_abi.py
@@ -170,7 +178,7 @@ SIZES = {
     "ftn_sphere": 288, "ftn_material": 48, "ftn_light": 160, "ftn_envmap": 16, "ftn_camera_desc": 296,
     "ftn_film_desc": 32, "ftn_sampler_desc": 24, "ftn_integrator_desc": 16, "ftn_tile_range": 16,
     "ftn_render_options": 16, "ftn_stats": 152, "ftn_scene_memory": 96, "ftn_texture": 48, "ftn_image": 24, "ftn_material_textures": 32,
-    "ftn_gbuffer_pixel": 48, "ftn_denoise_params": 32,
+    "ftn_gbuffer_pixel": 48, "ftn_denoise_params": 32, "ftn_moment_pixel": 16,
 }
 
 # Every function the header declares (name -> None); used by the symbol-export test.
@@ -200,4 +208,10 @@ GBUFFER_FUNCTIONS = [
 DENOISE_FUNCTIONS = [
     "ftn_denoise_params_default", "ftn_denoise", "ftn_denoise_workspace_size", "ftn_denoise_device", "ftn_denoise_cpu",
     "ftn_denoise_abi_version",
+]
+
+# Every function the extension header include/fountain_hip_moments.h declares (kept apart from the lists above: the reference keeps no
+# second moments, so these have no orc_* twin either).
+MOMENTS_FUNCTIONS = [
+    "ftn_render_moments", "ftn_render_moments_device", "ftn_moments_resolve", "ftn_moments_resolve_device", "ftn_moments_abi_version",
 ]

@@ -10,7 +10,9 @@ samples run in parallel (samplers).  --gbuffer also writes the fi
 (fountain_amd/gbuffer.py) beside the image: <name>_albedo.exr, <name>_normal.exr, <name>_position.exr and <name>_depth.exr (camera-space
 depth repeated in R, G and B); it needs the default sampler and one GPU.  --denoise then renders that G-buffer (also without
 --gbuffer) and writes <name>_denoised.exr: the image filtered by the edge-avoiding a-trous denoiser (fountain_amd/denoise.py, default
-parameters); the image itself is written unchanged.  It has the same needs as --gbuffer.
+parameters); the image itself is written unchanged.  It has the same needs as --gbuffer.  --variance renders the image together with
+the second moments of its camera samples (fountain_amd/moments.py), the same pixels bit for bit, and writes <name>_variance.exr: the
+estimated variance of each pixel's mean in R, G and B (+inf where a pixel has fewer than 2 samples).  It has the same needs as --gbuffer.
 """
 import argparse
 import sys
@@ -33,8 +35,9 @@ def main(argv=None):
     ap.add_argument("--gpus", type=int, default=None, help="render on N GPUs of this node: film tiles r, r+N, ... per rank, one reduce at the end")
     ap.add_argument("--gbuffer", action="store_true", help="also write the first-hit albedo / normal / position / depth buffers as <name>_<buffer>.exr")
     ap.add_argument("--denoise", action="store_true", help="also write <name>_denoised.exr, the image denoised with the first-hit G-buffer of its camera samples")
+    ap.add_argument("--variance", action="store_true", help="also write <name>_variance.exr, the estimated variance of each pixel's mean (r, g, b)")
     opts = ap.parse_args(argv)
-    for flag, on in (("--gbuffer", opts.gbuffer), ("--denoise", opts.denoise)):
+    for flag, on in (("--gbuffer", opts.gbuffer), ("--denoise", opts.denoise), ("--variance", opts.variance)):
         if on and opts.exact_stream:
             print("error: %s needs the default sampler: with --exact-stream a sample's camera ray depends on everything its tile drew before it" % flag, file=sys.stderr)
             return 2
@@ -48,8 +51,9 @@ def main(argv=None):
         # started plainly: start the N ranks as a child process (before anything here has touched HIP) and hand back its exit code
         return spawn_ranks(opts.gpus, sys.argv[1:] if argv is None else list(argv), module="fountain_amd.render")
     world, rank = (env_world[0], env_world[1]) if env_world is not None else (1, 0)
-    if (opts.gbuffer or opts.denoise) and world > 1:
-        print("error: %s renders on one GPU, not under a launcher of %d ranks" % ("--gbuffer" if opts.gbuffer else "--denoise", world), file=sys.stderr)
+    if (opts.gbuffer or opts.denoise or opts.variance) and world > 1:
+        flag = "--gbuffer" if opts.gbuffer else "--denoise" if opts.denoise else "--variance"
+        print("error: %s renders on one GPU, not under a launcher of %d ranks" % (flag, world), file=sys.stderr)
         return 2
     if opts.gpus is not None and opts.gpus != world:
         print("error: --gpus %d but the launcher started WORLD_SIZE %d ranks" % (opts.gpus, world), file=sys.stderr)
@@ -89,6 +93,10 @@ def main(argv=None):
         dist.destroy_process_group()
         if rank != 0:
             return 0
+    elif opts.variance:
+        # the beauty of ftn_render, bit for bit, with the moments of its samples beside it
+        from .moments import render_moments
+        variance, _, _, st = render_moments(be, None, parsed.camera, None, integrator.radiance, sampler, scene=scene, film=film, device=opts.gpu)
     else:
         st = integrator.render_parallel(scene, film, sampler, device=opts.gpu)
     dt = time.time() - t0
@@ -100,6 +108,10 @@ def main(argv=None):
         gb = write_gbuffer(be, scene, parsed.camera, film, sampler, filename, opts.gpu, write=opts.gbuffer)
         if opts.denoise:
             write_denoised(be, img, gb, filename, opts.gpu)
+    if opts.variance:
+        path = variance_path(filename)
+        write_exr(path, variance[..., :3], be)
+        print("variance: %s" % path, file=sys.stderr)
     return 0
 
 
@@ -113,6 +125,12 @@ def denoised_path(filename):
     """out.exr -> out_denoised.exr"""
     base = filename[:-4] if filename.endswith(".exr") else filename
     return "%s_denoised.exr" % base
+
+
+def variance_path(filename):
+    """out.exr -> out_variance.exr"""
+    base = filename[:-4] if filename.endswith(".exr") else filename
+    return "%s_variance.exr" % base
 
 
 def write_gbuffer(be, scene, camera, film, sampler, filename, device, write=True):
