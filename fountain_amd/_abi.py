@@ -170,6 +170,22 @@ class ftn_moment_pixel(C.Structure):
 
 FTN_MOMENTS_ABI_VERSION = 1  # include/fountain_hip_moments.h (an extension with a version of its own)
 
+
+class ftn_adaptive_params(C.Structure):
+    """include/fountain_hip_adaptive.h: the schedule and criterion of per-tile adaptive sampling (ftn_adaptive_params_default fills them)."""
+    _fields_ = [("min_samples", c_u32), ("step_samples", c_u32), ("threshold", c_f), ("abs_floor", c_f)]
+
+
+class ftn_adaptive_info(C.Structure):
+    """include/fountain_hip_adaptive.h: what an adaptive call did (rounds, tiles, tiles that reached N, samples in the crop)."""
+    _fields_ = [("rounds", c_u32), ("tiles", c_u32), ("tiles_at_max", c_u32), ("_pad", c_u32), ("pixel_samples", c_u64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "_pad"}
+
+
+FTN_ADAPTIVE_ABI_VERSION = 1  # include/fountain_hip_adaptive.h (an extension with a version of its own)
+
 FTN_ABI_VERSION = 3          # include/fountain_hip.h; Backend() refuses a product library that reports another one
 
 # Expected sizes (bytes) -- asserted against the header by the C side's static_asserts and tests/test_abi.py
@@ -178,7 +194,7 @@ SIZES = {
     "ftn_sphere": 288, "ftn_material": 48, "ftn_light": 160, "ftn_envmap": 16, "ftn_camera_desc": 296,
     "ftn_film_desc": 32, "ftn_sampler_desc": 24, "ftn_integrator_desc": 16, "ftn_tile_range": 16,
     "ftn_render_options": 16, "ftn_stats": 152, "ftn_scene_memory": 96, "ftn_texture": 48, "ftn_image": 24, "ftn_material_textures": 32,
-    "ftn_gbuffer_pixel": 48, "ftn_denoise_params": 32, "ftn_moment_pixel": 16,
+    "ftn_gbuffer_pixel": 48, "ftn_denoise_params": 32, "ftn_moment_pixel": 16, "ftn_adaptive_params": 16, "ftn_adaptive_info": 24,
 }
 
 # Every function the header declares (name -> None); used by the symbol-export test.
@@ -214,4 +230,10 @@ DENOISE_FUNCTIONS = [
 # second moments, so these have no orc_* twin either).
 MOMENTS_FUNCTIONS = [
     "ftn_render_moments", "ftn_render_moments_device", "ftn_moments_resolve", "ftn_moments_resolve_device", "ftn_moments_abi_version",
+]
+
+# Every function the extension header include/fountain_hip_adaptive.h declares (kept apart from the lists above: the reference has no
+# adaptive sampling, so these have no orc_* twin either).
+ADAPTIVE_FUNCTIONS = [
+    "ftn_adaptive_params_default", "ftn_render_adaptive", "ftn_render_adaptive_device", "ftn_adaptive_converged", "ftn_adaptive_abi_version",
 ]

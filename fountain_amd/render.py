@@ -13,6 +13,10 @@ depth repeated in R, G and B); it needs the default sampler and one GPU.  --deno
 parameters); the image itself is written unchanged.  It has the same needs as --gbuffer.  --variance renders the image together with
 the second moments of its camera samples (fountain_amd/moments.py), the same pixels bit for bit, and writes <name>_variance.exr: the
 estimated variance of each pixel's mean in R, G and B (+inf where a pixel has fewer than 2 samples).  It has the same needs as --gbuffer.
+--adaptive T renders with per-tile adaptive sampling (fountain_amd/adaptive.py): every 16x16 tile gets --min-samples samples (default
+8, at most the samples per pixel), then twice as many, and so on up to --samples, until the estimated relative standard error of
+each of its pixels' mean luminance is at most T.  It writes <name>_spp.exr beside the image: each pixel's final sample count in R, G and B.  --variance works with it (from
+the same moments); --gbuffer, --denoise, --exact-stream and more than one GPU do not.
 """
 import argparse
 import sys
@@ -36,7 +40,23 @@ def main(argv=None):
     ap.add_argument("--gbuffer", action="store_true", help="also write the first-hit albedo / normal / position / depth buffers as <name>_<buffer>.exr")
     ap.add_argument("--denoise", action="store_true", help="also write <name>_denoised.exr, the image denoised with the first-hit G-buffer of its camera samples")
     ap.add_argument("--variance", action="store_true", help="also write <name>_variance.exr, the estimated variance of each pixel's mean (r, g, b)")
+    ap.add_argument("--adaptive", type=float, default=None, metavar="T",
+                    help="per-tile adaptive sampling up to --samples: stop a tile once its pixels' relative standard error is at most T; also writes <name>_spp.exr")
+    ap.add_argument("--min-samples", type=int, default=None, help="with --adaptive: the samples every tile gets first (default 8)")
     opts = ap.parse_args(argv)
+    if opts.min_samples is not None and opts.adaptive is None:
+        print("error: --min-samples belongs to --adaptive", file=sys.stderr)
+        return 2
+    if opts.adaptive is not None:
+        for flag, on in (("--exact-stream", opts.exact_stream), ("--gbuffer", opts.gbuffer), ("--denoise", opts.denoise),
+                         ("more than one GPU (--gpus)", opts.gpus is not None and opts.gpus > 1)):
+            if on:
+                print("error: --adaptive does not work with %s: it renders each tile at its own sample count on one GPU with the default sampler"
+                      " (a G-buffer and the denoiser would have to follow those counts)" % flag, file=sys.stderr)
+                return 2
+        if not opts.adaptive >= 0.0 or opts.adaptive == float("inf"):
+            print("error: --adaptive takes a finite threshold >= 0", file=sys.stderr)
+            return 2
     for flag, on in (("--gbuffer", opts.gbuffer), ("--denoise", opts.denoise), ("--variance", opts.variance)):
         if on and opts.exact_stream:
             print("error: %s needs the default sampler: with --exact-stream a sample's camera ray depends on everything its tile drew before it" % flag, file=sys.stderr)
@@ -51,8 +71,8 @@ def main(argv=None):
         # started plainly: start the N ranks as a child process (before anything here has touched HIP) and hand back its exit code
         return spawn_ranks(opts.gpus, sys.argv[1:] if argv is None else list(argv), module="fountain_amd.render")
     world, rank = (env_world[0], env_world[1]) if env_world is not None else (1, 0)
-    if (opts.gbuffer or opts.denoise or opts.variance) and world > 1:
-        flag = "--gbuffer" if opts.gbuffer else "--denoise" if opts.denoise else "--variance"
+    if (opts.gbuffer or opts.denoise or opts.variance or opts.adaptive is not None) and world > 1:
+        flag = "--gbuffer" if opts.gbuffer else "--denoise" if opts.denoise else "--variance" if opts.variance else "--adaptive"
         print("error: %s renders on one GPU, not under a launcher of %d ranks" % (flag, world), file=sys.stderr)
         return 2
     if opts.gpus is not None and opts.gpus != world:
@@ -66,9 +86,16 @@ def main(argv=None):
     filename = opts.image_name or parsed.film_name
     if ".exr" not in filename:
         raise SystemExit("output must be an .exr file (render.rs:53)")
+    sampler = parsed.sampler(opts.samples, indexed=not opts.exact_stream)
+    if opts.adaptive is not None:
+        # min_samples: --min-samples, or 8 (the library's default) but at most the samples per pixel
+        n_max = sampler.desc.samples_per_pixel
+        opts.min_samples = opts.min_samples if opts.min_samples is not None else min(8, n_max)
+        if not 2 <= opts.min_samples <= n_max:
+            print("error: --adaptive needs 2 <= --min-samples <= samples per pixel (here %d and %d)" % (opts.min_samples, n_max), file=sys.stderr)
+            return 2
     scene = parsed.create_scene(device=opts.gpu)
     film = parsed.film()
-    sampler = parsed.sampler(opts.samples, indexed=not opts.exact_stream)
     integrator = SamplerIntegrator(parsed.camera, PathIntegrator.new(opts.max_depth, opts.rr_threshold))
     info = scene.info()
     print("scene: %d primitives, %d BVH nodes, %d lights" % (info["n_prims"], info["n_nodes"], info["n_lights"]), file=sys.stderr)
@@ -93,6 +120,18 @@ def main(argv=None):
         dist.destroy_process_group()
         if rank != 0:
             return 0
+    elif opts.adaptive is not None:
+        # each tile at its own sample count, with the moments that decided it beside the beauty
+        from .adaptive import params, render_adaptive
+        from .moments import resolve
+        kw = dict(threshold=opts.adaptive, min_samples=opts.min_samples)
+        _, moments, counts, ainfo, st = render_adaptive(be, None, parsed.camera, None, integrator.radiance, sampler, params(be, **kw), scene=scene,
+                                                        film=film, device=opts.gpu)
+        if opts.variance:
+            variance = resolve(be, film.pixels, moments)
+        print("adaptive: %d rounds, %d of %d tiles at %d samples, %.2f samples per pixel" % (
+            ainfo["rounds"], ainfo["tiles_at_max"], ainfo["tiles"], sampler.desc.samples_per_pixel,
+            ainfo["pixel_samples"] / max(1, counts.size)), file=sys.stderr)
     elif opts.variance:
         # the beauty of ftn_render, bit for bit, with the moments of its samples beside it
         from .moments import render_moments
@@ -108,6 +147,11 @@ def main(argv=None):
         gb = write_gbuffer(be, scene, parsed.camera, film, sampler, filename, opts.gpu, write=opts.gbuffer)
         if opts.denoise:
             write_denoised(be, img, gb, filename, opts.gpu)
+    if opts.adaptive is not None:
+        import numpy as np
+        path = spp_path(filename)
+        write_exr(path, np.repeat(counts.astype(np.float32)[..., None], 3, axis=-1), be)
+        print("samples per pixel: %s" % path, file=sys.stderr)
     if opts.variance:
         path = variance_path(filename)
         write_exr(path, variance[..., :3], be)
@@ -131,6 +175,12 @@ def variance_path(filename):
     """out.exr -> out_variance.exr"""
     base = filename[:-4] if filename.endswith(".exr") else filename
     return "%s_variance.exr" % base
+
+
+def spp_path(filename):
+    """out.exr -> out_spp.exr"""
+    base = filename[:-4] if filename.endswith(".exr") else filename
+    return "%s_spp.exr" % base
 
 
 def write_gbuffer(be, scene, camera, film, sampler, filename, device, write=True):
