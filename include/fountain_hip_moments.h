@@ -51,8 +51,11 @@ int ftn_render_moments_device(const ftn_scene* scene, const ftn_camera_desc* cam
  * f32 rounding in this order: mean = S / W; v = sq / W - mean * mean; v = v < 0 ? 0 : v; out = v / (W - 1).  NaN propagates.  The host
  * and the _device variant share one code path and agree bit for bit.
  * Precision: the one-pass formula cancels.  When the variance is small against mean^2 (bright, nearly constant pixels at high sample
- * counts) sq / W and mean^2 agree in most of their bits and the result keeps only about -log2(v / mean^2) of 24; a true variance below
- * about 2^-22 mean^2 can come out as 0 (clamped) or as that size of noise. */
+ * counts) sq / W and mean^2 agree in most of their bits, and a relative error e of the sums costs about 2 e mean^2 in v: a true variance
+ * below that can come out as 0 (clamped) or as that size of noise.  e grows with the sample count (W float32 additions: up to about
+ * W 2^-24); for r, g, b it also holds the round trip through the beauty's xyz (xyz_to_rgb's coefficients invert rgb_to_xyz's only to
+ * about 1e-6 of the three channels' sum).  At 64 samples a Y variance of 2^-21 mean^2, and an r, g or b variance above 2^-17 mean^2 in a
+ * channel small against the other two, can already come out as 0. */
 int ftn_moments_resolve(const ftn_pixel* beauty, const ftn_moment_pixel* moments, size_t n, float* out4);
 int ftn_moments_resolve_device(const void* beauty, const void* moments, size_t n, void* out4, void* stream);
 

@@ -163,9 +163,12 @@ int orc_intersect_full(const orc_scene* s, const float* rays, size_t n, float* o
 }
 
 // ---------------------------------------------------------------- render
-int orc_render(const orc_scene* s, const ftn_camera_desc* cam, const ftn_film_desc* fd, const ftn_sampler_desc* sd,
-               const ftn_integrator_desc* id, const ftn_tile_range* tr, int n_threads, int count_traffic,
-               ftn_pixel* out_pixels, ftn_stats* stats) {
+}  // extern "C"
+
+// orc_render's tile loop; with `records`, every camera sample is also written there (orc_render_sample_log's order)
+static int render_tiles(const orc_scene* s, const ftn_camera_desc* cam, const ftn_film_desc* fd, const ftn_sampler_desc* sd,
+                        const ftn_integrator_desc* id, const ftn_tile_range* tr, int n_threads, int count_traffic,
+                        ftn_pixel* out_pixels, ftn_stats* stats, SampleRecord* records, size_t capacity, size_t* n_records) {
     SceneData& scene = const_cast<SceneData&>(s->data);
     scene.count_traffic = count_traffic != 0;
     scene.rays_closest = 0; scene.rays_any = 0; scene.nodes_visited = 0; scene.prims_tested = 0; scene.nodes_any = 0; scene.prims_any = 0; scene.error = 0;
@@ -190,6 +193,13 @@ int orc_render(const orc_scene* s, const ftn_camera_desc* cam, const ftn_film_de
     std::vector<size_t> sel;
     uint32_t stride = tr && tr->stride ? tr->stride : 1, first = tr ? tr->first : 0, count = tr ? tr->count : 0;
     for (size_t i = first, k = 0; i < all_tiles.size() && (count == 0 || k < count); i += stride, k++) sel.push_back(i);
+    // each selected tile's records start where the previous tile's end
+    std::vector<size_t> rec_off(sel.size() + 1, 0);
+    for (size_t k = 0; k < sel.size(); k++)
+        rec_off[k + 1] = rec_off[k] + (size_t)std::max(all_tiles[sel[k]].area(), 0) * (size_t)(base.last_sample - base.first_sample);
+    if (n_records) *n_records = rec_off.back();
+    if (n_records && !records) return 0;
+    if (records && capacity < rec_off.back()) return fail(FTN_ERR_INVALID_ARGUMENT, "record buffer too small");
 
     std::vector<FilmTile> done(sel.size());
     std::vector<TileStats> tstats(sel.size());
@@ -200,7 +210,7 @@ int orc_render(const orc_scene* s, const ftn_camera_desc* cam, const ftn_film_de
             size_t k = next.fetch_add(1); if (k >= sel.size()) break;
             Bounds2i tile = all_tiles[sel[k]];
             uint64_t tile_id = (uint64_t)(int64_t)(tile.y0 * sb.x1 + tile.x0);   // tile_id: integrator/mod.rs:182-185
-            render_tile(scene, camera, film, it, base.clone_with_seed(tile_id), tile, &done[k], &tstats[k]);
+            render_tile(scene, camera, film, it, base.clone_with_seed(tile_id), tile, &done[k], &tstats[k], records ? records + rec_off[k] : nullptr, (uint32_t)k);
         }
     };
     if (n_threads <= 0) n_threads = (int)std::thread::hardware_concurrency();
@@ -209,7 +219,7 @@ int orc_render(const orc_scene* s, const ftn_camera_desc* cam, const ftn_film_de
     auto t1 = std::chrono::steady_clock::now();
     // merge in tile order (Film::render's order; render_parallel's order is scheduling dependent)
     uint64_t cs = 0, spill = 0;
-    for (size_t k = 0; k < sel.size(); k++) { film.merge_film_tile(done[k], out_pixels); cs += tstats[k].camera_samples; spill += tstats[k].spill_samples; }
+    for (size_t k = 0; k < sel.size(); k++) { if (out_pixels) film.merge_film_tile(done[k], out_pixels); cs += tstats[k].camera_samples; spill += tstats[k].spill_samples; }
     if (stats) {
         memset(stats, 0, sizeof(*stats));
         stats->rays_closest = scene.rays_closest; stats->rays_any = scene.rays_any;
@@ -221,6 +231,27 @@ int orc_render(const orc_scene* s, const ftn_camera_desc* cam, const ftn_film_de
     int err = scene.error.load();
     if (err) return fail(err, err == FTN_ERR_NAN_RADIANCE ? "NaN radiance" : (err == FTN_ERR_BVH_TOO_DEEP ? "BVH deeper than 64" : "unsupported material configuration"));
     return 0;
+}
+
+extern "C" {
+
+int orc_render(const orc_scene* s, const ftn_camera_desc* cam, const ftn_film_desc* fd, const ftn_sampler_desc* sd,
+               const ftn_integrator_desc* id, const ftn_tile_range* tr, int n_threads, int count_traffic,
+               ftn_pixel* out_pixels, ftn_stats* stats) {
+    return render_tiles(s, cam, fd, sd, id, tr, n_threads, count_traffic, out_pixels, stats, nullptr, 0, nullptr);
+}
+
+// Not a twin of an ftn_* function: orc_render's tile loop (the indexed sampler only), which writes one orc_sample_record per camera
+// sample -- selected-tile order, then row-major pixels within a tile, then increasing sample index (render_tile's order) -- and, when
+// out_pixels is not null, also adds the film as orc_render does.  With records null it only stores the record count in *n_records.
+struct orc_sample_record { int32_t px, py; uint32_t sample, tile; float p_film[2]; float L[3]; float ray_weight; };
+static_assert(sizeof(orc_sample_record) == sizeof(SampleRecord) && sizeof(orc_sample_record) == 40, "record layout");
+int orc_render_sample_log(const orc_scene* s, const ftn_camera_desc* cam, const ftn_film_desc* fd, const ftn_sampler_desc* sd,
+                          const ftn_integrator_desc* id, const ftn_tile_range* tr, int n_threads,
+                          orc_sample_record* records, size_t capacity, size_t* n_records, ftn_pixel* out_pixels, ftn_stats* stats) {
+    if (!s || !cam || !fd || !sd || !id || !n_records) return fail(FTN_ERR_INVALID_ARGUMENT, "null argument");
+    if (sd->kind != FTN_SAMPLER_INDEXED) return fail(FTN_ERR_UNSUPPORTED, "the sample log needs FTN_SAMPLER_INDEXED");
+    return render_tiles(s, cam, fd, sd, id, tr, n_threads, 0, out_pixels, stats, reinterpret_cast<SampleRecord*>(records), capacity, n_records);
 }
 
 // ---------------------------------------------------------------- known-answer hooks (reference unit tests)

@@ -387,8 +387,11 @@ inline Spectrum direct_li(const Integrator& it, RayDifferential& ray, const Scen
 
 // ---- SamplerIntegrator::render_tile: src/integrator/mod.rs:229-281
 struct TileStats { uint64_t camera_samples = 0, spill_samples = 0; };
+// one camera sample as the film tile receives it (the optional record sink of render_tile; not part of the reference)
+struct SampleRecord { int32_t px, py; uint32_t sample, tile; Float p_film[2]; Float L[3]; Float ray_weight; };
 inline void render_tile(const SceneData& scene, const Camera& camera, const Film& film, const Integrator& it,
-                        Sampler tile_sampler, Bounds2i tile, FilmTile* film_tile_out, TileStats* ts) {
+                        Sampler tile_sampler, Bounds2i tile, FilmTile* film_tile_out, TileStats* ts,
+                        SampleRecord* records = nullptr, uint32_t tile_index = 0) {
     FilmTile film_tile = film.get_film_tile(tile);
     for (int y = tile.y0; y < tile.y1; y++)
         for (int x = tile.x0; x < tile.x1; x++) {
@@ -403,6 +406,13 @@ inline void render_tile(const SceneData& scene, const Camera& camera, const Film
                     radiance = (it.kind == FTN_INTEGRATOR_DIRECT_LIGHTING || it.kind == FTN_INTEGRATOR_WHITTED) ? direct_li(it, rd, scene, tile_sampler, 0)
                                                                            : path_li(it, rd, scene, tile_sampler);
                     if (radiance.has_nans()) scene.error.store(FTN_ERR_NAN_RADIANCE);   // check_radiance :285-287
+                }
+                if (records) {                                                  // render_tile's order: pixels row-major, samples increasing
+                    SampleRecord& r = *records++;
+                    r.px = x; r.py = y; r.sample = tile_sampler.current_pixel_sample_num - 1; r.tile = tile_index;
+                    r.p_film[0] = cs.p_film.x; r.p_film[1] = cs.p_film.y;
+                    for (int c = 0; c < 3; c++) r.L[c] = radiance[c];
+                    r.ray_weight = ray_weight;
                 }
                 int touched = film.add_sample_to_tile(film_tile, cs.p_film, radiance, ray_weight);
                 ts->camera_samples++;

@@ -236,9 +236,10 @@ def resolve_ref(raw):
 
 
 # ------------------------------------------------------------------ scenes
-def textured_floor(be, res=(64, 48)):
+def textured_floor(be, res=(64, 48), null_layer=True):
     """a grazing floor with a non-constant image map (its far part takes coarse MIP levels), a small image-textured quad under a
-    null-material layer, a matte sphere and a sky the camera sees (an infinite light)"""
+    null-material layer, a matte sphere and a sky the camera sees (an infinite light).  Without the null layer (null_layer=False) the
+    direct-lighting and Whitted integrators accept it (they refuse a hit without a material)."""
     from fountain_amd import PerspectiveCamera, SceneBuilder, scenes
     rng = np.random.default_rng(17)
     img = rng.random((64, 64, 3)).astype(F32)
@@ -252,8 +253,9 @@ def textured_floor(be, res=(64, 48)):
     scenes._quad(b, (-20, -4, 0), (20, -4, 0), (20, 40, 0), (-20, 40, 0))
     b.material("matte", Kd="img2")
     scenes._quad(b, (0.3, -1.0, 0.4), (1.3, -1.0, 0.4), (1.3, 0.0, 0.9), (0.3, 0.0, 0.9))
-    b.material("none")
-    scenes._quad(b, (0.2, -1.1, 0.45), (1.4, -1.1, 0.45), (1.4, 0.1, 0.95), (0.2, 0.1, 0.95))
+    if null_layer:
+        b.material("none")
+        scenes._quad(b, (0.2, -1.1, 0.45), (1.4, -1.1, 0.45), (1.4, 0.1, 0.95), (0.2, 0.1, 0.95))
     b.attribute_begin(); b.material("matte", Kd=(0.3, 0.6, 0.3)); b.translate((-0.8, 0.2, 0.35)); b.shape("sphere", radius=0.35); b.attribute_end()
     cam = PerspectiveCamera.look_at(be, (0.0, -3.0, 0.6), (0.0, 6.0, 0.25), (0, 0, 1), res, fov=60.0)
     return b, cam, res

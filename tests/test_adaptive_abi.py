@@ -10,6 +10,8 @@ import pytest
 
 from fountain_amd import _abi as A
 
+from _moments_ref import criterion_ref
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "fountain_hip_adaptive.h")
 F32 = np.float32
@@ -53,24 +55,6 @@ def test_defaults(ftn):
     assert (q.min_samples, q.step_samples, q.threshold, q.abs_floor) == (8, 0, F32(0.2), F32(0.01))
     with pytest.raises(TypeError):
         adaptive.params(ftn, thresold=0.2)
-
-
-def criterion_ref(pix, m, t, a):
-    """the header's criterion in float32, one rounding per step: v = Y of the moments resolve (W < 2 -> inf); mean = Y / W; t2 = t * t;
-    a2 = a * a; bound = t2 * (mean * mean + a2); converged iff Y, W, sq_y, v and bound are finite and v <= bound"""
-    pix, m = np.asarray(pix, F32), np.asarray(m, F32)
-    y, w = pix[..., 1], pix[..., 3]
-    t, a = F32(t), F32(a)
-    with np.errstate(all="ignore"):
-        mean = (y / w).astype(F32)
-        v = ((m[..., 3] / w).astype(F32) - (mean * mean).astype(F32)).astype(F32)
-        v = np.where(v < 0, F32(0), v).astype(F32)
-        v = (v / (w - F32(1))).astype(F32)
-        v = np.where(w < 2, F32(np.inf), v)
-        t2, a2 = F32(t * t), F32(a * a)
-        bound = (t2 * (mean * mean + a2).astype(F32)).astype(F32)
-        fin = np.isfinite(y) & np.isfinite(w) & np.isfinite(m[..., 3]) & np.isfinite(v) & np.isfinite(bound)
-        return (fin & (v <= bound)).astype(np.uint8)
 
 
 def _converged(ftn, pix, m, t, a):
