@@ -109,6 +109,11 @@ struct DScene {
      * to eight children with outward-rounded 8-bit boxes, exact leaf boxes (oct_xbox: the leaves whose box is not their one triangle's) */
     const uint4* oct; const float4* oct_xbox;
     uint32_t n_octs, oct_stack_bound;
+    /* the same records as `quad` in 64 bytes for the closest-hit walk of triangle-only scenes (build_quad64s, ftn_host.cpp; NULL: not
+     * built): outward-rounded 8-bit boxes on a per-record grid, the leaves tested exactly on their own box (quad64_xbox: the leaves whose
+     * box is not their one triangle's).  Record q here is record q of `quad`; quad64_stack_bound = quad_stack_bound */
+    const uint4* quad64; const float4* quad64_xbox;
+    uint32_t n_quad64, quad64_stack_bound;
     /* shading class of every primitive (k_wf_classify, ftn_wavefront.hip): 2 + material type, 7 for a primitive without material.  One
      * byte per primitive -- cache resident where prim_info (32 bytes per primitive) is not.  Never NULL for a scene with primitives. */
     const unsigned char* prim_class;

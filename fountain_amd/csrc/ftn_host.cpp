@@ -581,6 +581,110 @@ static void build_octs(const std::vector<ftn_bvh_node>& nodes, const std::vector
     out->n_records = (uint32_t)recs.size(); out->stack_bound = bound[0]; out->ok = true;
 }
 
+/* ------------------------------------------------------------------ 64-byte four-box records (DScene::quad64): the records of build_quads with
+ * their boxes quantised as build_octs quantises its own, for Scene::intersect in triangle-only scenes (k_wf_trace4<.., Q64>, ftn_trace4.hip).
+ * Same tree, same slots, same DFS order, same stack bound: record q of the 128-byte array is record q here (links are byte offsets / 2).
+ * A record step then needs four dwordx4 loads instead of eight.  Exactness of the closest-hit walk over conservative boxes:
+ *   - interior boxes may be larger than the reference's: a child the ray does not truly enter is visited at most in vain -- every leaf under
+ *     it fails its exact test later (monotone in the box and in t_max, which only shrinks);
+ *   - the reference's visiting order is kept (the split axes of build_quads' slot a meta word);
+ *   - every leaf, whether entered from its record or popped, is tested exactly on its true box with the t_max of that moment (bvh.rs:173)
+ *     before its primitives: a single triangle whose node box is the min / max of its vertices by those vertices, any other leaf by its
+ *     explicit box in `xbox` (bit 30 of its link).
+ * Record (16 words): [0..2] origin = the min corner of the four slot boxes, [3] step exponents (biased, one byte per axis), [4..9] planes,
+ * one byte per slot: lo.x hi.x lo.y hi.y lo.z hi.z, [10..13] slot links (interior: byte offset of the child's record; leaf: bit 31 | first
+ * primitive, or bit 31 | bit 30 | index into xbox; empty: 0xffffffff), [14] the three one-hot split axes (bytes 0 A, 1 R, 2 B), [15] 0.
+ * `geom` empty: every leaf gets an explicit box (the C entry point for tests has no vertices). */
+struct Quad64Bvh { std::vector<uint32_t> rec; std::vector<float4> xbox; uint32_t n_records = 0, stack_bound = 0; bool ok = false; };
+static void build_quad64s(const QuadBvh& qb, const std::vector<float4>& geom, Quad64Bvh* out) {
+    out->rec.clear(); out->xbox.clear(); out->n_records = 0; out->stack_bound = 0; out->ok = false;
+    if (!qb.ok || qb.n_records == 0) return;
+    const size_t n = qb.n_records;
+    auto slot = [&](size_t q, int s) { return &qb.rec[(size_t)32 * q + 8 * s]; };
+    auto meta = [&](const float* S) { return ftn_det::f2u(S[7]); };
+    /* a leaf slot whose box is its single triangle's min / max (build_octs' test; the first primitive flagged GF_LEAF_END: one primitive) */
+    auto leaf_is_implicit = [&](const float* S) {
+        const uint32_t p = ftn_det::f2u(S[6]) & 0x7fffffffu;
+        if (geom.empty() || (size_t)FTN_GS * p + 2 >= geom.size()) return false;
+        const float4 g0 = geom[(size_t)FTN_GS * p], g1 = geom[(size_t)FTN_GS * p + 1], g2 = geom[(size_t)FTN_GS * p + 2];
+        const uint32_t fl = ftn_det::f2u(g0.w);
+        if ((fl & GF_KIND_SPHERE) || !(fl & GF_LEAF_END)) return false;
+        const float lo[3] = {std::min(std::min(g0.x, g1.x), g2.x), std::min(std::min(g0.y, g1.y), g2.y), std::min(std::min(g0.z, g1.z), g2.z)};
+        const float hi[3] = {std::max(std::max(g0.x, g1.x), g2.x), std::max(std::max(g0.y, g1.y), g2.y), std::max(std::max(g0.z, g1.z), g2.z)};
+        for (int a = 0; a < 3; a++) if (ftn_det::f2u(lo[a]) != ftn_det::f2u(S[2 * a]) || ftn_det::f2u(hi[a]) != ftn_det::f2u(S[2 * a + 1])) return false;
+        return true;
+    };
+    std::vector<uint8_t> xmask(n, 0);
+    parallel_for(n, [&](size_t q0, size_t q1) {
+        for (size_t q = q0; q < q1; q++) {
+            uint8_t m = 0;
+            for (int s = 0; s < 4; s++) { const float* S = slot(q, s); if ((meta(S) >> 24) == 1u && !leaf_is_implicit(S)) m |= (uint8_t)(1u << s); }
+            xmask[q] = m;
+        }
+    });
+    std::vector<uint32_t> xbase(n, 0);
+    { uint32_t run = 0; for (size_t q = 0; q < n; q++) { xbase[q] = run; run += (uint32_t)__builtin_popcount(xmask[q]); } out->xbox.assign(2 * (size_t)run, make_float4(0.0f, 0.0f, 0.0f, 0.0f)); }
+    if (out->xbox.size() / 2 >= (1u << 30)) return;
+    out->rec.assign((size_t)16 * n, 0u);
+    std::atomic<bool> bad{false};
+    parallel_for(n, [&](size_t q0, size_t q1) {
+    for (size_t q = q0; q < q1; q++) {
+        uint32_t* W = &out->rec[(size_t)16 * q];
+        bool used[4];
+        for (int s = 0; s < 4; s++) used[s] = !((meta(slot(q, s)) >> 25) & 1u);
+        for (int a = 0; a < 3; a++) {
+            /* origin and extent of the four boxes; the step as build_octs chooses it (smallest power of two that leaves one step of slack) */
+            float org = FTN_INF, top = -FTN_INF;
+            for (int s = 0; s < 4; s++) if (used[s]) { org = std::min(org, slot(q, s)[2 * a]); top = std::max(top, slot(q, s)[2 * a + 1]); }
+            if (!(std::fabs(org) < FTN_INF && std::fabs(top) < FTN_INF)) { bad = true; break; }
+            const double ext = (double)top - (double)org;
+            int e = ext > 0.0 ? (int)ceil(log2(ext / 255.0)) : -126;
+            if (e < -126) e = -126;
+            for (;; e++) {
+                const double st = ldexp(1.0, e);
+                if (ceil(((double)top - (double)org) / st) <= 254.0 || e >= 126) break;
+            }
+            const double stp = ldexp(1.0, e), o = (double)org;
+            memcpy(&W[a], &org, 4);
+            W[3] |= (uint32_t)(e + 127) << (8 * a);
+            for (int s = 0; s < 4; s++) {
+                uint32_t ql = 255u, qh = 0u;                                               /* empty: lo > hi (its link alone keeps it out) */
+                if (used[s]) {
+                    /* decoded plane = origin + q * step, exact in double: lo_dec <= lo and hi_dec >= hi as real numbers */
+                    const double lo = slot(q, s)[2 * a], hi = slot(q, s)[2 * a + 1];
+                    double l = floor((lo - o) / stp), h = ceil((hi - o) / stp);
+                    while (l > 0.0 && o + l * stp > lo) l -= 1.0;
+                    while (o + h * stp < hi) h += 1.0;
+                    if (l < 0.0 || h > 255.0 || o + l * stp > lo || o + h * stp < hi) { bad = true; break; }
+                    ql = (uint32_t)l; qh = (uint32_t)h;
+                }
+                W[4 + 2 * a] |= ql << (8 * s); W[5 + 2 * a] |= qh << (8 * s);
+            }
+        }
+        uint32_t xi = xbase[q];
+        for (int s = 0; s < 4; s++) {
+            const float* S = slot(q, s);
+            const uint32_t link = ftn_det::f2u(S[6]), m = meta(S);
+            uint32_t l = 0xffffffffu;
+            if (!used[s]) l = 0xffffffffu;
+            else if (!((m >> 24) & 1u)) l = link >> 1;                                   /* 128-byte record q -> 64-byte record q */
+            else if (link & 0x40000000u) bad = true;                                      /* (bit 30 marks an explicit box) */
+            else if (!((xmask[q] >> s) & 1u)) l = link;
+            else {
+                l = 0xc0000000u | xi;
+                out->xbox[2 * (size_t)xi] = make_float4(S[0], S[2], S[4], ftn_det::u2f(link & 0x7fffffffu));
+                out->xbox[2 * (size_t)xi + 1] = make_float4(S[1], S[3], S[5], 0.0f);
+                xi++;
+            }
+            W[10 + s] = l;
+        }
+        W[14] = meta(slot(q, 0)) & 0x00ffffffu;
+    }
+    });
+    if (bad) { out->rec.clear(); out->xbox.clear(); return; }
+    out->n_records = (uint32_t)n; out->stack_bound = qb.stack_bound; out->ok = true;
+}
+
 static int bvh_default_threads() {
     int cores = (int)std::thread::hardware_concurrency();
 #ifdef __linux__
@@ -783,7 +887,7 @@ struct ftn_scene {
     int device = 0;
     HostScene host;
     DScene d; uint32_t stack_entries = 1;
-    DevBuf<float4> nodes, geom, fat, srec, quad, oct_xbox; DevBuf<uint4> prim_info, oct; DevBuf<float> N, UV, T; DevBuf<DSphere> spheres; DevBuf<ftn_material> materials; DevBuf<DLight> lights;
+    DevBuf<float4> nodes, geom, fat, srec, quad, oct_xbox, quad64_xbox; DevBuf<uint4> prim_info, oct, quad64; DevBuf<float> N, UV, T; DevBuf<DSphere> spheres; DevBuf<ftn_material> materials; DevBuf<DLight> lights;
     DevBuf<uint32_t> inf_lights; DevBuf<unsigned char> prim_class; std::vector<DevBuf<float>> misc; std::vector<DevBuf<float4>> misc4;
     DevBuf<ftn_texture> textures; DevBuf<ftn_material_textures> mtex; DevBuf<DImage> images; DevBuf<float4> texels;
     /* render work buffers (grow-only, reused across calls) */
@@ -792,7 +896,7 @@ struct ftn_scene {
     WavefrontState* wf = nullptr;
     std::vector<DTile> sel; int32_t tile_key[10] = {0};
     ~ftn_scene() {
-        nodes.release(); geom.release(); fat.release(); srec.release(); quad.release(); oct.release(); oct_xbox.release(); prim_info.release(); N.release(); UV.release(); T.release(); spheres.release(); materials.release(); lights.release(); inf_lights.release(); prim_class.release();
+        nodes.release(); geom.release(); fat.release(); srec.release(); quad.release(); quad64.release(); quad64_xbox.release(); oct.release(); oct_xbox.release(); prim_info.release(); N.release(); UV.release(); T.release(); spheres.release(); materials.release(); lights.release(); inf_lights.release(); prim_class.release();
         for (auto& b : misc) b.release();
         for (auto& b : misc4) b.release();
         textures.release(); mtex.release(); images.release(); texels.release();
@@ -883,14 +987,28 @@ static int upload_scene(const ftn_scene_desc* d, ftn_scene* sc) {
     if (n_fat && n_fat < (1u << 25)) { if ((rc = sc->fat.upload(fat.data(), fat.size()))) return rc; }
     /* four-box records (DScene::quad): what the production traversal kernels walk.  FTN_QUAD=0: not built (the two-record kernels run) */
     uint32_t n_quads = 0, quad_bound = 0;
+    QuadBvh qb;
     if (!env_is("FTN_QUAD", 0)) {
-        QuadBvh qb; build_quads(hs.nodes, &qb);
+        build_quads(hs.nodes, &qb);
         if (qb.ok && qb.n_records) {
             if ((rc = sc->quad.upload(reinterpret_cast<const float4*>(qb.rec.data()), (size_t)8 * qb.n_records))) return rc;
             n_quads = qb.n_records; quad_bound = qb.stack_bound;
         }
     }
     clk.mark("four-box records (host + upload)");
+    /* 64-byte four-box records (DScene::quad64): the closest-hit walk of triangle-only scenes.  FTN_QUAD64=0: not built.  The 128-byte
+     * records stay resident: the any-hit kernels of FTN_T8=0, scenes with spheres and the FTN_QUAD64=0 A/B at render time walk them */
+    uint32_t n_quad64 = 0, quad64_bound = 0;
+    if (!env_is("FTN_QUAD64", 0) && n_quads != 0 && d->n_spheres == 0) {
+        Quad64Bvh q6; build_quad64s(qb, geom, &q6);
+        if (q6.ok && q6.n_records) {
+            if ((rc = sc->quad64.upload(reinterpret_cast<const uint4*>(q6.rec.data()), (size_t)4 * q6.n_records))) return rc;
+            if (!q6.xbox.empty() && (rc = sc->quad64_xbox.upload(q6.xbox.data(), q6.xbox.size()))) return rc;
+            n_quad64 = q6.n_records; quad64_bound = q6.stack_bound;
+        }
+    }
+    qb = QuadBvh();
+    clk.mark("64-byte four-box records (host + upload)");
     /* eight-box occlusion records (DScene::oct): triangle-only scenes with four-box records (the kernel hands its exceptional rays to the
      * same fallback).  FTN_OCT=0: not built (the four-box any-hit kernel traces the shadow rays) */
     uint32_t n_octs = 0, oct_bound = 0;
@@ -1070,6 +1188,7 @@ static int upload_scene(const ftn_scene_desc* d, ftn_scene* sc) {
     D.srec = sc->srec.p; D.prim_class = sc->prim_class.p;
     D.quad = sc->quad.p; D.n_quads = n_quads; D.quad_stack_bound = quad_bound;
     D.oct = sc->oct.p; D.oct_xbox = sc->oct_xbox.p; D.n_octs = n_octs; D.oct_stack_bound = oct_bound;
+    D.quad64 = sc->quad64.p; D.quad64_xbox = sc->quad64_xbox.p; D.n_quad64 = n_quad64; D.quad64_stack_bound = quad64_bound;
     D.fat = sc->fat.p; D.n_fat = n_fat; D.root_is_leaf = (!hs.nodes.empty() && hs.nodes[0].is_leaf) ? 1u : 0u;
     for (int k = 0; k < 3; k++) { D.root_lo[k] = hs.nodes.empty() ? 0.0f : hs.nodes[0].bmin[k]; D.root_hi[k] = hs.nodes.empty() ? 0.0f : hs.nodes[0].bmax[k]; }
     if (lights.size() == 1 && lights[0].kind == LK_INFINITE) { D.env_only = 1; D.env0 = lights[0]; }
@@ -1148,6 +1267,23 @@ int ftn_bvh_quads(const ftn_bvh_node* nodes, uint32_t n_nodes, float* records_ou
     return FTN_OK;
 }
 
+/* the 64-byte four-box records of a flattened BVH (build_quad64s), for tests/test_quad64_bvh.py.  Exported, but not declared in
+ * include/fountain_hip.h, whose every function has a twin in the CPU oracle: this one has none (the oracle walks the reference's nodes) */
+extern "C" int ftn_bvh_quad64s(const ftn_bvh_node* nodes, uint32_t n_nodes, uint32_t* records_out, uint32_t* n_records_out, uint32_t* stack_bound_out, float* xbox_out, uint32_t* n_xbox_out) {
+    if (!nodes && n_nodes) return fail(FTN_ERR_INVALID_ARGUMENT, "null nodes");
+    std::vector<ftn_bvh_node> v(nodes, nodes + n_nodes);
+    for (uint32_t i = 0; i < n_nodes; i++) if (!v[i].is_leaf && (v[i].idx <= i + 1 || v[i].idx >= n_nodes || v[i].axis > 2)) return fail(FTN_ERR_INVALID_ARGUMENT, "not a flattened BVH (bvh.rs:133-158)");
+    QuadBvh qb; build_quads(v, &qb);
+    Quad64Bvh q6; build_quad64s(qb, std::vector<float4>(), &q6);       /* (no vertex data here: every leaf gets an explicit box) */
+    if (!q6.ok) return fail(FTN_ERR_UNSUPPORTED, "no interior node, a non-finite box, or more than 2^24 four-box records");
+    if (records_out) memcpy(records_out, q6.rec.data(), q6.rec.size() * sizeof(uint32_t));
+    if (n_records_out) *n_records_out = q6.n_records;
+    if (stack_bound_out) *stack_bound_out = q6.stack_bound;
+    if (xbox_out) memcpy(xbox_out, q6.xbox.data(), q6.xbox.size() * sizeof(float4));
+    if (n_xbox_out) *n_xbox_out = (uint32_t)(q6.xbox.size() / 2);
+    return FTN_OK;
+}
+
 int ftn_bvh_octs(const ftn_bvh_node* nodes, uint32_t n_nodes, uint32_t* records_out, uint32_t* n_records_out, uint32_t* stack_bound_out, float* xbox_out, uint32_t* n_xbox_out) {
     if (!nodes && n_nodes) return fail(FTN_ERR_INVALID_ARGUMENT, "null nodes");
     std::vector<ftn_bvh_node> v(nodes, nodes + n_nodes);
@@ -1188,7 +1324,7 @@ int ftn_scene_memory_info(const ftn_scene* s, ftn_scene_memory* m) {
     if (!s || !m) return fail(FTN_ERR_INVALID_ARGUMENT, "null scene / output");
     memset(m, 0, sizeof(*m));
     m->oct = s->oct.n * sizeof(uint4) + s->oct_xbox.n * sizeof(float4);
-    m->nodes = s->nodes.n * sizeof(float4); m->quad = s->quad.n * sizeof(float4); m->fat = s->fat.n * sizeof(float4); m->geom = s->geom.n * sizeof(float4);
+    m->nodes = s->nodes.n * sizeof(float4); m->quad = s->quad.n * sizeof(float4) + s->quad64.n * sizeof(uint4) + s->quad64_xbox.n * sizeof(float4); m->fat = s->fat.n * sizeof(float4); m->geom = s->geom.n * sizeof(float4);
     m->srec = s->srec.n * sizeof(float4); m->indexed_attributes = s->prim_info.n * sizeof(uint4) + (s->N.n + s->UV.n + s->T.n) * sizeof(float);
     m->prim_class = s->prim_class.n;
     m->lights = s->lights.n * sizeof(DLight) + s->inf_lights.n * sizeof(uint32_t);

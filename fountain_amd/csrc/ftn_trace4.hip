@@ -24,6 +24,8 @@
  *      host launches the reference-order kernel (k_wf_trace, ftn_wavefront.hip) over that queue right behind this one.  Jittered
  *      camera rays, BSDF-sampled and light-sampled directions practically never qualify; hand-made axis-parallel ray batches do.
  * Any-hit rays (k_wf_trace4_any): t_max never shrinks and only the boolean matters, so order is free and entries need no t0.
+ * Triangle-only scenes walk the same records in 64 bytes (k_wf_trace4<.., Q64>, DScene::quad64): boxes quantised outwards, tested
+ * conservatively, every leaf re-tested exactly on its true box before its primitives -- see t4q_record_step and build_quad64s.
  *
  * Per-lane stack: LDS, [level][lane], 8-byte (closest: link, t0) or 4-byte (any-hit) entries.  LDS holds the first `lds_entries`
  * levels; deeper pushes (rare: the host sizes LDS for the occupancy it wants, DScene::quad_stack_bound is the true bound) go to a
@@ -126,6 +128,35 @@ template <class E> struct T4Stack {
     __device__ inline bool empty() const { return sp == base; }
 };
 
+enum : uint32_t { T8_IDLE = 0, T8_NODE = 1, T8_LEAF = 2, T8_LEAF_IN = 3 /* inside a leaf of several primitives whose box has passed */ };
+#define T8_XBOX 0x40000000u
+__device__ inline bool ray_out_of_range8(float ox, float oy, float oz, float ix, float iy, float iz) {
+    const float big_i = 1.152921504606846976e18f /* 2^60 */, big_o = 1.099511627776e12f /* 2^40 */;
+    return !(fabsf(ix) <= big_i && fabsf(iy) <= big_i && fabsf(iz) <= big_i && fabsf(ox) <= big_o && fabsf(oy) <= big_o && fabsf(oz) <= big_o);
+}
+struct T8Axis { float a, bn, bf; uint32_t n03, n47, f03, f47; };
+/* per record and axis: the two constants of the plane expression, the outward margin folded into the offsets, near / far byte rows by sign */
+__device__ inline T8Axis t8_axis(float org, uint32_t ebyte, float o, float inv, uint32_t lo03, uint32_t lo47, uint32_t hi03, uint32_t hi47) {
+    T8Axis A;
+    const float step = __uint_as_float(ebyte << 23);
+    A.a = step * inv;
+    const float b = (org - o) * inv;
+    const float m = (fabsf(b) + 255.0f * fabsf(A.a)) * 9.5367431640625e-07f;
+    A.bn = b - m; A.bf = b + m;
+    const bool neg = inv < 0.0f;
+    A.n03 = neg ? hi03 : lo03; A.n47 = neg ? hi47 : lo47; A.f03 = neg ? lo03 : hi03; A.f47 = neg ? lo47 : hi47;
+    return A;
+}
+#define T8_BYTE(w, k) ((float)(((w) >> (8 * (k))) & 0xffu))
+/* child c of the record: conservative entry / exit distances.  The near and the far plane of an axis share the slope `a`: one packed
+ * fused multiply-add (v_pk_fma_f32: each half is the scalar fma) gives both */
+#define T8_CHILD(c, t0v, t1v) \
+    { const uint32_t kx_ = (c) & 3; \
+      const t4_f2 tx_ = __builtin_elementwise_fma((t4_f2){T8_BYTE((c) < 4 ? X.n03 : X.n47, kx_), T8_BYTE((c) < 4 ? X.f03 : X.f47, kx_)}, (t4_f2){X.a, X.a}, (t4_f2){X.bn, X.bf}); \
+      const t4_f2 ty_ = __builtin_elementwise_fma((t4_f2){T8_BYTE((c) < 4 ? Y.n03 : Y.n47, kx_), T8_BYTE((c) < 4 ? Y.f03 : Y.f47, kx_)}, (t4_f2){Y.a, Y.a}, (t4_f2){Y.bn, Y.bf}); \
+      const t4_f2 tz_ = __builtin_elementwise_fma((t4_f2){T8_BYTE((c) < 4 ? Z.n03 : Z.n47, kx_), T8_BYTE((c) < 4 ? Z.f03 : Z.f47, kx_)}, (t4_f2){Z.a, Z.a}, (t4_f2){Z.bn, Z.bf}); \
+      t0v = fmax_(fmax_(fmax_(0.0f, tx_.x), ty_.x), tz_.x); t1v = fmin_(t_max, fmin_(fmin_(tx_.y, ty_.y), tz_.y) * k2); }
+
 /* ------------------------------------------------------------------ closest hit */
 struct T4Lane { uint32_t mode, cur, lp; bool finish; };
 
@@ -143,6 +174,27 @@ __device__ inline void t4_pop_next(T4Stack<uint2>& St, T4Lane& L, float t_max) {
     }
 }
 
+/* the reference's order of a record's four slots: pair A = slots (a, b) ordered by A's axis, pair B = (c, d) by B's axis, the pairs by
+ * R's axis (ax = the record's axes & the ray's dir_is_neg bytes).  The first child in order that the ray enters is visited next, the
+ * later ones wait on the stack with their t0; nothing entered: the next deferred entry */
+template <bool CHECK>
+__device__ __forceinline__ void t4_visit(T4Stack<uint2>& St, T4Lane& L, float t_max, uint32_t ea, uint32_t eb, uint32_t ec, uint32_t ed, float ta, float tb, float tc, float td, uint32_t ax) {
+    const bool sA = (ax & 0xffu) != 0, sR = (ax & 0xff00u) != 0, sB = (ax & 0xff0000u) != 0;
+    const uint32_t ex0 = sA ? eb : ea, ex1 = sA ? ea : eb, ey0 = sB ? ed : ec, ey1 = sB ? ec : ed;
+    const float tx0 = sA ? tb : ta, tx1 = sA ? ta : tb, ty0 = sB ? td : tc, ty1 = sB ? tc : td;
+    const uint32_t e0 = sR ? ey0 : ex0, e1 = sR ? ey1 : ex1, e2 = sR ? ex0 : ey0, e3 = sR ? ex1 : ey1;
+    const float t1_ = sR ? ty1 : tx1, t2_ = sR ? tx0 : ty0, t3_ = sR ? tx1 : ty1;
+    const bool h0 = e0 != T4_NONE, h1 = e1 != T4_NONE, h2 = e2 != T4_NONE, h3 = e3 != T4_NONE;
+    const bool h01 = h0 || h1, h012 = h01 || h2;
+    if (h3 && h012) St.template push<CHECK>(make_uint2(e3, __float_as_uint(t3_)));
+    if (h2 && h01) St.template push<CHECK>(make_uint2(e2, __float_as_uint(t2_)));
+    if (h1 && h0) St.template push<CHECK>(make_uint2(e1, __float_as_uint(t1_)));
+    if (h012 || h3) {
+        const uint32_t next = h0 ? e0 : (h1 ? e1 : (h2 ? e2 : e3));
+        if (next >> 31) { L.lp = next & 0x7fffffffu; L.mode = T4_LEAF; } else L.cur = next;
+    } else t4_pop_next<CHECK>(St, L, t_max);
+}
+
 /* one record: four box tests, the reference's visiting order, at most three pushes */
 template <bool CHECK>
 __device__ inline void t4_record_step(const DScene& S, const RaySetup& R, T4Stack<uint2>& St, T4Lane& L) {
@@ -154,28 +206,38 @@ __device__ inline void t4_record_step(const DScene& S, const RaySetup& R, T4Stac
     /* entries as stored: byte offset of an interior child's record, or first primitive | bit 31 for a leaf; a child the ray does not
      * enter becomes T4_NONE here, so that "entered" travels through the reordering inside the entry word */
     const uint32_t ea = ha ? __float_as_uint(q1.z) : T4_NONE, eb = hb ? __float_as_uint(q3.z) : T4_NONE, ec = hc ? __float_as_uint(q5.z) : T4_NONE, ed = hd ? __float_as_uint(q7.z) : T4_NONE;
-    /* the reference's order: pair A = slots (a, b) ordered by A's axis, pair B = (c, d) by B's axis, the pairs by R's axis.  Slot a's
-     * meta word holds the three one-hot axes in bytes 0 (A), 1 (R), 2 (B); neg24 holds dir_is_neg in the same three bytes */
-    const uint32_t ax = __float_as_uint(q1.w) & R.neg24;
-    const bool sA = (ax & 0xffu) != 0, sR = (ax & 0xff00u) != 0, sB = (ax & 0xff0000u) != 0;
-    const uint32_t ex0 = sA ? eb : ea, ex1 = sA ? ea : eb, ey0 = sB ? ed : ec, ey1 = sB ? ec : ed;
-    const float tx0 = sA ? tb : ta, tx1 = sA ? ta : tb, ty0 = sB ? td : tc, ty1 = sB ? tc : td;
-    const uint32_t e0 = sR ? ey0 : ex0, e1 = sR ? ey1 : ex1, e2 = sR ? ex0 : ey0, e3 = sR ? ex1 : ey1;
-    const float t1_ = sR ? ty1 : tx1, t2_ = sR ? tx0 : ty0, t3_ = sR ? tx1 : ty1;
-    const bool h0 = e0 != T4_NONE, h1 = e1 != T4_NONE, h2 = e2 != T4_NONE, h3 = e3 != T4_NONE;
-    /* the first child in order that the ray enters is visited next; the later ones wait on the stack with their t0 */
-    const bool h01 = h0 || h1, h012 = h01 || h2;
-    if (h3 && h012) St.template push<CHECK>(make_uint2(e3, __float_as_uint(t3_)));
-    if (h2 && h01) St.template push<CHECK>(make_uint2(e2, __float_as_uint(t2_)));
-    if (h1 && h0) St.template push<CHECK>(make_uint2(e1, __float_as_uint(t1_)));
-    if (h012 || h3) {
-        const uint32_t next = h0 ? e0 : (h1 ? e1 : (h2 ? e2 : e3));
-        if (next >> 31) { L.lp = next & 0x7fffffffu; L.mode = T4_LEAF; } else L.cur = next;
-    } else t4_pop_next<CHECK>(St, L, R.t_max);
+    /* slot a's meta word holds the three one-hot axes in bytes 0 (A), 1 (R), 2 (B); neg24 holds dir_is_neg in the same three bytes */
+    t4_visit<CHECK>(St, L, R.t_max, ea, eb, ec, ed, ta, tb, tc, td, __float_as_uint(q1.w) & R.neg24);
 }
 
-template <bool COUNT, bool SPHERES, int BURST>
-__global__ void __launch_bounds__(256, (SPHERES ? 1 : 5)) k_wf_trace4(DScene S, WfBuffers W, const uint32_t* __restrict__ queue, const uint32_t* count_ptr, uint32_t* head, DevStats* stats,
+/* one 64-byte record (DScene::quad64, build_quad64s): four conservative box tests on the decoded planes -- the fused multiply-add form and
+ * the outward margins of k_wf_trace8_any (t8_axis), which pass whenever the reference's test of any box inside the decoded one passes --
+ * then the same order and pushes as t4_record_step.  A pushed entry carries its conservative t0 (<= the reference's), so the pop test
+ * `!(t0 > t_max)` lets through at least what the reference's lets through; the leaf step re-tests every leaf exactly (see k_wf_trace4).
+ * (o, inv, t_max by value: see ray_is_exceptional) */
+template <bool CHECK>
+__device__ __forceinline__ void t4q_record_step(const DScene& S, T4Stack<uint2>& St, T4Lane& L, V3 o, V3 inv, float t_max, uint32_t neg24) {
+    const uint4* rec = reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(S.quad64) + L.cur);
+    const uint4 r0 = rec[0], r1 = rec[1], r2 = rec[2], r3 = rec[3];
+    const float k2 = 1.0f + 4.0f * gamma_n(3);
+    /* words: r0 = origin.xyz, step exponents; r1 = lo.x hi.x lo.y hi.y; r2 = lo.z hi.z, links a b; r3 = links c d, axes, 0 (one byte per slot) */
+    const T8Axis X = t8_axis(__uint_as_float(r0.x), r0.w & 0xffu, o.x, inv.x, r1.x, r1.x, r1.y, r1.y);
+    const T8Axis Y = t8_axis(__uint_as_float(r0.y), (r0.w >> 8) & 0xffu, o.y, inv.y, r1.z, r1.z, r1.w, r1.w);
+    const T8Axis Z = t8_axis(__uint_as_float(r0.z), (r0.w >> 16) & 0xffu, o.z, inv.z, r2.x, r2.x, r2.y, r2.y);
+    float ta, a1, tb, b1, tc, c1, td, d1;
+    T8_CHILD(0, ta, a1) T8_CHILD(1, tb, b1) T8_CHILD(2, tc, c1) T8_CHILD(3, td, d1)
+    /* an empty slot's link is T4_NONE whatever its test says */
+    const uint32_t ea = !(ta > a1) ? r2.z : T4_NONE, eb = !(tb > b1) ? r2.w : T4_NONE, ec = !(tc > c1) ? r3.x : T4_NONE, ed = !(td > d1) ? r3.y : T4_NONE;
+    t4_visit<CHECK>(St, L, t_max, ea, eb, ec, ed, ta, tb, tc, td, r3.z & neg24);
+}
+
+/* Q64: the walk over DScene::quad64 (triangle-only scenes).  A leaf is then reached through conservative boxes, and its first leaf step
+ * (mode T4_LEAF) runs the reference's own test of the leaf node (bvh.rs:173: Bounds3f::intersect_test on its true box with the t_max of
+ * that moment) before any primitive -- exactly as k_wf_trace8_any's T8_LEAF; further primitives of the leaf run in mode T4_LEAF_IN.
+ * Rays outside the range of the margins (ray_out_of_range8) join the exceptional rays. */
+enum : uint32_t { T4_LEAF_IN = 3 };
+template <bool COUNT, bool SPHERES, int BURST, bool Q64 = false>
+__global__ void __launch_bounds__(256, (SPHERES ? 1 : (Q64 ? T4Q_WAVES : 5))) k_wf_trace4(DScene S, WfBuffers W, const uint32_t* __restrict__ queue, const uint32_t* count_ptr, uint32_t* head, DevStats* stats,
                                                    uint32_t refill, uint32_t leaf_batch, uint32_t chunk_max, uint32_t lds_entries, uint2* __restrict__ spill, uint32_t spill_levels) {
     T4Stack<uint2> St;
     extern __shared__ uint2 lds_stack2[];
@@ -216,7 +278,8 @@ __global__ void __launch_bounds__(256, (SPHERES ? 1 : 5)) k_wf_trace4(DScene S, 
                 load_queued_ray<false>(W, q_entry, &a, &b, &rid);
                 ray_setup<SPHERES>(R, a, b);
                 St.sp = St.base; L.cur = 0; found = false; hprim = -1; hb0 = 0.0f; hb1 = 0.0f; hb2 = 0.0f;
-                if (ray_is_exceptional(R.o.x, R.o.y, R.o.z, R.inv.x, R.inv.y, R.inv.z)) hand_back = true;            /* walked by the reference-order kernel instead */
+                if (ray_is_exceptional(R.o.x, R.o.y, R.o.z, R.inv.x, R.inv.y, R.inv.z) || (Q64 && ray_out_of_range8(R.o.x, R.o.y, R.o.z, R.inv.x, R.inv.y, R.inv.z)))
+                    hand_back = true;                                                                                      /* walked by the reference-order kernel instead */
                 /* the root's own box test (bvh.rs:173 at node 0) */
                 else if (S.n_nodes == 0 || !slab_test(rlo, rhi, R.o, R.inv, R.t_max)) { W.hit[rid] = make_float4(FTN_INF, 0.0f, 0.0f, 0.0f); W.hit_prim[rid] = -1; }
                 else if (S.root_is_leaf) { L.lp = 0; L.mode = T4_LEAF; }
@@ -225,7 +288,7 @@ __global__ void __launch_bounds__(256, (SPHERES ? 1 : 5)) k_wf_trace4(DScene S, 
             if (__ballot(hand_back) != 0) wave_push(hand_back, q_entry, W.q_exc_closest, &W.counters[CTR(32)]);
             Q.chunk_next += (need < avail ? need : avail);
         }
-        const unsigned long long m_node = __ballot(L.mode == T4_NODE), m_leaf = __ballot(L.mode == T4_LEAF);
+        const unsigned long long m_node = __ballot(L.mode == T4_NODE), m_leaf = __ballot(L.mode >= T4_LEAF);
         if ((m_node | m_leaf) == 0) { if (Q.exhausted) break; else continue; }
         L.finish = false;
         if (COUNT) occ[0]++;
@@ -237,22 +300,37 @@ __global__ void __launch_bounds__(256, (SPHERES ? 1 : 5)) k_wf_trace4(DScene S, 
                 const bool on = L.mode == T4_NODE && !L.finish;
                 if (COUNT && on) n_rec++;
                 if (COUNT) { const unsigned long long m_on = __ballot(on); if (m_on) { occ[1]++; occ[2] += (unsigned long long)__popcll(m_on); } }
-                if (__builtin_expect(__ballot(on && (st_tiny || St.sp > st_soft)) == 0, 1)) { if (on) t4_record_step<false>(S, R, St, L); }
-                else if (on) t4_record_step<true>(S, R, St, L);
+                if (__builtin_expect(__ballot(on && (st_tiny || St.sp > st_soft)) == 0, 1)) {
+                    if (on) { if (Q64) t4q_record_step<false>(S, St, L, R.o, R.inv, R.t_max, R.neg24); else t4_record_step<false>(S, R, St, L); }
+                } else if (on) { if (Q64) t4q_record_step<true>(S, St, L, R.o, R.inv, R.t_max, R.neg24); else t4_record_step<true>(S, R, St, L); }
             }
         } else {
-            /* ---- leaf step: one primitive per lane */
+            /* ---- leaf step: one primitive per lane (Q64: the leaf's exact box first, on entering it) */
             if (COUNT) { occ[3]++; occ[4] += (unsigned long long)__popcll(m_leaf); }
-            if (L.mode == T4_LEAF) {
-                const uint32_t prim = L.lp;
+            if (L.mode >= T4_LEAF) {
+                uint32_t prim = L.lp;
+                const bool entering = Q64 && L.mode == T4_LEAF, explicit_box = entering && (L.lp & T8_XBOX);
+                float4 x0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), x1 = x0;
+                if (Q64) prim &= 0x3fffffffu;
+                if (explicit_box) { x0 = S.quad64_xbox[2 * (size_t)prim]; x1 = S.quad64_xbox[2 * (size_t)prim + 1]; prim = __float_as_uint(x0.w); }
                 float4 g0 = S.geom[S.geom_stride * prim], g1 = S.geom[S.geom_stride * prim + 1], g2 = S.geom[S.geom_stride * prim + 2];
                 pin4(g0); pin4(g1); pin4(g2);
-                if (COUNT) n_prim++;
-                float t = 0.0f, b0 = 0.0f, b1 = 0.0f, b2 = 0.0f;
-                const bool hh = prim_hit<SPHERES>(S, prim, g0, g1, g2, R.o, R.dorig, R.t_max, R.kz, R.sx, R.sy, R.sz, &t, &b0, &b1, &b2);
-                if (hh) { found = true; R.t_max = t; hprim = (int)prim; hb0 = b0; hb1 = b1; hb2 = b2; }
-                if (__float_as_uint(g0.w) & GF_LEAF_END) t4_pop_next<true>(St, L, R.t_max);
-                else L.lp++;
+                bool pass = true;
+                if (entering) {
+                    if (!explicit_box) {                               /* Triangle::world_bound (triangle.rs:152-158): the union of the three vertices */
+                        x0 = make_float4(fmin_(fmin_(g0.x, g1.x), g2.x), fmin_(fmin_(g0.y, g1.y), g2.y), fmin_(fmin_(g0.z, g1.z), g2.z), 0.0f);
+                        x1 = make_float4(fmax_(fmax_(g0.x, g1.x), g2.x), fmax_(fmax_(g0.y, g1.y), g2.y), fmax_(fmax_(g0.z, g1.z), g2.z), 0.0f);
+                    }
+                    pass = slab_test(x0, x1, R.o, R.inv, R.t_max);     /* the reference's test of the leaf node (bvh.rs:173) */
+                }
+                if (pass) {
+                    if (COUNT) n_prim++;
+                    float t = 0.0f, b0 = 0.0f, b1 = 0.0f, b2 = 0.0f;
+                    const bool hh = prim_hit<SPHERES>(S, prim, g0, g1, g2, R.o, R.dorig, R.t_max, R.kz, R.sx, R.sy, R.sz, &t, &b0, &b1, &b2);
+                    if (hh) { found = true; R.t_max = t; hprim = (int)prim; hb0 = b0; hb1 = b1; hb2 = b2; }
+                }
+                if (!pass || (__float_as_uint(g0.w) & GF_LEAF_END)) t4_pop_next<true>(St, L, R.t_max);
+                else { L.lp = prim + 1u; if (Q64) L.mode = T4_LEAF_IN; }
             }
         }
         if (L.finish) {
@@ -401,35 +479,6 @@ __global__ void __launch_bounds__(256) k_wf_trace4_any(DScene S, WfBuffers W, co
  * Rays whose 1/d or o/d are outside the range where these bounds hold (|1/d| > 2^60, |o| > 2^40) join the exceptional rays in the queue
  * of the reference-order kernel.  Same scheduling as k_wf_trace4_any: persistent workgroups, XCD queue slices, LDS stack with a global
  * spill area, record steps and leaf steps as separate convergent bodies.  ~12 records per ray instead of 20 four-box records. */
-enum : uint32_t { T8_IDLE = 0, T8_NODE = 1, T8_LEAF = 2, T8_LEAF_IN = 3 /* inside a leaf of several primitives whose box has passed */ };
-#define T8_XBOX 0x40000000u
-__device__ inline bool ray_out_of_range8(float ox, float oy, float oz, float ix, float iy, float iz) {
-    const float big_i = 1.152921504606846976e18f /* 2^60 */, big_o = 1.099511627776e12f /* 2^40 */;
-    return !(fabsf(ix) <= big_i && fabsf(iy) <= big_i && fabsf(iz) <= big_i && fabsf(ox) <= big_o && fabsf(oy) <= big_o && fabsf(oz) <= big_o);
-}
-struct T8Axis { float a, bn, bf; uint32_t n03, n47, f03, f47; };
-/* per record and axis: the two constants of the plane expression, the outward margin folded into the offsets, near / far byte rows by sign */
-__device__ inline T8Axis t8_axis(float org, uint32_t ebyte, float o, float inv, uint32_t lo03, uint32_t lo47, uint32_t hi03, uint32_t hi47) {
-    T8Axis A;
-    const float step = __uint_as_float(ebyte << 23);
-    A.a = step * inv;
-    const float b = (org - o) * inv;
-    const float m = (fabsf(b) + 255.0f * fabsf(A.a)) * 9.5367431640625e-07f;
-    A.bn = b - m; A.bf = b + m;
-    const bool neg = inv < 0.0f;
-    A.n03 = neg ? hi03 : lo03; A.n47 = neg ? hi47 : lo47; A.f03 = neg ? lo03 : hi03; A.f47 = neg ? lo47 : hi47;
-    return A;
-}
-#define T8_BYTE(w, k) ((float)(((w) >> (8 * (k))) & 0xffu))
-/* child c of the record: conservative entry / exit distances.  The near and the far plane of an axis share the slope `a`: one packed
- * fused multiply-add (v_pk_fma_f32: each half is the scalar fma) gives both */
-#define T8_CHILD(c, t0v, t1v) \
-    { const uint32_t kx_ = (c) & 3; \
-      const t4_f2 tx_ = __builtin_elementwise_fma((t4_f2){T8_BYTE((c) < 4 ? X.n03 : X.n47, kx_), T8_BYTE((c) < 4 ? X.f03 : X.f47, kx_)}, (t4_f2){X.a, X.a}, (t4_f2){X.bn, X.bf}); \
-      const t4_f2 ty_ = __builtin_elementwise_fma((t4_f2){T8_BYTE((c) < 4 ? Y.n03 : Y.n47, kx_), T8_BYTE((c) < 4 ? Y.f03 : Y.f47, kx_)}, (t4_f2){Y.a, Y.a}, (t4_f2){Y.bn, Y.bf}); \
-      const t4_f2 tz_ = __builtin_elementwise_fma((t4_f2){T8_BYTE((c) < 4 ? Z.n03 : Z.n47, kx_), T8_BYTE((c) < 4 ? Z.f03 : Z.f47, kx_)}, (t4_f2){Z.a, Z.a}, (t4_f2){Z.bn, Z.bf}); \
-      t0v = fmax_(fmax_(fmax_(0.0f, tx_.x), ty_.x), tz_.x); t1v = fmin_(t_max, fmin_(fmin_(tx_.y, ty_.y), tz_.y) * k2); }
-
 template <bool CHECK, int POLICY>
 __device__ __forceinline__ void t8_any_step(const DScene& S, T4Stack<uint32_t>& St, T4Lane& L, V3 o, V3 inv, float t_max) {
     const uint4* rec = reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(S.oct) + L.cur);
@@ -586,6 +635,19 @@ Trace4Plan trace4_plan(const DScene& S, int n_cu, uint32_t knob_entries_closest,
     p.lds_closest = (size_t)p.entries_closest * 256u * 8u; p.lds_any = (size_t)p.entries_any * 256u * 4u;
     auto per_cu = [](size_t lds, uint32_t wg) { return (unsigned)std::max<size_t>(1, std::min<size_t>(wg, (size_t)(158 * 1024) / std::max<size_t>(lds, 1))); };
     p.grid_closest = (unsigned)n_cu * per_cu(p.lds_closest, wg_c); p.grid_any = (unsigned)n_cu * per_cu(p.lds_any, wg_a);
+    /* 64-byte four-box records (closest hit in triangle-only scenes): the same tree and stack bound as `quad`, T4Q_WAVES workgroups per
+     * CU unless FTN_T4_WG says otherwise */
+    if (S.quad64 && S.n_quad64) {
+        const uint32_t wg_q = knob_wg_closest ? knob_wg_closest : (uint32_t)T4Q_WAVES, budget_q = ((158u * 1024u) / wg_q) & ~1023u;
+        const uint32_t bound_q = S.quad64_stack_bound ? S.quad64_stack_bound : 1u;
+        uint32_t eq = knob_entries_closest ? knob_entries_closest : budget_q / (256u * 8u);
+        p.entries_q64 = eq < bound_q ? eq : bound_q;
+        if (p.entries_q64 == 0) p.entries_q64 = 1;
+        p.spill_q64 = bound_q - p.entries_q64;
+        p.lds_q64 = (size_t)p.entries_q64 * 256u * 8u;
+        p.grid_q64 = (unsigned)n_cu * per_cu(p.lds_q64, wg_q);
+        p.q64_ok = true;
+    }
     /* eight-box occlusion records (k_wf_trace8_any): 4-byte entries, their own stack bound */
     if (S.oct && S.n_octs) {
         const uint32_t wg_8 = knob_wg_oct ? knob_wg_oct : 5u, budget_8 = ((158u * 1024u) / wg_8) & ~1023u, bound8 = S.oct_stack_bound ? S.oct_stack_bound : 1u;
@@ -601,9 +663,13 @@ Trace4Plan trace4_plan(const DScene& S, int n_cu, uint32_t knob_entries_closest,
 
 void launch_trace4(int kind, bool count, bool spheres, unsigned grid, size_t lds, uint32_t lds_entries, void* spill, hipStream_t stream, const DScene& S, const WfBuffers& W,
                    const uint32_t* queue, const uint32_t* count_ptr, uint32_t* head, DevStats* stats, uint32_t refill, uint32_t leaf_batch, uint32_t chunk, uint32_t burst, uint32_t any_policy, uint32_t spill_levels) {
-    const bool any = kind != T4K_CLOSEST;
+    const bool any = kind == T4K_ANY || kind == T4K_ANY_OCT;
 #define FTN_T4(K, SPILL_T, ...) hipLaunchKernelGGL((K<__VA_ARGS__>), dim3(grid), dim3(256), lds, stream, S, W, queue, count_ptr, head, stats, refill, leaf_batch, chunk, lds_entries, (SPILL_T)spill, spill_levels)
-    if (kind == T4K_ANY_OCT) {        /* (triangle-only scenes with eight-box records: the caller checked) */
+    if (kind == T4K_CLOSEST_Q64) {    /* (triangle-only scenes with 64-byte records: the caller checked) */
+        if (count) FTN_T4(k_wf_trace4, uint2*, true, false, 2, true);
+        else if (burst <= 1) FTN_T4(k_wf_trace4, uint2*, false, false, 1, true); else if (burst == 2) FTN_T4(k_wf_trace4, uint2*, false, false, 2, true);
+        else if (burst == 3) FTN_T4(k_wf_trace4, uint2*, false, false, 3, true); else FTN_T4(k_wf_trace4, uint2*, false, false, 4, true);
+    } else if (kind == T4K_ANY_OCT) {        /* (triangle-only scenes with eight-box records: the caller checked) */
 #define FTN_T8(C, B) do { if (any_policy == 0) FTN_T4(k_wf_trace8_any, uint32_t*, C, B, 0); else FTN_T4(k_wf_trace8_any, uint32_t*, C, B, 1); } while (0)
         if (count) FTN_T8(true, 2);
         else if (burst <= 1) FTN_T8(false, 1); else if (burst == 2) FTN_T8(false, 2); else FTN_T8(false, 3);

@@ -1151,7 +1151,7 @@ struct WavefrontState {
     /* four-box traversal (ftn_trace4.hip): launch plan of the current call and the global spill areas behind the LDS stacks */
     /* buffers of the direct-lighting / Whitted mode (grow-only): level terms, and shadow-ray records / results / queue sized for one ray per light */
     void* dl_mem[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; size_t dl_paths = 0; uint32_t dl_levels = 0, dl_slots = 0; bool dl_tex = false;
-    Trace4Plan t4; bool t4_on = false, t8_on = false;
+    Trace4Plan t4; bool t4_on = false, t8_on = false, q64_on = false;
     void* ser_mem[4] = {nullptr, nullptr, nullptr, nullptr}; size_t ser_paths = 0; bool ser_tex = false; uint32_t* ser_host = nullptr;      /* tile-serial sampler on the queues: cursor, film position, retired flag, differentials */
     void* t4_spill_c = nullptr; void* t4_spill_a = nullptr; size_t t4_spill_c_bytes = 0, t4_spill_a_bytes = 0;
 };
@@ -1232,7 +1232,10 @@ static int trace4_prepare(WavefrontState* st, const DScene& S) {
     st->t4_on = S.quad != nullptr && knob("FTN_TRACE4", 1) != 0;
     if (!st->t4_on) return FTN_OK;
     st->t4 = trace4_plan(S, st->n_cu, knob("FTN_T4_ENTRIES", 0), knob("FTN_T4_ENTRIES_ANY", 0), knob("FTN_T4_WG", 0), knob("FTN_T4_WG_ANY", 0), knob("FTN_T8_WG", 0), knob("FTN_T8_ENTRIES", 0));
-    const size_t need_c = (size_t)st->t4.grid_closest * 256u * st->t4.spill_closest * sizeof(uint2);
+    /* 64-byte four-box records for the closest-hit rays of triangle-only scenes (FTN_QUAD64=0: the 128-byte records) */
+    st->q64_on = st->t4.q64_ok && S.n_spheres == 0 && knob("FTN_QUAD64", 1) != 0;
+    const size_t need_c = std::max<size_t>((size_t)st->t4.grid_closest * 256u * st->t4.spill_closest * sizeof(uint2),
+                                           st->q64_on ? (size_t)st->t4.grid_q64 * 256u * st->t4.spill_q64 * sizeof(uint2) : 0);
     /* eight-box occlusion records for the any-hit rays of triangle-only scenes (FTN_T8=0: the four-box kernels trace them) */
     st->t8_on = st->t4.oct_ok && S.n_spheres == 0 && knob("FTN_T8", 1) != 0;
     const size_t need_a8 = st->t8_on ? (size_t)st->t4.grid_oct * 256u * st->t4.spill_oct * sizeof(uint32_t) : 0;
@@ -1248,8 +1251,8 @@ static void launch_trace(WavefrontState* st, bool any, int count, bool spheres, 
                          const uint32_t* queue, const uint32_t* count_ptr, uint32_t* head, uint32_t max_rays, bool camera_rays = false) {
     if (st->t4_on && count != 1) {     /* four-box records */
         const Trace4Plan& T = st->t4;
-        const bool oct = any && st->t8_on;
-        const unsigned g = std::min<unsigned>(oct ? T.grid_oct : (any ? T.grid_any : T.grid_closest), std::max<unsigned>(1u, (max_rays + 255u) / 256u));
+        const bool oct = any && st->t8_on, q64 = !any && st->q64_on;
+        const unsigned g = std::min<unsigned>(oct ? T.grid_oct : (any ? T.grid_any : (q64 ? T.grid_q64 : T.grid_closest)), std::max<unsigned>(1u, (max_rays + 255u) / 256u));
         uint32_t chunk4 = knob("FTN_TRACE_CHUNK", 128);
         while (chunk4 > 64u && (uint64_t)chunk4 * g * 4u * 4u > (uint64_t)max_rays) chunk4 >>= 1;
         /* measured optima on the config-5 scene (profiles/r02_*, r03): lanes re-armed once 32 (closest, four-box any-hit) / 24 (eight-box any-hit)
@@ -1262,11 +1265,12 @@ static void launch_trace(WavefrontState* st, bool any, int count, bool spheres, 
          * 25.5 -> 24.9 ms at 4096^2; with rows of 16 pixels it lost 2 %) */
         if (oct) launch_trace4(T4K_ANY_OCT, count == 2, false, g, T.lds_oct, T.entries_oct, st->t4_spill_a, stream, P.S, W, queue, count_ptr, head, P.stats,
                                camera_rays ? knob("FTN_T8_REFILL1", 16) : knob("FTN_T8_REFILL", 24), camera_rays ? knob("FTN_T8_LEAF_BATCH1", 16) : knob("FTN_T8_LEAF_BATCH", 16), chunk4, knob("FTN_T8_BURST", 2), knob("FTN_T8_POLICY", 1), T.spill_oct);
-        else launch_trace4(any ? T4K_ANY : T4K_CLOSEST, count == 2, spheres, g, any ? T.lds_any : T.lds_closest, any ? T.entries_any : T.entries_closest, any ? st->t4_spill_a : st->t4_spill_c, stream, P.S, W,
+        else launch_trace4(any ? T4K_ANY : (q64 ? T4K_CLOSEST_Q64 : T4K_CLOSEST), count == 2, spheres, g, any ? T.lds_any : (q64 ? T.lds_q64 : T.lds_closest),
+                      any ? T.entries_any : (q64 ? T.entries_q64 : T.entries_closest), any ? st->t4_spill_a : st->t4_spill_c, stream, P.S, W,
                       queue, count_ptr, head, P.stats,
                       any ? knob("FTN_T4_ANY_REFILL", 32) : (camera_rays ? knob("FTN_T4_REFILL0", 64) : knob("FTN_T4_REFILL", 32)),
                       any ? knob("FTN_T4_ANY_LEAF_BATCH", 16) : (camera_rays ? knob("FTN_T4_LEAF_BATCH0", 2) : knob("FTN_T4_LEAF_BATCH", 16)), chunk4,
-                      any ? knob("FTN_T4_ANY_BURST", 4) : (camera_rays ? knob("FTN_T4_BURST0", 3) : knob("FTN_T4_BURST", 2)), knob("FTN_T4_ANY_POLICY", 1), any ? T.spill_any : T.spill_closest);
+                      any ? knob("FTN_T4_ANY_BURST", 4) : (camera_rays ? knob("FTN_T4_BURST0", 3) : knob("FTN_T4_BURST", 2)), knob("FTN_T4_ANY_POLICY", 1), any ? T.spill_any : (q64 ? T.spill_q64 : T.spill_closest));
         /* the rays it handed back (a zero direction component: ftn_trace4.hip, point 5) take the reference-order kernel.  The queue is
          * nearly always empty and the persistent workgroups leave at once; its rays are already in the statistics (stats = NULL) */
         const unsigned ge = std::min<unsigned>(grid, (unsigned)st->n_cu);

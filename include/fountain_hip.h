@@ -370,7 +370,7 @@ int ftn_scene_get_nodes(const ftn_scene* scene, ftn_bvh_node* nodes_out, uint32_
  * with shading tangents keep them). */
 typedef struct ftn_scene_memory {
     uint64_t nodes;             /* LinearBVHNode records, 32 B each (reference-order kernels: counting builds, exception rays, megakernel) */
-    uint64_t quad;              /* four-box records, 128 B each (production traversal) */
+    uint64_t quad;              /* four-box records, 128 B each (production traversal), + their 64-byte form and its leaf boxes (triangle-only scenes) */
     uint64_t oct;               /* eight-box occlusion records, 128 B each + explicit leaf boxes (any-hit traversal of triangle scenes) */
     uint64_t fat;               /* two-box records, 64 B each (legacy any-hit kernel; 0 unless asked for) */
     uint64_t geom;              /* triangle vertices, 48 B per primitive (leaf tests) */
