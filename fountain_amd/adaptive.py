@@ -14,18 +14,14 @@ import ctypes as C
 import numpy as np
 
 from . import _abi as A
-from .api import Film, FountainError
-from .moments import _call_args, _check_array, _check_tensor
+from ._nontwin import call_args as _call_args, check_tensor as _check_tensor, checked_lib
+from .api import Film
+from .moments import _check_array
 
 
 def _lib(be):
-    if be.is_oracle:
-        raise FountainError(A.FTN_ERR_UNSUPPORTED, "adaptive sampling has no oracle twin: the reference has no adaptive sampling")
-    have = be.lib.ftn_adaptive_abi_version()
-    if have != A.FTN_ADAPTIVE_ABI_VERSION:
-        raise FountainError(A.FTN_ERR_INTERNAL, "%s reports adaptive ABI version %d, this binding was written for %d: rebuild the library"
-                            % (be.path, have, A.FTN_ADAPTIVE_ABI_VERSION))
-    return be.lib
+    return checked_lib(be, "adaptive sampling has no oracle twin: the reference has no adaptive sampling", "adaptive", "ftn_adaptive_abi_version",
+                       A.FTN_ADAPTIVE_ABI_VERSION)
 
 
 def params(be, **overrides):

@@ -1,12 +1,15 @@
 /*
  * ftn_denoise_host.cpp -- C entry points of include/fountain_hip_denoise.h.
  *
- * They are part of the host library's translation unit: this file includes ftn_gbuffer_host.cpp (which includes ftn_host.cpp) and the
- * Makefile compiles it in its place, so that the entry points share that file's error reporting, device selection and host thread
- * budget (fail, set_device, parallel_for) without exporting them.  The filter's math is ftn_denoise.h's, shared with the kernels.
+ * The filter's math is ftn_denoise.h's, shared with the kernels; error reporting, device selection and the host thread budget are the host
+ * library's (ftn_host_internal.h).
  */
-#include "ftn_gbuffer_host.cpp"
+#include "ftn_host_internal.h"
 #include "ftn_denoise.h"
+
+#include <cstring>
+
+using namespace ftn;
 
 extern "C" {
 

@@ -1,13 +1,16 @@
 /*
  * ftn_gbuffer_host.cpp -- C entry points of include/fountain_hip_gbuffer.h.
  *
- * They are part of the host library's translation unit: this file includes ftn_host.cpp and the Makefile compiles it in its place, so
- * that the entry points share that file's scene internals (device arrays, tile-list cache, film accumulators, WavefrontState) and its
- * tile and device rules without exporting them.
+ * The pass takes the steps of every render call (ftn_host_internal.h): the scene's tile-list cache and film accumulators (the samples whose
+ * footprint leaves their own pixel are summed there), with PathIntegrator of max_depth 0 in the parameters.
  */
-#include "ftn_host.cpp"
+#include "ftn_host_internal.h"
 #include "../../include/fountain_hip_gbuffer.h"
 #include "ftn_gbuffer.h"
+
+#include <cstring>
+
+using namespace ftn;
 
 extern "C" {
 
@@ -25,75 +28,19 @@ int ftn_render_gbuffer_device(const ftn_scene* cs, const ftn_camera_desc* cam, c
     if (pipeline != FTN_PIPELINE_AUTO && pipeline != FTN_PIPELINE_WAVEFRONT) return fail(FTN_ERR_INVALID_ARGUMENT, "unknown pipeline");
     if (ftn_device_count() <= 0) return fail(FTN_ERR_NO_DEVICE, "no HIP device available: the fountain HIP path needs an AMD GPU (there is no CPU fallback)");
     ftn_scene* s = const_cast<ftn_scene*>(cs);
-    if (opt && opt->device >= 0 && s->device >= 0 && opt->device != s->device) return fail(FTN_ERR_INVALID_ARGUMENT, "ftn_render_options.device differs from the device the scene was created on");
-    int rc = set_device(opt && opt->device >= 0 ? opt->device : s->device); if (rc) return rc;
+    int rc = bind_scene_device(s, opt); if (rc) return rc;
     hipStream_t stream = (hipStream_t)stream_v;
     if ((uint64_t)sd->first_sample > (uint64_t)sd->samples_per_pixel || (uint64_t)sd->first_sample + (uint64_t)sd->sample_count > (uint64_t)sd->samples_per_pixel)
         return fail(FTN_ERR_INVALID_ARGUMENT, "sample range outside [0, samples_per_pixel]");
 
-    /* the tile selection of ftn_render_device, through the same cache (key, host list, device copy) */
-    const uint32_t stride = tr && tr->stride ? tr->stride : 1, first = tr ? tr->first : 0, cnt = tr ? tr->count : 0;
-    int32_t key[10] = {film->crop[0], film->crop[1], film->crop[2], film->crop[3], (int32_t)ftn_det::f2u(film->filter_radius[0]), (int32_t)ftn_det::f2u(film->filter_radius[1]),
-                       (int32_t)first, (int32_t)stride, (int32_t)cnt, 1};
-    const bool tiles_cached = memcmp(key, s->tile_key, sizeof(key)) == 0;
-    if (!tiles_cached) {
-        memset(s->tile_key, 0, sizeof(s->tile_key));
-        std::vector<DTile> all; list_tiles(film, &all);
-        s->sel.clear();
-        for (size_t i = first, k = 0; i < all.size() && (cnt == 0 || k < cnt); i += stride, k++) s->sel.push_back(all[i]);
-        uint32_t off = 0; for (DTile& t : s->sel) { t.valid_off = off; t._pad = 0; off += (uint32_t)((t.x1 - t.x0) * (t.y1 - t.y0)); }
-    }
-    std::vector<DTile>& sel = s->sel;
-
-    RenderParams P; memset(&P, 0, sizeof(P));
-    P.S = s->d;
-    memcpy(P.C.c2w, cam->camera_to_world.m, 64); memcpy(P.C.r2c, cam->raster_to_camera.m, 64);
-    P.C.shutter_open = cam->shutter_open; P.C.shutter_close = cam->shutter_close; P.C.lens_radius = cam->lens_radius; P.C.focal_dist = cam->focal_dist;
-    for (int k = 0; k < 3; k++) { P.C.dx_camera[k] = cam->dx_camera[k]; P.C.dy_camera[k] = cam->dy_camera[k]; }
-    for (int i = 0; i < 4; i++) P.crop[i] = film->crop[i];
-    P.radius[0] = film->filter_radius[0]; P.radius[1] = film->filter_radius[1]; P.inv_radius[0] = 1.0f / P.radius[0]; P.inv_radius[1] = 1.0f / P.radius[1];
-    P.sampler_kind = sd->kind; P.spp = sd->samples_per_pixel; P.seed = sd->seed;
-    P.first_sample = sd->first_sample;
-    P.last_sample = sd->first_sample + (sd->sample_count ? sd->sample_count : (sd->samples_per_pixel - sd->first_sample));
-    P.integrator_kind = FTN_INTEGRATOR_PATH;
-    P.stack_entries = s->stack_entries;
-
-    const size_t npix = (size_t)std::max(0, film->crop[2] - film->crop[0]) * (size_t)std::max(0, film->crop[3] - film->crop[1]);
-    /* the samples whose footprint leaves their own pixel are summed in the scene's three film accumulators (12 floats per pixel), under the
-     * rules ftn_render_device keeps for them: accA is cleared on every call, accB / accC while spill_acc_dirty says they may be non-zero */
-    if (npix > s->acc_pixels) {
-        s->accA.release(); s->accB.release(); s->accC.release(); s->acc_pixels = 0;
-        HIP_TRY(hipMalloc((void**)&s->accA.p, npix * sizeof(float4))); HIP_TRY(hipMalloc((void**)&s->accB.p, npix * sizeof(float4))); HIP_TRY(hipMalloc((void**)&s->accC.p, npix * sizeof(float4)));
-        s->acc_pixels = npix; s->spill_acc_dirty = true;
-    }
-    if (sel.size() > s->tiles.n) { s->tiles.release(); HIP_TRY(hipMalloc((void**)&s->tiles.p, sel.size() * sizeof(DTile))); s->tiles.n = sel.size(); }
-    if (npix) {
-        HIP_TRY(hipMemsetAsync(s->accA.p, 0, npix * sizeof(float4), stream));
-        if (s->spill_acc_dirty) { HIP_TRY(hipMemsetAsync(s->accB.p, 0, npix * sizeof(float4), stream)); HIP_TRY(hipMemsetAsync(s->accC.p, 0, npix * sizeof(float4), stream)); }
-    }
-    s->spill_acc_dirty = true;         /* until this call has finished and reported otherwise */
-    HIP_TRY(hipMemsetAsync(s->stats.p, 0, sizeof(DevStats), stream));
-    if (!tiles_cached) {
-        if (!sel.empty()) HIP_TRY(hipMemcpyAsync(s->tiles.p, sel.data(), sel.size() * sizeof(DTile), hipMemcpyHostToDevice, stream));
-        memcpy(s->tile_key, key, sizeof(key));
-    }
-    P.tiles = s->tiles.p; P.n_tiles = (uint32_t)sel.size();
-    P.stats = s->stats.p;
-
-    struct EventPair {
-        hipEvent_t a = nullptr, b = nullptr;
-        ~EventPair() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-    } ev;
-    HIP_TRY(hipEventCreate(&ev.a)); HIP_TRY(hipEventCreate(&ev.b));
-    HIP_TRY(hipEventRecord(ev.a, stream));
+    ftn_integrator_desc first_hit; memset(&first_hit, 0, sizeof(first_hit)); first_hit.kind = FTN_INTEGRATOR_PATH;
+    RenderParams P = render_params(s, cam, film, sd, &first_hit);
+    if ((rc = scene_tiles(s, film, tr, stream, &P)) || (rc = prepare_film(s, false, stream, &P))) return rc;
+    EventPair ev; if ((rc = ev.start(stream))) return rc;
     double trace_ms = 0.0;
-    if ((rc = wavefront_gbuffer(&s->wf, P, sel, cam->camera_to_world.inv, (float*)device_pixels, s->accA.p, s->accB.p, s->accC.p, stream, &trace_ms))) return fail(rc, wavefront_error());
-    HIP_TRY(hipEventRecord(ev.b, stream));
-    HIP_TRY(hipEventSynchronize(ev.b));
-    HIP_TRY(hipGetLastError());
-    float ms = 0.0f; (void)hipEventElapsedTime(&ms, ev.a, ev.b);
-    DevStats ds; HIP_TRY(hipMemcpy(&ds, s->stats.p, sizeof(ds), hipMemcpyDeviceToHost));
-    s->spill_acc_dirty = ds.bc_writes != 0;
+    if ((rc = wavefront_gbuffer(&s->wf, P, s->sel, cam->camera_to_world.inv, (float*)device_pixels, P.accA, P.accB, P.accC, stream, &trace_ms))) return fail(rc, wavefront_error());
+    float ms; if ((rc = ev.stop(stream, &ms))) return rc;
+    DevStats ds; if ((rc = read_stats(s, false, &ds))) return rc;
     if (st) {
         memset(st, 0, sizeof(*st));
         st->rays_closest = ds.rays_closest; st->camera_samples = ds.camera_samples; st->spill_samples = ds.spill_samples;
@@ -108,8 +55,7 @@ int ftn_render_gbuffer(const ftn_scene* cs, const ftn_camera_desc* cam, const ft
     if (sd->kind == FTN_SAMPLER_TILE_SERIAL || (opt && opt->pipeline == FTN_PIPELINE_MEGAKERNEL))          /* (the refusals come before any device work) */
         return ftn_render_gbuffer_device(cs, cam, film, sd, tr, opt, out_pixels, nullptr, st);
     if (ftn_device_count() <= 0) return fail(FTN_ERR_NO_DEVICE, "no HIP device available: the fountain HIP path needs an AMD GPU (there is no CPU fallback)");
-    if (opt && opt->device >= 0 && cs->device >= 0 && opt->device != cs->device) return fail(FTN_ERR_INVALID_ARGUMENT, "ftn_render_options.device differs from the device the scene was created on");
-    int rc = set_device(opt && opt->device >= 0 ? opt->device : cs->device); if (rc) return rc;
+    int rc = bind_scene_device(cs, opt); if (rc) return rc;
     const size_t npix = (size_t)std::max(0, film->crop[2] - film->crop[0]) * (size_t)std::max(0, film->crop[3] - film->crop[1]);
     /* the caller's sums go to the device and come back: every pixel's own samples are added to them one at a time (not summed apart and
      * added at the end), so splitting a sample range over calls gives the bits of one call */

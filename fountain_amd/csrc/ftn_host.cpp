@@ -8,8 +8,7 @@
  *   - the render driver (SamplerIntegrator::render_parallel, src/integrator/mod.rs:218-227).
  * There is no CPU fallback: every compute entry point needs a HIP device and fails with FTN_ERR_NO_DEVICE without one.
  */
-#include "ftn_kernels.h"
-#include "ftn_wavefront.h"
+#include "ftn_host_internal.h"
 #include "ftn_texture.h"
 
 #include <algorithm>
@@ -34,8 +33,7 @@ static_assert(sizeof(ftn_envmap) == 16 && sizeof(ftn_camera_desc) == 296 && size
 static_assert(sizeof(ftn_integrator_desc) == 16 && sizeof(ftn_tile_range) == 16 && sizeof(ftn_render_options) == 16 && sizeof(ftn_stats) == 152, "ABI");
 
 static thread_local std::string g_err;
-static int fail(int code, const std::string& msg) { g_err = msg; return code; }
-#define HIP_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return fail(e_ == hipErrorOutOfMemory ? FTN_ERR_OUT_OF_MEMORY : FTN_ERR_NO_DEVICE, std::string(#expr ": ") + hipGetErrorString(e_)); } while (0)
+int fail(int code, const std::string& msg) { g_err = msg; return code; }
 
 /* ================================================================== Transform algebra (cgmath 0.17 Matrix4 semantics) */
 static void m4_identity(float* m) { for (int i = 0; i < 16; i++) m[i] = (i % 5 == 0) ? 1.0f : 0.0f; }
@@ -180,14 +178,6 @@ int ftn_film_sample_bounds(const ftn_film_desc* f, int32_t o[4]) {              
     o[2] = f2i_sat(ceilf((float)f->crop[2] - 0.5f + f->filter_radius[0])); o[3] = f2i_sat(ceilf((float)f->crop[3] - 0.5f + f->filter_radius[1]));
     return FTN_OK;
 }
-static void list_tiles(const ftn_film_desc* f, std::vector<DTile>* tiles) {        /* bounds.rs:85-97, integrator/mod.rs:182-185 */
-    int32_t sb[4]; ftn_film_sample_bounds(f, sb);
-    for (int y = sb[1]; y < sb[3]; y += 16) for (int x = sb[0]; x < sb[2]; x += 16) {
-        DTile t; t.valid_off = 0; t._pad = 0; t.x0 = x; t.y0 = y; t.x1 = std::min(x + 16, sb[2]); t.y1 = std::min(y + 16, sb[3]);
-        t.tile_id = (unsigned long long)(long long)(t.y0 * sb[2] + t.x0);
-        tiles->push_back(t);
-    }
-}
 int ftn_film_tile_count(const ftn_film_desc* f, uint32_t* out) { std::vector<DTile> t; list_tiles(f, &t); *out = (uint32_t)t.size(); return FTN_OK; }
 int ftn_film_resolve(const ftn_pixel* p, size_t n, float* rgb_out) {               /* film.rs:195-210 (host buffers; output stage) */
     for (size_t i = 0; i < n; i++) {
@@ -200,31 +190,23 @@ int ftn_film_resolve(const ftn_pixel* p, size_t n, float* rgb_out) {            
 
 }  /* extern "C" */
 
+void list_tiles(const ftn_film_desc* f, std::vector<DTile>* tiles) {               /* bounds.rs:85-97, integrator/mod.rs:182-185 */
+    int32_t sb[4]; ftn_film_sample_bounds(f, sb);
+    for (int y = sb[1]; y < sb[3]; y += 16) for (int x = sb[0]; x < sb[2]; x += 16) {
+        DTile t; t.valid_off = 0; t._pad = 0; t.x0 = x; t.y0 = y; t.x1 = std::min(x + 16, sb[2]); t.y1 = std::min(y + 16, sb[3]);
+        t.tile_id = (unsigned long long)(long long)(t.y0 * sb[2] + t.x0);
+        tiles->push_back(t);
+    }
+}
+
 /* ================================================================== BVH::build (bvh.rs:27-158), written directly in flattened DFS order */
 namespace {
 
-struct Aabb { float lo[3], hi[3]; };
 static const float kFmax = 3.402823466e+38f;
 static Aabb aabb_empty() { Aabb b; for (int i = 0; i < 3; i++) { b.lo[i] = kFmax; b.hi[i] = -kFmax; } return b; }
 static void aabb_join_point(Aabb& b, V3 p) { b.lo[0] = fmin_(b.lo[0], p.x); b.lo[1] = fmin_(b.lo[1], p.y); b.lo[2] = fmin_(b.lo[2], p.z); b.hi[0] = fmax_(b.hi[0], p.x); b.hi[1] = fmax_(b.hi[1], p.y); b.hi[2] = fmax_(b.hi[2], p.z); }
 
-/* ------------------------------------------------------------------ host threads for the per-element passes of ftn_scene_create
- * (this process's share of the host: bvh_default_threads; FTN_BVH_THREADS overrides; at most 32).  f(begin, end) over [0, n) in
- * contiguous blocks: every pass that uses it writes each element from that element's inputs alone, so the result does not depend on
- * the number of threads. */
 static int bvh_default_threads();
-static int host_threads() {
-    int n = bvh_default_threads();
-    if (const char* e = getenv("FTN_BVH_THREADS")) n = atoi(e);
-    return std::max(1, std::min(n, 32));
-}
-template <class F> static void parallel_for(size_t n, F f) {
-    const int nt = (int)std::min<size_t>((size_t)host_threads(), n / 65536 + 1);
-    if (nt <= 1) { f((size_t)0, n); return; }
-    std::vector<std::thread> th;
-    for (int t = 0; t < nt; t++) th.emplace_back([&, t]() { f(n * (size_t)t / (size_t)nt, n * (size_t)(t + 1) / (size_t)nt); });
-    for (auto& x : th) x.join();
-}
 
 struct BvhBuilder {
     const std::vector<Aabb>& bounds;
@@ -696,11 +678,6 @@ static int bvh_default_threads() {
     return std::max(1, cores / ranks);
 }
 
-struct HostScene {
-    std::vector<ftn_bvh_node> nodes; std::vector<uint32_t> order; uint32_t max_depth = 0; Aabb world;
-    std::vector<int32_t> light_kind, light_prim;
-};
-
 static Aabb prim_bounds(const ftn_scene_desc* d, const ftn_prim& p) {
     Aabb b = aabb_empty();
     if (p.shape_kind == FTN_SHAPE_TRIANGLE) {                                      /* Triangle::world_bound triangle.rs:152-158 */
@@ -810,24 +787,14 @@ static float dist1d_build(const float* f, size_t n, float* cdf) {
     return integral;
 }
 
-template <class T> struct DevBuf {
-    T* p = nullptr; size_t n = 0;
-    int upload(const T* src, size_t count) {
-        n = count; if (!count) return FTN_OK;
-        HIP_TRY(hipMalloc((void**)&p, count * sizeof(T)));
-        HIP_TRY(hipMemcpy(p, src, count * sizeof(T), hipMemcpyHostToDevice));
-        return FTN_OK;
-    }
-    int alloc_zero(size_t count) {
-        n = count; if (!count) return FTN_OK;
-        HIP_TRY(hipMalloc((void**)&p, count * sizeof(T)));
-        HIP_TRY(hipMemset(p, 0, count * sizeof(T)));
-        return FTN_OK;
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; n = 0; }
-};
-
 }  // namespace
+
+/* host threads for the per-element passes (parallel_for): this process's share of the host (bvh_default_threads), FTN_BVH_THREADS overrides */
+int host_threads() {
+    int n = bvh_default_threads();
+    if (const char* e = getenv("FTN_BVH_THREADS")) n = atoi(e);
+    return std::max(1, std::min(n, 32));
+}
 
 /* ------------------------------------------------------------------ MIPMap::<Spectrum>::new (mipmap.rs:78-145): level 0 = the image, every further
  * level = the previous one shrunk to max(1, w/2) x max(1, h/2) by the `resize` crate's Triangle filter (resize 0.4.3, un-vendored:
@@ -882,28 +849,6 @@ static void build_mip_pyramid(uint32_t w, uint32_t h, const float* rgb, std::vec
     }
 }
 }  // namespace
-
-struct ftn_scene {
-    int device = 0;
-    HostScene host;
-    DScene d; uint32_t stack_entries = 1;
-    DevBuf<float4> nodes, geom, fat, srec, quad, oct_xbox, quad64_xbox; DevBuf<uint4> prim_info, oct, quad64; DevBuf<float> N, UV, T; DevBuf<DSphere> spheres; DevBuf<ftn_material> materials; DevBuf<DLight> lights;
-    DevBuf<uint32_t> inf_lights; DevBuf<unsigned char> prim_class; std::vector<DevBuf<float>> misc; std::vector<DevBuf<float4>> misc4;
-    DevBuf<ftn_texture> textures; DevBuf<ftn_material_textures> mtex; DevBuf<DImage> images; DevBuf<float4> texels;
-    /* render work buffers (grow-only, reused across calls) */
-    DevBuf<float4> accA, accB, accC; DevBuf<DTile> tiles; DevBuf<DevStats> stats; size_t acc_pixels = 0;
-    bool spill_acc_dirty = true;       /* accB / accC may hold something other than zeros */
-    WavefrontState* wf = nullptr;
-    std::vector<DTile> sel; int32_t tile_key[10] = {0};
-    ~ftn_scene() {
-        nodes.release(); geom.release(); fat.release(); srec.release(); quad.release(); quad64.release(); quad64_xbox.release(); oct.release(); oct_xbox.release(); prim_info.release(); N.release(); UV.release(); T.release(); spheres.release(); materials.release(); lights.release(); inf_lights.release(); prim_class.release();
-        for (auto& b : misc) b.release();
-        for (auto& b : misc4) b.release();
-        textures.release(); mtex.release(); images.release(); texels.release();
-        accA.release(); accB.release(); accC.release(); tiles.release(); stats.release();
-        wavefront_destroy(wf);
-    }
-};
 
 /* FTN_SCENE_DEBUG: wall time of the phases of ftn_scene_create on stderr */
 struct PhaseClock {
@@ -1228,7 +1173,7 @@ static int upload_scene(const ftn_scene_desc* d, ftn_scene* sc) {
     return FTN_OK;
 }
 
-static int set_device(int device) {
+int set_device(int device) {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || n == 0) return fail(FTN_ERR_NO_DEVICE, "no HIP device available: the fountain HIP path needs an AMD GPU (there is no CPU fallback)");
     if (device >= 0) {
@@ -1236,6 +1181,123 @@ static int set_device(int device) {
         if (e != hipSuccess) { (void)hipGetLastError();      /* do not leave the error behind for the next call's hipGetLastError() */
                                return fail(FTN_ERR_NO_DEVICE, std::string("hipSetDevice(device): ") + hipGetErrorString(e)); }
     }
+    return FTN_OK;
+}
+
+void stats_out(const DevStats& ds, ftn_stats* st, double ms) {
+    if (!st) return;
+    memset(st, 0, sizeof(*st));
+    st->rays_closest = ds.rays_closest; st->rays_any = ds.rays_any; st->nodes_visited = ds.nodes_visited; st->prims_tested = ds.prims_tested;
+    st->camera_samples = ds.camera_samples; st->spill_samples = ds.spill_samples; st->kernel_ms = ms;
+    st->nodes_visited_any = ds.nodes_any; st->prims_tested_any = ds.prims_any;
+    st->quad_records = ds.quad_records; st->quad_records_any = ds.quad_records_any;
+}
+
+/* ------------------------------------------------------------------ the steps of a render call (ftn_host_internal.h) */
+int bind_scene_device(const ftn_scene* s, const ftn_render_options* opt) {
+    if (opt && opt->device >= 0 && s->device >= 0 && opt->device != s->device) return fail(FTN_ERR_INVALID_ARGUMENT, "ftn_render_options.device differs from the device the scene was created on");
+    return set_device(opt && opt->device >= 0 ? opt->device : s->device);
+}
+
+void select_tiles(const ftn_film_desc* film, const ftn_tile_range* tr, std::vector<DTile>* sel) {
+    const uint32_t stride = tr && tr->stride ? tr->stride : 1, first = tr ? tr->first : 0, cnt = tr ? tr->count : 0;
+    std::vector<DTile> all; list_tiles(film, &all);
+    sel->clear();
+    for (size_t i = first, k = 0; i < all.size() && (cnt == 0 || k < cnt); i += stride, k++) sel->push_back(all[i]);
+    uint32_t off = 0; for (DTile& t : *sel) { t.valid_off = off; t._pad = 0; off += (uint32_t)((t.x1 - t.x0) * (t.y1 - t.y0)); }
+}
+
+int scene_tiles(ftn_scene* s, const ftn_film_desc* film, const ftn_tile_range* tr, hipStream_t stream, RenderParams* P) {
+    /* the tile list only depends on the film and the tile range: keep it (and its device copy) between calls */
+    const uint32_t stride = tr && tr->stride ? tr->stride : 1, first = tr ? tr->first : 0, cnt = tr ? tr->count : 0;
+    const int32_t key[10] = {film->crop[0], film->crop[1], film->crop[2], film->crop[3], (int32_t)ftn_det::f2u(film->filter_radius[0]), (int32_t)ftn_det::f2u(film->filter_radius[1]),
+                             (int32_t)first, (int32_t)stride, (int32_t)cnt, 1};
+    if (memcmp(key, s->tile_key, sizeof(key)) != 0) {
+        memset(s->tile_key, 0, sizeof(s->tile_key));      /* the host list is about to change: no key is valid until list AND device copy are in place */
+        select_tiles(film, tr, &s->sel);
+        if (s->sel.size() > s->tiles.n) { s->tiles.release(); HIP_TRY(hipMalloc((void**)&s->tiles.p, s->sel.size() * sizeof(DTile))); s->tiles.n = s->sel.size(); }
+        if (!s->sel.empty()) HIP_TRY(hipMemcpyAsync(s->tiles.p, s->sel.data(), s->sel.size() * sizeof(DTile), hipMemcpyHostToDevice, stream));
+        memcpy(s->tile_key, key, sizeof(key));            /* (an empty selection is a valid cached state too) */
+    }
+    P->tiles = s->tiles.p; P->n_tiles = (uint32_t)s->sel.size();
+    return FTN_OK;
+}
+
+RenderParams render_params(const ftn_scene* s, const ftn_camera_desc* cam, const ftn_film_desc* film, const ftn_sampler_desc* sd, const ftn_integrator_desc* id) {
+    RenderParams P; memset(&P, 0, sizeof(P));
+    P.S = s->d;
+    memcpy(P.C.c2w, cam->camera_to_world.m, 64); memcpy(P.C.r2c, cam->raster_to_camera.m, 64);
+    P.C.shutter_open = cam->shutter_open; P.C.shutter_close = cam->shutter_close; P.C.lens_radius = cam->lens_radius; P.C.focal_dist = cam->focal_dist;
+    for (int k = 0; k < 3; k++) { P.C.dx_camera[k] = cam->dx_camera[k]; P.C.dy_camera[k] = cam->dy_camera[k]; }
+    for (int i = 0; i < 4; i++) P.crop[i] = film->crop[i];
+    P.radius[0] = film->filter_radius[0]; P.radius[1] = film->filter_radius[1]; P.inv_radius[0] = 1.0f / P.radius[0]; P.inv_radius[1] = 1.0f / P.radius[1];
+    const bool indexed = sd->kind == FTN_SAMPLER_INDEXED;
+    P.sampler_kind = sd->kind; P.spp = sd->samples_per_pixel; P.seed = sd->seed;
+    P.first_sample = indexed ? sd->first_sample : 0;
+    P.last_sample = indexed ? sd->first_sample + (sd->sample_count ? sd->sample_count : (sd->samples_per_pixel - sd->first_sample)) : sd->samples_per_pixel;
+    P.integrator_kind = id->kind; P.max_depth = id->max_depth; P.rr_threshold = id->rr_threshold;
+    P.stack_entries = s->stack_entries;
+    return P;
+}
+
+int FilmAcc::prepare(size_t npix, hipStream_t stream) {
+    if (npix > pixels) {
+        release();                     /* (pixels = 0 until all three exist again) */
+        HIP_TRY(hipMalloc((void**)&own.p, npix * sizeof(float4))); HIP_TRY(hipMalloc((void**)&in_tile.p, npix * sizeof(float4))); HIP_TRY(hipMalloc((void**)&other_tile.p, npix * sizeof(float4)));
+        pixels = npix;
+    }
+    if (npix) {
+        HIP_TRY(hipMemsetAsync(own.p, 0, npix * sizeof(float4), stream));
+        if (spill_dirty) {             /* else: still all zero from the last call (DevStats::bc_writes said nothing was added) */
+            HIP_TRY(hipMemsetAsync(in_tile.p, 0, npix * sizeof(float4), stream));
+            HIP_TRY(hipMemsetAsync(other_tile.p, 0, npix * sizeof(float4), stream));
+        }
+    }
+    spill_dirty = true;                /* until this call has finished and reported otherwise */
+    return FTN_OK;
+}
+
+int prepare_film(ftn_scene* s, bool moments, hipStream_t stream, RenderParams* P) {
+    const size_t npix = (size_t)std::max(0, P->crop[2] - P->crop[0]) * (size_t)std::max(0, P->crop[3] - P->crop[1]);
+    int rc = s->acc.prepare(npix, stream); if (rc) return rc;
+    if (moments && (rc = s->moments.prepare(npix, stream))) return rc;
+    HIP_TRY(hipMemsetAsync(s->stats.p, 0, sizeof(DevStats), stream));
+    P->accA = s->acc.own.p; P->accB = s->acc.in_tile.p; P->accC = s->acc.other_tile.p; P->stats = s->stats.p;
+    return FTN_OK;
+}
+
+int EventPair::start(hipStream_t stream) {
+    HIP_TRY(hipEventCreate(&a)); HIP_TRY(hipEventCreate(&b));
+    HIP_TRY(hipEventRecord(a, stream));
+    return FTN_OK;
+}
+int EventPair::stop(hipStream_t stream, float* ms) {
+    HIP_TRY(hipEventRecord(b, stream));
+    HIP_TRY(hipEventSynchronize(b));
+    HIP_TRY(hipGetLastError());
+    *ms = 0.0f; (void)hipEventElapsedTime(ms, a, b);
+    return FTN_OK;
+}
+
+int read_stats(ftn_scene* s, bool moments, DevStats* ds) {
+    HIP_TRY(hipMemcpy(ds, s->stats.p, sizeof(*ds), hipMemcpyDeviceToHost));
+    s->acc.spill_dirty = ds->bc_writes != 0;
+    if (moments) s->moments.spill_dirty = ds->bc_writes != 0;     /* the moments' footprints are the beauty's: they spilled exactly where it did */
+    return FTN_OK;
+}
+
+void render_stats_out(DevStats ds, const WavefrontTimes& wt, float ms, ftn_stats* st) {
+    ds.rays_closest += wt.mis_any_rays; ds.rays_any -= wt.mis_any_rays;       /* they are Scene::intersect calls in the reference's accounting */
+    stats_out(ds, st, ms);
+    if (st) {
+        st->trace_ms = wt.trace_ms; st->trace_launches = wt.trace_launches; st->mis_rays_any_hit = wt.mis_any_rays;
+        st->any_ms = wt.any_ms; st->any_launches = wt.any_launches; st->shade_ms = wt.shade_ms; st->shade_launches = wt.shade_launches; st->sort_ms = wt.sort_ms;
+    }
+}
+
+int render_error(int error) {
+    if (error == FTN_ERR_NAN_RADIANCE) return fail(FTN_ERR_NAN_RADIANCE, "NaN radiance value (integrator/mod.rs:285-287)");
+    if (error) return fail(error, "unsupported material / integrator combination (e.g. specular glass: material/glass.rs:66)");
     return FTN_OK;
 }
 
@@ -1346,14 +1408,6 @@ int ftn_scene_get_lights(const ftn_scene* s, int32_t* kind, int32_t* prim) {
 }
 
 /* ------------------------------------------------------------------ batch intersection */
-static void stats_out(const DevStats& ds, ftn_stats* st, double ms) {
-    if (!st) return;
-    memset(st, 0, sizeof(*st));
-    st->rays_closest = ds.rays_closest; st->rays_any = ds.rays_any; st->nodes_visited = ds.nodes_visited; st->prims_tested = ds.prims_tested;
-    st->camera_samples = ds.camera_samples; st->spill_samples = ds.spill_samples; st->kernel_ms = ms;
-    st->nodes_visited_any = ds.nodes_any; st->prims_tested_any = ds.prims_any;
-    st->quad_records = ds.quad_records; st->quad_records_any = ds.quad_records_any;
-}
 static int trace_batch(const ftn_scene* cs, const float* rays, size_t n, int mode, float* t_hit, int32_t* prim, float* bary, uint8_t* occ, float* out24, ftn_stats* st) {
     ftn_scene* s = const_cast<ftn_scene*>(cs);
     int rc = set_device(s->device); if (rc) return rc;
@@ -1364,14 +1418,10 @@ static int trace_batch(const ftn_scene* cs, const float* rays, size_t n, int mod
     else if (mode == 1) { if ((rc = d_occ.alloc_zero(n))) { cleanup(); return rc; } }
     else { if ((rc = d_o.alloc_zero(24 * n))) { cleanup(); return rc; } }
     HIP_TRY(hipMemset(s->stats.p, 0, sizeof(DevStats)));
-    hipEvent_t e0, e1; HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1));
-    HIP_TRY(hipEventRecord(e0, 0));
+    EventPair ev; if ((rc = ev.start(0))) { cleanup(); return rc; }
     if (getenv("FTN_BATCH_SIMPLE")) launch_trace_batch(s->d, d_rays.p, n, mode, d_t.p, d_p.p, d_b.p, d_occ.p, d_o.p, s->stats.p, s->stack_entries, st != nullptr, 0);   /* one lane per ray, plain loop */
     else if ((rc = wavefront_trace_batch(&s->wf, s->d, s->stack_entries, d_rays.p, n, mode, st != nullptr, d_t.p, d_p.p, d_b.p, d_occ.p, d_o.p, s->stats.p, 0))) { cleanup(); return fail(rc, wavefront_error()); }
-    HIP_TRY(hipEventRecord(e1, 0));
-    HIP_TRY(hipEventSynchronize(e1));
-    HIP_TRY(hipGetLastError());
-    float ms = 0.0f; (void)hipEventElapsedTime(&ms, e0, e1); (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+    float ms; if ((rc = ev.stop(0, &ms))) { cleanup(); return rc; }
     if (t_hit) HIP_TRY(hipMemcpy(t_hit, d_t.p, n * 4, hipMemcpyDeviceToHost));
     if (prim) HIP_TRY(hipMemcpy(prim, d_p.p, n * 4, hipMemcpyDeviceToHost));
     if (bary) HIP_TRY(hipMemcpy(bary, d_b.p, 3 * n * 4, hipMemcpyDeviceToHost));
@@ -1397,9 +1447,7 @@ int ftn_render_device(const ftn_scene* cs, const ftn_camera_desc* cam, const ftn
                       const ftn_tile_range* tr, const ftn_render_options* opt, void* device_pixels, void* stream_v, ftn_stats* st) {
     if (!cs || !cam || !film || !sd || !id || !device_pixels) return fail(FTN_ERR_INVALID_ARGUMENT, "null argument");
     ftn_scene* s = const_cast<ftn_scene*>(cs);
-    /* the scene's arrays live on the device it was created on: a different device in the options would launch with foreign pointers */
-    if (opt && opt->device >= 0 && s->device >= 0 && opt->device != s->device) return fail(FTN_ERR_INVALID_ARGUMENT, "ftn_render_options.device differs from the device the scene was created on");
-    int rc = set_device(opt && opt->device >= 0 ? opt->device : s->device); if (rc) return rc;
+    int rc = bind_scene_device(s, opt); if (rc) return rc;
     hipStream_t stream = (hipStream_t)stream_v;
     const bool indexed = sd->kind == FTN_SAMPLER_INDEXED;
     /* sample range [first_sample, first_sample + sample_count) must lie inside [0, samples_per_pixel] (64-bit: no wrap-around) */
@@ -1423,86 +1471,26 @@ int ftn_render_device(const ftn_scene* cs, const ftn_camera_desc* cam, const ftn
     const bool count = opt && opt->count_traffic;
     const bool count_production = opt && opt->count_traffic == 2;      /* tally the production configuration instead of the reference's walk */
 
-    const uint32_t stride = tr && tr->stride ? tr->stride : 1, first = tr ? tr->first : 0, cnt = tr ? tr->count : 0;
-    /* the tile list only depends on the film and the tile range: keep it (and its device copy) between calls */
-    int32_t key[10] = {film->crop[0], film->crop[1], film->crop[2], film->crop[3], (int32_t)ftn_det::f2u(film->filter_radius[0]), (int32_t)ftn_det::f2u(film->filter_radius[1]),
-                       (int32_t)first, (int32_t)stride, (int32_t)cnt, 1};
-    const bool tiles_cached = memcmp(key, s->tile_key, sizeof(key)) == 0;
-    if (!tiles_cached) {
-        memset(s->tile_key, 0, sizeof(s->tile_key));      /* the host list is about to change: no key is valid until list AND device copy are in place */
-        std::vector<DTile> all; list_tiles(film, &all);
-        s->sel.clear();
-        for (size_t i = first, k = 0; i < all.size() && (cnt == 0 || k < cnt); i += stride, k++) s->sel.push_back(all[i]);
-        uint32_t off = 0; for (DTile& t : s->sel) { t.valid_off = off; t._pad = 0; off += (uint32_t)((t.x1 - t.x0) * (t.y1 - t.y0)); }
-    }
-    std::vector<DTile>& sel = s->sel;
+    RenderParams P = render_params(s, cam, film, sd, id);
+    if ((rc = scene_tiles(s, film, tr, stream, &P))) return rc;
     /* tile-serial: a round of the queue pipeline costs ~0.3 ms whatever it holds, a megakernel lane per tile diverges from its 63 neighbours:
      * the queues win once a call has a few thousand tiles (measured: profiles/r03), a handful of tiles is the megakernel's */
-    if (auto_pipeline && !indexed && pipeline == FTN_PIPELINE_WAVEFRONT && sel.size() < 2048) pipeline = FTN_PIPELINE_MEGAKERNEL;
+    if (auto_pipeline && !indexed && pipeline == FTN_PIPELINE_WAVEFRONT && P.n_tiles < 2048) pipeline = FTN_PIPELINE_MEGAKERNEL;
+    if ((rc = prepare_film(s, false, stream, &P))) return rc;
 
-    RenderParams P; memset(&P, 0, sizeof(P));
-    P.S = s->d;
-    memcpy(P.C.c2w, cam->camera_to_world.m, 64); memcpy(P.C.r2c, cam->raster_to_camera.m, 64);
-    P.C.shutter_open = cam->shutter_open; P.C.shutter_close = cam->shutter_close; P.C.lens_radius = cam->lens_radius; P.C.focal_dist = cam->focal_dist;
-    for (int k = 0; k < 3; k++) { P.C.dx_camera[k] = cam->dx_camera[k]; P.C.dy_camera[k] = cam->dy_camera[k]; }
-    for (int i = 0; i < 4; i++) P.crop[i] = film->crop[i];
-    P.radius[0] = film->filter_radius[0]; P.radius[1] = film->filter_radius[1]; P.inv_radius[0] = 1.0f / P.radius[0]; P.inv_radius[1] = 1.0f / P.radius[1];
-    P.sampler_kind = sd->kind; P.spp = sd->samples_per_pixel; P.seed = sd->seed;
-    P.first_sample = indexed ? sd->first_sample : 0;
-    P.last_sample = indexed ? sd->first_sample + (sd->sample_count ? sd->sample_count : (sd->samples_per_pixel - sd->first_sample)) : sd->samples_per_pixel;
-    P.integrator_kind = id->kind; P.max_depth = id->max_depth; P.rr_threshold = id->rr_threshold;
-    P.stack_entries = s->stack_entries;
-
-    const size_t npix = (size_t)std::max(0, film->crop[2] - film->crop[0]) * (size_t)std::max(0, film->crop[3] - film->crop[1]);
-    if (npix > s->acc_pixels) {
-        s->accA.release(); s->accB.release(); s->accC.release();
-        HIP_TRY(hipMalloc((void**)&s->accA.p, npix * sizeof(float4))); HIP_TRY(hipMalloc((void**)&s->accB.p, npix * sizeof(float4))); HIP_TRY(hipMalloc((void**)&s->accC.p, npix * sizeof(float4)));
-        s->acc_pixels = npix; s->spill_acc_dirty = true;
-    }
-    if (sel.size() > s->tiles.n) { s->tiles.release(); HIP_TRY(hipMalloc((void**)&s->tiles.p, sel.size() * sizeof(DTile))); s->tiles.n = sel.size(); }
-    HIP_TRY(hipMemsetAsync(s->accA.p, 0, npix * sizeof(float4), stream));
-    if (s->spill_acc_dirty) {          /* else: still all zero from the last call (DevStats::bc_writes said nothing was added) */
-        HIP_TRY(hipMemsetAsync(s->accB.p, 0, npix * sizeof(float4), stream));
-        HIP_TRY(hipMemsetAsync(s->accC.p, 0, npix * sizeof(float4), stream));
-    }
-    s->spill_acc_dirty = true;         /* until this call has finished and reported otherwise */
-    HIP_TRY(hipMemsetAsync(s->stats.p, 0, sizeof(DevStats), stream));
-    if (!tiles_cached) {
-        if (!sel.empty()) HIP_TRY(hipMemcpyAsync(s->tiles.p, sel.data(), sel.size() * sizeof(DTile), hipMemcpyHostToDevice, stream));
-        memcpy(s->tile_key, key, sizeof(key));            /* (an empty selection is a valid cached state too) */
-    }
-    P.tiles = s->tiles.p; P.n_tiles = (uint32_t)sel.size();
-    P.accA = s->accA.p; P.accB = s->accB.p; P.accC = s->accC.p; P.stats = s->stats.p;
-
-    struct EventPair {                                    /* destroyed on every way out */
-        hipEvent_t a = nullptr, b = nullptr;
-        ~EventPair() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-    } ev;
-    HIP_TRY(hipEventCreate(&ev.a)); HIP_TRY(hipEventCreate(&ev.b));
-    HIP_TRY(hipEventRecord(ev.a, stream));
+    EventPair ev; if ((rc = ev.start(stream))) return rc;
     WavefrontTimes wt; memset(&wt, 0, sizeof(wt));
-    if (pipeline == FTN_PIPELINE_WAVEFRONT) { rc = wavefront_render(&s->wf, P, sel, count, stream, &wt, count_production); if (rc) return fail(rc, wavefront_error()); }
+    if (pipeline == FTN_PIPELINE_WAVEFRONT) { rc = wavefront_render(&s->wf, P, s->sel, count, stream, &wt, count_production); if (rc) return fail(rc, wavefront_error()); }
     else launch_render_mega(P, count, stream);
     launch_film_resolve(P, (ftn_pixel*)device_pixels, stream);
-    HIP_TRY(hipEventRecord(ev.b, stream));
-    HIP_TRY(hipEventSynchronize(ev.b));
-    HIP_TRY(hipGetLastError());
-    float ms = 0.0f; (void)hipEventElapsedTime(&ms, ev.a, ev.b);
-    DevStats ds; HIP_TRY(hipMemcpy(&ds, s->stats.p, sizeof(ds), hipMemcpyDeviceToHost));
-    s->spill_acc_dirty = ds.bc_writes != 0;
-    ds.rays_closest += wt.mis_any_rays; ds.rays_any -= wt.mis_any_rays;       /* they are Scene::intersect calls in the reference's accounting */
-    stats_out(ds, st, ms);
+    float ms; if ((rc = ev.stop(stream, &ms))) return rc;
+    DevStats ds; if ((rc = read_stats(s, false, &ds))) return rc;
     if (ds.t4_occ[0] | ds.t4_occ[7]) { const char* dbg = getenv("FTN_WF_DEBUG"); if (dbg && atoi(dbg)) {     /* lane occupancy of the counting builds (experiments) */
         for (int k = 0; k < 2; k++) { const unsigned long long* o = &ds.t4_occ[7 * k]; if (!o[0]) continue;
             fprintf(stderr, "[wf] %s four-box trace: %llu control rounds; %llu record steps with %.1f of 64 lanes; %llu leaf steps with %.1f lanes; %llu refills of %.1f lanes\n", k ? "any-hit" : "closest-hit",
                     o[0], o[1], o[1] ? (double)o[2] / (double)o[1] : 0.0, o[3], o[3] ? (double)o[4] / (double)o[3] : 0.0, o[5], o[5] ? (double)o[6] / (double)o[5] : 0.0); } } }
-    if (st) {
-        st->trace_ms = wt.trace_ms; st->trace_launches = wt.trace_launches; st->mis_rays_any_hit = wt.mis_any_rays;
-        st->any_ms = wt.any_ms; st->any_launches = wt.any_launches; st->shade_ms = wt.shade_ms; st->shade_launches = wt.shade_launches; st->sort_ms = wt.sort_ms;
-    }
-    if (ds.error == FTN_ERR_NAN_RADIANCE) return fail(FTN_ERR_NAN_RADIANCE, "NaN radiance value (integrator/mod.rs:285-287)");
-    if (ds.error) return fail(ds.error, "unsupported material / integrator combination (e.g. specular glass: material/glass.rs:66)");
-    return FTN_OK;
+    render_stats_out(ds, wt, ms, st);
+    return render_error(ds.error);
 }
 
 int ftn_test_math(int which, const float* x, const float* y, size_t n, float* out) {
@@ -1551,22 +1539,11 @@ int ftn_film_resolve_device(const void* device_pixels, size_t n, void* device_rg
 int ftn_render(const ftn_scene* cs, const ftn_camera_desc* cam, const ftn_film_desc* film, const ftn_sampler_desc* sd, const ftn_integrator_desc* id,
                const ftn_tile_range* tr, const ftn_render_options* opt, ftn_pixel* out_pixels, ftn_stats* st) {
     if (!cs || !film || !out_pixels) return fail(FTN_ERR_INVALID_ARGUMENT, "null argument");
-    if (opt && opt->device >= 0 && cs->device >= 0 && opt->device != cs->device) return fail(FTN_ERR_INVALID_ARGUMENT, "ftn_render_options.device differs from the device the scene was created on");
-    int rc = set_device(opt && opt->device >= 0 ? opt->device : cs->device); if (rc) return rc;
+    int rc = bind_scene_device(cs, opt); if (rc) return rc;
     const size_t npix = (size_t)std::max(0, film->crop[2] - film->crop[0]) * (size_t)std::max(0, film->crop[3] - film->crop[1]);
-    DevBuf<ftn_pixel> dev;
-    if ((rc = dev.alloc_zero(npix))) return rc;
-    rc = ftn_render_device(cs, cam, film, sd, id, tr, opt, dev.p, nullptr, st);
-    if (rc == FTN_OK || rc == FTN_ERR_NAN_RADIANCE) {
-        std::vector<ftn_pixel> h(npix);
-        if (hipMemcpy(h.data(), dev.p, npix * sizeof(ftn_pixel), hipMemcpyDeviceToHost) != hipSuccess) { dev.release(); return fail(FTN_ERR_NO_DEVICE, "copy back failed"); }
-        for (size_t i = 0; i < npix; i++) {                                       /* merge_pixel.xyz[i] += xyz[i] (film.rs:127-130) */
-            out_pixels[i].xyz[0] += h[i].xyz[0]; out_pixels[i].xyz[1] += h[i].xyz[1]; out_pixels[i].xyz[2] += h[i].xyz[2];
-            out_pixels[i].filter_weight_sum += h[i].filter_weight_sum;
-        }
-    }
-    dev.release();
-    return rc;
+    /* merge_pixel.xyz[i] += xyz[i] (film.rs:127-130) */
+    return render_to_host(npix, {{out_pixels, sizeof(ftn_pixel), true}},
+                          [&](void* const* d) { return ftn_render_device(cs, cam, film, sd, id, tr, opt, d[0], nullptr, st); });
 }
 
 }  /* extern "C" */

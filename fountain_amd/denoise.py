@@ -14,17 +14,11 @@ import ctypes as C
 import numpy as np
 
 from . import _abi as A
-from .api import FountainError
+from ._nontwin import checked_lib
 
 
 def _lib(be):
-    if be.is_oracle:
-        raise FountainError(A.FTN_ERR_UNSUPPORTED, "the denoiser has no oracle twin: the reference has no denoiser")
-    have = be.lib.ftn_denoise_abi_version()
-    if have != A.FTN_DENOISE_ABI_VERSION:
-        raise FountainError(A.FTN_ERR_INTERNAL, "%s reports denoise ABI version %d, this binding was written for %d: rebuild the library"
-                            % (be.path, have, A.FTN_DENOISE_ABI_VERSION))
-    return be.lib
+    return checked_lib(be, "the denoiser has no oracle twin: the reference has no denoiser", "denoise", "ftn_denoise_abi_version", A.FTN_DENOISE_ABI_VERSION)
 
 
 def default_params(be, **fields):

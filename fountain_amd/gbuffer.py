@@ -13,7 +13,8 @@ import ctypes as C
 import numpy as np
 
 from . import _abi as A
-from .api import Film, FountainError
+from ._nontwin import call_args, check_tensor as _check_tensor, checked_lib
+from .api import Film
 
 # resolved channels: name -> slice of the 12 floats ftn_gbuffer_resolve writes per pixel
 CHANNELS = {"albedo": slice(0, 3), "normal": slice(3, 6), "position": slice(6, 9), "depth": slice(9, 10),
@@ -21,21 +22,8 @@ CHANNELS = {"albedo": slice(0, 3), "normal": slice(3, 6), "position": slice(6, 9
 
 
 def _lib(be):
-    if be.is_oracle:
-        raise FountainError(A.FTN_ERR_UNSUPPORTED, "the G-buffer pass has no oracle twin: the reference renders no G-buffer")
-    have = be.lib.ftn_gbuffer_abi_version()
-    if have != A.FTN_GBUFFER_ABI_VERSION:
-        raise FountainError(A.FTN_ERR_INTERNAL, "%s reports G-buffer ABI version %d, this binding was written for %d: rebuild the library"
-                            % (be.path, have, A.FTN_GBUFFER_ABI_VERSION))
-    return be.lib
-
-
-def _call_args(cam, film, sampler, tiles, pipeline, device):
-    tr = A.ftn_tile_range()
-    tr.first, tr.stride, tr.count = tiles if tiles is not None else (0, 1, 0)
-    opt = A.ftn_render_options()
-    opt.pipeline, opt.device = pipeline, device
-    return [C.byref(cam.desc), C.byref(film.desc), C.byref(sampler.desc), C.byref(tr), C.byref(opt)], (tr, opt)
+    return checked_lib(be, "the G-buffer pass has no oracle twin: the reference renders no G-buffer", "G-buffer", "ftn_gbuffer_abi_version",
+                       A.FTN_GBUFFER_ABI_VERSION)
 
 
 def resolve(be, raw):
@@ -59,16 +47,10 @@ def render_gbuffer(be, builder, cam, res, sampler, tiles=None, crop=(0.0, 0.0, 1
         raw = np.zeros((film.height, film.width, 12), np.float32)
     if raw.shape != (film.height, film.width, 12) or raw.dtype != np.float32 or not raw.flags.c_contiguous:
         raise ValueError("raw must be a C-contiguous float32 array of shape %r" % ((film.height, film.width, 12),))
-    args, keep = _call_args(cam, film, sampler, tiles, pipeline, device)
+    args, keep = call_args(cam, film, None, sampler, tiles, pipeline, device)
     st = A.ftn_stats()
     be.check(lib.ftn_render_gbuffer(scene.handle, *args, raw.ctypes.data_as(C.c_void_p), C.byref(st)))
     return resolve(be, raw), raw, st.as_dict()
-
-
-def _check_tensor(t, shape):
-    import torch
-    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() or tuple(t.shape) != tuple(shape):
-        raise ValueError("expected a contiguous float32 CUDA tensor of shape %r" % (tuple(shape),))
 
 
 def render_gbuffer_torch(scene, cam, film, sampler, out, tiles=None, pipeline=A.FTN_PIPELINE_AUTO):
@@ -77,7 +59,7 @@ def render_gbuffer_torch(scene, cam, film, sampler, out, tiles=None, pipeline=A.
     be = scene.be
     lib = _lib(be)
     _check_tensor(out, (film.height, film.width, 12))
-    args, keep = _call_args(cam, film, sampler, tiles, pipeline, out.device.index)
+    args, keep = call_args(cam, film, None, sampler, tiles, pipeline, out.device.index)
     st = A.ftn_stats()
     stream = torch.cuda.current_stream(out.device).cuda_stream
     be.check(lib.ftn_render_gbuffer_device(scene.handle, *args, C.c_void_p(out.data_ptr()), C.c_void_p(stream), C.byref(st)))

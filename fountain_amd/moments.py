@@ -13,27 +13,15 @@ import ctypes as C
 import numpy as np
 
 from . import _abi as A
-from .api import Film, FountainError
+from ._nontwin import call_args as _call_args, check_tensor as _check_tensor, checked_lib
+from .api import Film
 
 CHANNELS = ("r", "g", "b", "Y")          # the 4 floats per pixel of the moments and of the resolved variance
 
 
 def _lib(be):
-    if be.is_oracle:
-        raise FountainError(A.FTN_ERR_UNSUPPORTED, "the moments pass has no oracle twin: the reference keeps no second moments")
-    have = be.lib.ftn_moments_abi_version()
-    if have != A.FTN_MOMENTS_ABI_VERSION:
-        raise FountainError(A.FTN_ERR_INTERNAL, "%s reports moments ABI version %d, this binding was written for %d: rebuild the library"
-                            % (be.path, have, A.FTN_MOMENTS_ABI_VERSION))
-    return be.lib
-
-
-def _call_args(cam, film, integrator, sampler, tiles, pipeline, device, count_traffic=False):
-    tr = A.ftn_tile_range()
-    tr.first, tr.stride, tr.count = tiles if tiles is not None else (0, 1, 0)
-    opt = A.ftn_render_options()
-    opt.pipeline, opt.device, opt.count_traffic = pipeline, device, int(count_traffic)
-    return [C.byref(cam.desc), C.byref(film.desc), C.byref(sampler.desc), C.byref(integrator.desc), C.byref(tr), C.byref(opt)], (tr, opt)
+    return checked_lib(be, "the moments pass has no oracle twin: the reference keeps no second moments", "moments", "ftn_moments_abi_version",
+                       A.FTN_MOMENTS_ABI_VERSION)
 
 
 def _check_array(a, shape, what):
@@ -71,12 +59,6 @@ def render_moments(be, builder, cam, res, integrator, sampler, tiles=None, crop=
     st = A.ftn_stats()
     be.check(lib.ftn_render_moments(scene.handle, *args, film.pixels.ctypes.data_as(C.c_void_p), moments.ctypes.data_as(C.c_void_p), C.byref(st)))
     return resolve(be, film.pixels, moments), film, moments, st.as_dict()
-
-
-def _check_tensor(t, shape):
-    import torch
-    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() or tuple(t.shape) != tuple(shape):
-        raise ValueError("expected a contiguous float32 CUDA tensor of shape %r" % (tuple(shape),))
 
 
 def render_moments_torch(scene, cam, film, integrator, sampler, pixels, moments, tiles=None, pipeline=A.FTN_PIPELINE_AUTO):
