@@ -163,6 +163,15 @@ FTN_DENOISE_MAX_LEVELS = 10
 FTN_DENOISE_ABI_VERSION = 1  # include/fountain_hip_denoise.h (an extension with a version of its own)
 
 
+class ftn_denoise_guided_params(C.Structure):
+    """include/fountain_hip_denoise_guided.h: parameters of the variance-guided a-trous denoiser (ftn_denoise_guided_params_default)."""
+    _fields_ = [("levels", C.c_int32), ("flags", c_u32), ("sigma_variance", c_f), ("sigma_normal", c_f), ("sigma_plane", c_f),
+                ("albedo_eps", c_f), ("rel_eps", c_f), ("reserved", c_u32)]
+
+
+FTN_DENOISE_GUIDED_ABI_VERSION = 1  # include/fountain_hip_denoise_guided.h (an extension with a version of its own)
+
+
 class ftn_moment_pixel(C.Structure):
     """include/fountain_hip_moments.h: per-pixel sums of the squares of the samples' radiance (box filter weight 1)."""
     _fields_ = [("sq", c_f * 3), ("sq_y", c_f)]
@@ -194,7 +203,7 @@ SIZES = {
     "ftn_sphere": 288, "ftn_material": 48, "ftn_light": 160, "ftn_envmap": 16, "ftn_camera_desc": 296,
     "ftn_film_desc": 32, "ftn_sampler_desc": 24, "ftn_integrator_desc": 16, "ftn_tile_range": 16,
     "ftn_render_options": 16, "ftn_stats": 152, "ftn_scene_memory": 96, "ftn_texture": 48, "ftn_image": 24, "ftn_material_textures": 32,
-    "ftn_gbuffer_pixel": 48, "ftn_denoise_params": 32, "ftn_moment_pixel": 16, "ftn_adaptive_params": 16, "ftn_adaptive_info": 24,
+    "ftn_gbuffer_pixel": 48, "ftn_denoise_params": 32, "ftn_denoise_guided_params": 32, "ftn_moment_pixel": 16, "ftn_adaptive_params": 16, "ftn_adaptive_info": 24,
 }
 
 # Every function the header declares (name -> None); used by the symbol-export test.
@@ -224,6 +233,13 @@ GBUFFER_FUNCTIONS = [
 DENOISE_FUNCTIONS = [
     "ftn_denoise_params_default", "ftn_denoise", "ftn_denoise_workspace_size", "ftn_denoise_device", "ftn_denoise_cpu",
     "ftn_denoise_abi_version",
+]
+
+# Every function the extension header include/fountain_hip_denoise_guided.h declares (kept apart from the lists above: the reference has
+# no denoiser, so these have no orc_* twin either).
+DENOISE_GUIDED_FUNCTIONS = [
+    "ftn_denoise_guided_params_default", "ftn_denoise_guided", "ftn_denoise_guided_workspace_size", "ftn_denoise_guided_device",
+    "ftn_denoise_guided_cpu", "ftn_denoise_guided_abi_version",
 ]
 
 # Every function the extension header include/fountain_hip_moments.h declares (kept apart from the lists above: the reference keeps no

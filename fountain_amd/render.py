@@ -13,6 +13,9 @@ depth repeated in R, G and B); it needs the default sampler and one GPU.  --deno
 parameters); the image itself is written unchanged.  It has the same needs as --gbuffer.  --variance renders the image together with
 the second moments of its camera samples (fountain_amd/moments.py), the same pixels bit for bit, and writes <name>_variance.exr: the
 estimated variance of each pixel's mean in R, G and B (+inf where a pixel has fewer than 2 samples).  It has the same needs as --gbuffer.
+--denoise-guided renders the image with those moments (as --variance does) and the G-buffer, and writes <name>_denoised_guided.exr:
+the image filtered by the variance-guided a-trous denoiser (fountain_amd/denoise.py, default parameters); the image itself is written
+unchanged.  It has the needs of --gbuffer and at least 2 samples per pixel, and combines with --variance and --denoise.
 --adaptive T renders with per-tile adaptive sampling (fountain_amd/adaptive.py): every 16x16 tile gets --min-samples samples (default
 8, at most the samples per pixel), then twice as many, and so on up to --samples, until the estimated relative standard error of
 each of its pixels' mean luminance is at most T.  It writes <name>_spp.exr beside the image: each pixel's final sample count in R, G and B.  --variance works with it (from
@@ -40,6 +43,8 @@ def main(argv=None):
     ap.add_argument("--gbuffer", action="store_true", help="also write the first-hit albedo / normal / position / depth buffers as <name>_<buffer>.exr")
     ap.add_argument("--denoise", action="store_true", help="also write <name>_denoised.exr, the image denoised with the first-hit G-buffer of its camera samples")
     ap.add_argument("--variance", action="store_true", help="also write <name>_variance.exr, the estimated variance of each pixel's mean (r, g, b)")
+    ap.add_argument("--denoise-guided", action="store_true",
+                    help="also write <name>_denoised_guided.exr, the image denoised with its G-buffer and the variance of each pixel's mean")
     ap.add_argument("--adaptive", type=float, default=None, metavar="T",
                     help="per-tile adaptive sampling up to --samples: stop a tile once its pixels' relative standard error is at most T; also writes <name>_spp.exr")
     ap.add_argument("--min-samples", type=int, default=None, help="with --adaptive: the samples every tile gets first (default 8)")
@@ -49,7 +54,7 @@ def main(argv=None):
         return 2
     if opts.adaptive is not None:
         for flag, on in (("--exact-stream", opts.exact_stream), ("--gbuffer", opts.gbuffer), ("--denoise", opts.denoise),
-                         ("more than one GPU (--gpus)", opts.gpus is not None and opts.gpus > 1)):
+                         ("--denoise-guided", opts.denoise_guided), ("more than one GPU (--gpus)", opts.gpus is not None and opts.gpus > 1)):
             if on:
                 print("error: --adaptive does not work with %s: it renders each tile at its own sample count on one GPU with the default sampler"
                       " (a G-buffer and the denoiser would have to follow those counts)" % flag, file=sys.stderr)
@@ -57,7 +62,7 @@ def main(argv=None):
         if not opts.adaptive >= 0.0 or opts.adaptive == float("inf"):
             print("error: --adaptive takes a finite threshold >= 0", file=sys.stderr)
             return 2
-    for flag, on in (("--gbuffer", opts.gbuffer), ("--denoise", opts.denoise), ("--variance", opts.variance)):
+    for flag, on in (("--gbuffer", opts.gbuffer), ("--denoise", opts.denoise), ("--variance", opts.variance), ("--denoise-guided", opts.denoise_guided)):
         if on and opts.exact_stream:
             print("error: %s needs the default sampler: with --exact-stream a sample's camera ray depends on everything its tile drew before it" % flag, file=sys.stderr)
             return 2
@@ -71,8 +76,9 @@ def main(argv=None):
         # started plainly: start the N ranks as a child process (before anything here has touched HIP) and hand back its exit code
         return spawn_ranks(opts.gpus, sys.argv[1:] if argv is None else list(argv), module="fountain_amd.render")
     world, rank = (env_world[0], env_world[1]) if env_world is not None else (1, 0)
-    if (opts.gbuffer or opts.denoise or opts.variance or opts.adaptive is not None) and world > 1:
-        flag = "--gbuffer" if opts.gbuffer else "--denoise" if opts.denoise else "--variance" if opts.variance else "--adaptive"
+    if (opts.gbuffer or opts.denoise or opts.variance or opts.denoise_guided or opts.adaptive is not None) and world > 1:
+        flag = "--gbuffer" if opts.gbuffer else "--denoise" if opts.denoise else "--variance" if opts.variance else \
+            "--denoise-guided" if opts.denoise_guided else "--adaptive"
         print("error: %s renders on one GPU, not under a launcher of %d ranks" % (flag, world), file=sys.stderr)
         return 2
     if opts.gpus is not None and opts.gpus != world:
@@ -87,6 +93,10 @@ def main(argv=None):
     if ".exr" not in filename:
         raise SystemExit("output must be an .exr file (render.rs:53)")
     sampler = parsed.sampler(opts.samples, indexed=not opts.exact_stream)
+    if opts.denoise_guided and sampler.desc.samples_per_pixel < 2:
+        print("error: --denoise-guided needs at least 2 samples per pixel: a pixel's variance is unknown below that (here %d)"
+              % sampler.desc.samples_per_pixel, file=sys.stderr)
+        return 2
     if opts.adaptive is not None:
         # min_samples: --min-samples, or 8 (the library's default) but at most the samples per pixel
         n_max = sampler.desc.samples_per_pixel
@@ -132,7 +142,7 @@ def main(argv=None):
         print("adaptive: %d rounds, %d of %d tiles at %d samples, %.2f samples per pixel" % (
             ainfo["rounds"], ainfo["tiles_at_max"], ainfo["tiles"], sampler.desc.samples_per_pixel,
             ainfo["pixel_samples"] / max(1, counts.size)), file=sys.stderr)
-    elif opts.variance:
+    elif opts.variance or opts.denoise_guided:
         # the beauty of ftn_render, bit for bit, with the moments of its samples beside it
         from .moments import render_moments
         variance, _, _, st = render_moments(be, None, parsed.camera, None, integrator.radiance, sampler, scene=scene, film=film, device=opts.gpu)
@@ -143,10 +153,12 @@ def main(argv=None):
     print("Completed rendering in %.3f s (%.1f Mrays/s%s)" % (dt, rays / dt / 1e6, " on rank 0 of %d" % world if world > 1 else ""), file=sys.stderr)
     img, (w, h) = film.into_spectrum_buffer()
     write_exr(filename, img, be)
-    if opts.gbuffer or opts.denoise:
+    if opts.gbuffer or opts.denoise or opts.denoise_guided:
         gb = write_gbuffer(be, scene, parsed.camera, film, sampler, filename, opts.gpu, write=opts.gbuffer)
         if opts.denoise:
             write_denoised(be, img, gb, filename, opts.gpu)
+        if opts.denoise_guided:
+            write_denoised_guided(be, img, gb, variance, filename, opts.gpu)
     if opts.adaptive is not None:
         import numpy as np
         path = spp_path(filename)
@@ -169,6 +181,12 @@ def denoised_path(filename):
     """out.exr -> out_denoised.exr"""
     base = filename[:-4] if filename.endswith(".exr") else filename
     return "%s_denoised.exr" % base
+
+
+def denoised_guided_path(filename):
+    """out.exr -> out_denoised_guided.exr"""
+    base = filename[:-4] if filename.endswith(".exr") else filename
+    return "%s_denoised_guided.exr" % base
 
 
 def variance_path(filename):
@@ -206,6 +224,17 @@ def write_denoised(be, img, gb12, filename, device):
     path = denoised_path(filename)
     write_exr(path, out, be)
     print("denoised: %s (%.1f ms)" % (path, (time.time() - t0) * 1e3), file=sys.stderr)
+
+
+def write_denoised_guided(be, img, gb12, var4, filename, device):
+    """The resolved image denoised with its G-buffer and the variance of each pixel's mean (default parameters), written as
+    <name>_denoised_guided.exr."""
+    from .denoise import denoise_guided
+    t0 = time.time()
+    out = denoise_guided(be, img, gb12, var4, device=device)
+    path = denoised_guided_path(filename)
+    write_exr(path, out, be)
+    print("denoised (variance-guided): %s (%.1f ms)" % (path, (time.time() - t0) * 1e3), file=sys.stderr)
 
 
 if __name__ == "__main__":
