@@ -2,7 +2,7 @@
 """Headline benchmark: Mrays/s (primary + secondary) of the wavefront path tracer on the 10M-triangle synthetic scene
 (BASELINE.json config 5: 2309 baked copies of rounded_cube, 4096x4096 film, PathIntegrator(5, 1.0), env-map light).
 
-  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   N > 1: either under a launcher (python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P
   bench.py --gpus N ...) or plainly -- then bench.py starts its N ranks itself as a child process (fountain_amd/launch.py) and relays
   rank 0's line.  A launcher whose WORLD_SIZE differs from --gpus is an error (exit code 2).
@@ -12,7 +12,14 @@ with the film's 65,536 tiles interleaved over the N ranks -- so every GPU traces
 (weak scaling of the 4096-spp job; `value` is the whole-job rate).  The batch is sized for the part's memory: one wavefront of 268 M
 paths keeps ~88 GB of path state in HBM and is 18 % faster per ray than sixteen wavefronts of 17 M.  The film stays resident in HBM (a torch tensor handed to
 ftn_render_device by pointer); at the end of the timed region the ranks' films are summed by ONE RCCL reduce.
-Prints one JSON line on rank 0."""
+Prints one JSON line on rank 0.
+
+A plain run does only what the headline figure needs: it builds the scene, warms up, times the K steps, writes --dump-outputs and prints
+the line (metric, value, unit, ms_per_step, config, ranks).  With --warmup 0 the first timed step is also the library's first call and
+carries its one-off allocations.  --full adds everything that takes runs of its own, outside the timed region and without touching
+it: one untimed counting step before the warm-up (the `algorithmic` bytes of the roofline block), the `roofline` block itself, and
+the `cpu_baseline` leg (the CPU oracle builds its own BVH over the 10 M triangles and renders a tile sample for 10-20 s).  value,
+ms_per_step and the dumped arrays are the same with and without it."""
 import argparse
 import ctypes as C
 import json
@@ -34,14 +41,16 @@ def main():
     ap.add_argument("--copies", type=int, default=int(os.environ.get("FTN_BENCH_COPIES", "2309")), help="mesh copies (2309 = 10,002,588 triangles)")
     ap.add_argument("--res", type=int, default=int(os.environ.get("FTN_BENCH_RES", "4096")))
     ap.add_argument("--spp-per-gpu", type=int, default=int(os.environ.get("FTN_BENCH_SPP_PER_GPU", "16")), help="samples per pixel one GPU renders per step")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline figure does not need: the untimed counting step and the roofline block, and the CPU baseline "
+                                                        "(about half a minute on top of a plain run)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
     ap.add_argument("--cpu-tiles", type=int, default=int(os.environ.get("FTN_BENCH_CPU_TILES", "96")))
     ap.add_argument("--dist-backend", default=os.environ.get("FTN_BENCH_DIST_BACKEND", "nccl"), choices=["nccl", "gloo"],
                     help="nccl = RCCL over xGMI, one GPU per rank (the measured configuration); gloo = rehearsal of the N-rank path (see --share-gpu)")
     ap.add_argument("--share-gpu", action="store_true", help="rehearsal on a one-GPU box: every rank renders on GPU 0, films merged over gloo on the host (implies --dist-backend gloo: RCCL refuses two ranks on one device)")
     ap.add_argument("--scaling", default=os.environ.get("FTN_BENCH_SCALING", "weak"), choices=["weak", "strong"],
                     help="weak (default): every GPU renders --spp-per-gpu samples of its tiles per step, the job's work grows with N; strong: a step is --spp-per-gpu samples of the WHOLE film whatever N is, each GPU renders its 1/N of the tiles")
-    ap.add_argument("--no-count-step", action="store_true", help="skip the untimed counting step (tools/make_traffic_json.py: every dispatch of the run then belongs to the timed steps)")
+    ap.add_argument("--no-count-step", action="store_true", help="with --full: skip the untimed counting step (the roofline block then has no `algorithmic` part)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last one handed back (the film, a fixed seeded sample of it when large, and the "
                          "step's ray counters) as DIR/<name>.npy, so that two builds can be compared output for output")
@@ -123,11 +132,13 @@ def main():
             dist.barrier()
         torch.cuda.synchronize(dev)
 
-    # one counted step: algorithmic bytes of the dominant kernel (nodes / triangles per ray are data dependent: SURVEY 8(d)).
+    # --full only, one counted step: algorithmic bytes of the dominant kernel (nodes / triangles per ray are data dependent: SURVEY 8(d)).
     # count_traffic = 2: tally exactly the rays each kernel traces in production (MIS rays toward the environment light only need
     # hit / miss and go through the any-hit kernel: ftn_stats.mis_rays_any_hit)
-    cst = step(0, count=2) if not args.no_count_step else None
-    dev_film.zero_()
+    cst = None
+    if args.full and not args.no_count_step:
+        cst = step(0, count=2)
+        dev_film.zero_()
     for i in range(args.warmup):
         step(i)
     def merge():
@@ -190,9 +201,10 @@ def main():
             # min / max over the ranks: device time of one step (HIP events inside the library), wall time of the K steps, and the single film
             # reduce at the end of the timed region (as each rank saw it: it includes waiting for the slowest rank)
             "ranks": {k: {"min": round(v["min"], 3), "max": round(v["max"], 3)} for k, v in per_rank.items()},
-            "roofline": roofline(args, cst, tot, n_steps, spp_per_step),
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full:
+            out["roofline"] = roofline(args, cst, tot, n_steps, spp_per_step)
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(desc, cam, film, args.cpu_tiles, n_tiles)
         print(json.dumps(out), flush=True)
     if use_dist:

@@ -1,9 +1,12 @@
 """bench.py's one JSON line: the fields the driver's contract names are present, typed and mutually consistent -- checked on the line of
-the last profiled run (profiles/r03/bench.json, written by `python bench.py --steps 10 --warmup 2` on the GPU box) and on the helper
+the last profiled run (profiles/r03/bench.json, the line of what is now `python bench.py --full --steps 10 --warmup 2`: a plain run leaves the
+roofline and cpu_baseline blocks out) and on the helper
 functions the line is built from.  CPU only; the line itself is produced on a GPU (tests/test_multigpu_gloo.py runs bench.py end to end
 there)."""
 import json
 import os
+import subprocess
+import sys
 
 import pytest
 
@@ -115,3 +118,47 @@ def test_dump_outputs(tmp_path):
         assert np.array_equal(runs[0][k], runs[1][k]), k
     assert np.array_equal(runs[0]["film_pixels"], big.numpy().reshape(-1, 4)[idx.astype(np.int64)])
     assert not runs[0]["last_step_counts"].any()
+
+
+SMALL = ["--gpus", "1", "--copies", "8", "--res", "256", "--spp-per-gpu", "2", "--steps", "2", "--warmup", "1"]
+HEADLINE = ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step")
+
+
+def _bench(args, timeout=600):
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args, capture_output=True, text=True, timeout=timeout, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, r.stdout                      # stdout carries the result line alone
+    return json.loads(lines[0])
+
+
+def test_full_is_an_option_of_every_run():
+    """--full is off by default and parses beside the other options (no GPU: --launch-check stops before any rendering)"""
+    env = dict(os.environ, OMP_NUM_THREADS="1", HIP_VISIBLE_DEVICES="", CUDA_VISIBLE_DEVICES="")
+    for extra in ([], ["--full"]):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--launch-check"] + extra, env=env, capture_output=True, text=True, timeout=300, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-2000:]
+        assert json.loads(r.stdout.strip().splitlines()[-1])["n_gpus"] == 1
+
+
+@pytest.mark.gpu
+def test_plain_run_is_lean_and_full_run_adds_the_rest(tmp_path):
+    """a plain run prints the headline fields without the blocks that take runs of their own; --full adds the roofline block (with the
+    counting step's `algorithmic` part) and the CPU baseline, and changes neither the meaning of the headline fields nor one bit of
+    what --dump-outputs writes"""
+    import numpy as np
+    plain = _bench(SMALL + ["--dump-outputs", str(tmp_path / "plain")])
+    full = _bench(SMALL + ["--full", "--dump-outputs", str(tmp_path / "full")])
+    for out in (plain, full):
+        assert all(k in out for k in HEADLINE) and out["value"] > 0 and out["ms_per_step"] > 0
+        assert abs(out["config"]["rays_per_step"] / (out["ms_per_step"] * 1e-3) / 1e6 - out["value"]) / out["value"] < 1e-2
+    assert "roofline" not in plain and "cpu_baseline" not in plain
+    assert "algorithmic" in full["roofline"] and full["roofline"]["launches_per_step"] > 0
+    assert full["cpu_baseline"]["kind"] == "port" and full["cpu_baseline"]["value"] > 0
+    for k in HEADLINE:
+        if k not in ("value", "ms_per_step"):
+            assert plain[k] == full[k], k
+    assert plain["config"]["rays_per_step"] == full["config"]["rays_per_step"]
+    for name in ("film_pixels.npy", "film_pixel_index.npy", "last_step_counts.npy"):
+        a, b = np.load(tmp_path / "plain" / name), np.load(tmp_path / "full" / name)
+        assert a.dtype == b.dtype and a.shape == b.shape and np.array_equal(a.view(np.uint8), b.view(np.uint8)), name

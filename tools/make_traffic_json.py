@@ -2,15 +2,15 @@
 
 Run ON THE GPU BOX (from the repository root):
     python tools/make_traffic_json.py profiles/r03 [--spp-per-gpu 16]
-It runs `bench.py --steps 1 --warmup 0 --no-cpu-baseline` once per counter group under
+It runs a plain `bench.py --steps 1 --warmup 0` (no --full: neither counting step nor CPU baseline) once per counter group under
 `rocprofv3 --pmc <counters> --kernel-trace --output-format csv` (separate passes: the TCC block has four slots and FETCH_SIZE /
 WRITE_SIZE do not fit together, MI355X_MICROARCH.md "rocprofv3 PMC slots"), sums every counter per kernel group and per timed step,
 and stores the sums with a hash of the kernel sources.  bench.py reports the figures only while that hash matches the sources it runs.
 
 Byte accounting (checked in profiles/r02/fetch_size_calibration.md): on gfx950 FETCH_SIZE (KiB) x 1024 x 2 == TCC_EA0_RDREQ_128B x 128 B for
 these gather kernels as well (the reads leave L2 as 128-byte requests and FETCH_SIZE tallies them at 64 B) -- the microarchitecture
-guide's x2 correction; WRITE_SIZE (KiB) is taken as is.  The passes run bench.py with --no-count-step, so that every dispatch of the run belongs to the one timed step (the
-counting builds of the traversal kernels are kept apart by name anyway)."""
+guide's x2 correction; WRITE_SIZE (KiB) is taken as is.  A plain run of bench.py has no counting step, so every dispatch of the run belongs to the one timed step (the
+counting builds of the traversal kernels, which a --full run launches, are kept apart by name anyway)."""
 import collections
 import csv
 import glob
@@ -71,7 +71,7 @@ def main():
         d = os.path.join(scratch, name)
         subprocess.run(["rm", "-rf", d])
         cmd = ["rocprofv3", "--pmc"] + ctrs + ["--kernel-trace", "--output-format", "csv", "-d", d, "-o", "p", "--", sys.executable, os.path.join(ROOT, "bench.py"),
-               "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--no-count-step"] + extra
+               "--steps", "1", "--warmup", "0"] + extra
         r = subprocess.run(cmd, cwd="/tmp", env=env, capture_output=True, text=True, timeout=900)
         if r.returncode != 0:
             print("pass %s failed (rc %d): %s" % (name, r.returncode, r.stderr[-500:]), file=sys.stderr)
@@ -125,8 +125,8 @@ def main():
                            "write_bytes_per_step": c.get("WRITE_SIZE", 0.0) * 1024.0,
                            "l2_hit_rate": c.get("TCC_HIT_sum", 0.0) / max(c.get("TCC_HIT_sum", 0.0) + c.get("TCC_MISS_sum", 0.0), 1.0),
                            "valu_wave_instructions": c.get("SQ_INSTS_VALU", 0.0), "gpu_cycles": c.get("GRBM_GUI_ACTIVE", 0.0) / 8.0, "counters": dict(c)} for k, c in sorted(per_kernel.items())},
-           "method": "rocprofv3 --pmc (one counter group per pass: " + "; ".join("+".join(c) for _, c in PASSES) + ") --kernel-trace over `python bench.py --steps 1 --warmup 0 "
-                     "--no-cpu-baseline --no-count-step`; production kernel instantiations only (the bench's counting step runs other instantiations); HBM-side bytes = FETCH_SIZE KiB x 1024 x 2 + "
+           "method": "rocprofv3 --pmc (one counter group per pass: " + "; ".join("+".join(c) for _, c in PASSES) + ") --kernel-trace over a plain `python bench.py --steps 1 --warmup 0` "
+                     "(no counting step); production kernel instantiations only; HBM-side bytes = FETCH_SIZE KiB x 1024 x 2 + "
                      "WRITE_SIZE KiB x 1024 (gfx950: 128-byte read requests are tallied at 64 B; cross-checked against TCC_EA0_RDREQ_128B x 128 B in the same file)"}
     json.dump(out, open(os.path.join(out_dir, "traffic.json"), "w"), indent=1)
     print(json.dumps({k: (v if not isinstance(v, dict) else "...") for k, v in out.items()}))
