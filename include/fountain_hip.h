@@ -465,6 +465,18 @@ int ftn_test_math(int which, const float* x, const float* y, size_t n, float* ou
  * {u, v, dudx, dvdx, dudy, dvdy} (HOST memory) -> rgb_out[3n] (a float texture repeats its value).                              */
 int ftn_test_mipmap_level(uint32_t width, uint32_t height, const float* texels, uint32_t level, uint32_t* level_w, uint32_t* level_h, float* rgb_out);
 int ftn_test_texture_eval(const ftn_scene* scene, int32_t texture, const float* uv_diffs6, size_t n, float* rgb_out);
+/* BSDF hook: Material::compute_scattering_functions, Bsdf::f, Bsdf::pdf and Bsdf::sample_f ON THE DEVICE for n synthetic hits on
+ * material `material` of the scene (constant parameters only: a textured material is refused).  rows_in (HOST memory), 17 floats per
+ * row: geometric normal ng[3], shading normal ns[3], shading dpdu[3], world-space wo[3], wi[3], sample u[2].  rows_out, 16 floats per
+ * row: [0] 1 = the material gave a BSDF, 0 = refused (specular glass with allow_multiple_lobes; the rest of the row is 0);
+ * [1] lobes matching `flags` (BxDFType bits, reflection/mod.rs:14-22); [2..4] Bsdf::f(wo, wi, flags); [5] Bsdf::pdf(wo, wi, flags);
+ * [6] 1 = Bsdf::sample_f(wo, u, flags) returned a sample, then [7..9] its f, [10..12] its world-space wi, [13] its pdf,
+ * [14] its sampled type; [15] 0.  specialised = 1 builds the BSDF through the material-type-specialised path of the shade kernels,
+ * 0 through the generic one: the rows must not differ.                                                                          */
+#define FTN_TEST_BSDF_IN 17
+#define FTN_TEST_BSDF_OUT 16
+int ftn_test_bsdf(const ftn_scene* scene, int32_t material, uint32_t flags, int allow_multiple_lobes, int specialised,
+                  const float* rows_in, size_t n, float* rows_out);
 
 /* ------------------------------------------------------------------ misc */
 const char* ftn_last_error(void);

@@ -374,6 +374,32 @@ int orc_test_texture_eval(const orc_scene* s, int32_t texture, const float* in6,
     }
     return FTN_OK;
 }
+// ---- BSDFs (orc_reflection.hpp): the twin of ftn_test_bsdf (fountain_hip.h has the row layouts); `specialised` has no meaning here
+int orc_test_bsdf(const orc_scene* s, int32_t material, uint32_t flags, int allow_multiple_lobes, int /*specialised*/, const float* in17, size_t n, float* out16) {
+    if (!s || !in17 || !out16) return fail(FTN_ERR_INVALID_ARGUMENT, "null argument");
+    if (material < 0 || (size_t)material >= s->data.materials.size()) return fail(FTN_ERR_INVALID_ARGUMENT, "material index out of range");
+    if (flags > 31u) return fail(FTN_ERR_INVALID_ARGUMENT, "flags hold bits outside BxDFType");
+    if (!s->data.mtex.empty()) { const ftn_material_textures& mt = s->data.mtex[material];
+        if ((mt.a & mt.b & mt.s0 & mt.s1 & mt.s2) >= 0) return fail(FTN_ERR_UNSUPPORTED, "orc_test_bsdf takes materials with constant parameters only"); }
+    const ftn_material& m = s->data.materials[material];
+    for (size_t i = 0; i < n; i++) {
+        const float* r = in17 + 17 * i; float* o = out16 + 16 * i;
+        for (int k = 0; k < 16; k++) o[k] = 0.0f;
+        SurfaceInteraction si;
+        si.hit.n = Vec3(r[0], r[1], r[2]); si.shading_n = Vec3(r[3], r[4], r[5]); si.shading_geom.dpdu = Vec3(r[6], r[7], r[8]);
+        const Vec3 wo(r[9], r[10], r[11]), wi(r[12], r[13], r[14]); const Vec2 u(r[15], r[16]);
+        si.wo = wo;
+        Bsdf bsdf;
+        if (compute_scattering_functions(m, si, allow_multiple_lobes != 0, &bsdf) != MAT_OK) continue;
+        const Spectrum f = bsdf.f(wo, wi, (uint8_t)flags);
+        o[0] = 1.0f; o[1] = (float)bsdf.num_components((uint8_t)flags); o[2] = f[0]; o[3] = f[1]; o[4] = f[2]; o[5] = bsdf.pdf(wo, wi, (uint8_t)flags);
+        ScatterSample sc;
+        if (bsdf.sample_f(wo, u, (uint8_t)flags, &sc)) {
+            o[6] = 1.0f; o[7] = sc.f[0]; o[8] = sc.f[1]; o[9] = sc.f[2]; o[10] = sc.wi.x; o[11] = sc.wi.y; o[12] = sc.wi.z; o[13] = sc.pdf; o[14] = (float)sc.sampled_type;
+        }
+    }
+    return FTN_OK;
+}
 // MIPMap::lookup_trilinear_width on an image built by MIPMap::new (custom = 0) or new_custom (custom = 1): rows of {s, t, width}
 void orc_kat_mipmap_lookup(uint32_t w, uint32_t h, const float* texels, int wrap, int custom, const float* st_width3, size_t n, float* out3) {
     MIPMap m;

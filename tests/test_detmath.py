@@ -30,6 +30,43 @@ def test_accuracy_vs_correct_rounding(orc_det, which):
     assert ulp.max() <= 1.0, name
 
 
+def _neighbours(centre, k=1000):
+    """the k binary32 values on either side of `centre` (and the one nearest to it)"""
+    c = f32(centre)
+    i = int(np.array(c, f32).view(np.uint32))
+    return np.arange(i - k, i + k + 1, dtype=np.uint32).view(f32)
+
+
+def call_site_inputs(which):
+    """What TrowbridgeReitzDistribution::sample_wh (microfacet.rs:169-174), the one caller of tan and atan on the hot path, feeds them:
+    tan(2 pi u + pi/2) over [pi/2, 5pi/2] with its poles at the odd multiples of pi/2, atan of that times alpha_y / alpha_x (up to
+    +-inf), then sin and cos of phi [+ pi] (bounded here by 7pi/2)."""
+    rng = np.random.default_rng(100 + which)
+    if which == 2:
+        return np.concatenate([rng.uniform(np.pi / 2, 5 * np.pi / 2, 20000).astype(f32)] + [_neighbours(k * np.pi / 2) for k in (1, 3, 5)])
+    if which == 4:
+        mag = np.exp(rng.uniform(np.log(50.0), np.log(3.4e38), 10000)).astype(f32)
+        return np.concatenate([mag, -mag, f32([50.0, -50.0, 3.4e38, -3.4e38, np.inf, -np.inf])])
+    return np.concatenate([rng.uniform(0.0, 7 * np.pi / 2, 20000).astype(f32), f32([0.0, 7 * np.pi / 2])] + [_neighbours(k * np.pi / 2, 50) for k in range(1, 8)])
+
+
+@pytest.mark.parametrize("which", [0, 1, 2, 4])
+def test_accuracy_at_the_call_site_ranges(orc_det, which):
+    """the thresholds of test_accuracy_vs_correct_rounding on the ranges the BSDF code reaches.  Next to a pole of tan the binary64 value of a
+    binary32 argument is well conditioned (the argument is at least 2^-25 relative away from the pole), so the 1 ulp bound holds there too."""
+    name, ref, _ = FUNCS[which]
+    x = call_site_inputs(which)
+    got = host_eval(orc_det, which, x, x)
+    exact = ref(x.astype(np.float64))
+    want = exact.astype(f32)
+    assert np.all(np.isfinite(got)), name
+    assert (got != want).mean() <= 1e-3, name
+    ulp = np.abs(got.astype(np.float64) - exact) / np.spacing(np.abs(want)).astype(np.float64)
+    assert ulp.max() <= 1.0, (name, x[np.argmax(ulp)], ulp.max())
+    if which == 4:
+        assert got[-2] == f32(np.pi / 2) and got[-1] == f32(-np.pi / 2)
+
+
 def test_powf_correctly_rounded(orc_det):
     """f32::powf for a positive base (imageio/mod.rs:173 is its only caller on this path): exp(y ln x) in binary64, one rounding"""
     rng = np.random.default_rng(13)
@@ -89,3 +126,14 @@ def test_device_math_is_bit_identical_to_host(gpu, orc_det):
         h.argtypes = [C.c_float]
         ref = np.array([h(float(a)) for a in v], dtype=f32)
         assert np.array_equal(out.view(np.uint32), ref.view(np.uint32)), name
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("which", [0, 1, 2, 4])
+def test_device_math_is_bit_identical_to_host_at_the_call_site_ranges(gpu, orc_det, which):
+    """sin / cos / tan / atan on what tr_sample_wh feeds them (call_site_inputs): the same bits on the MI355X and on the host"""
+    x = np.ascontiguousarray(call_site_inputs(which))
+    out = np.empty(len(x), f32)
+    gpu.check(gpu.lib.ftn_test_math(which, x.ctypes.data_as(C.c_void_p), x.ctypes.data_as(C.c_void_p), C.c_size_t(len(x)), out.ctypes.data_as(C.c_void_p)))
+    ref = host_eval(orc_det, which, x, x)
+    assert np.array_equal(out.view(np.uint32), ref.view(np.uint32)), FUNCS[which][0]
