@@ -2,10 +2,8 @@
  * ftn_adaptive.hip -- the device side of per-tile adaptive sampling (include/fountain_hip_adaptive.h): the per-round decision and the
  * per-pixel sample counts.  The rounds themselves are wavefront_moments calls over the active tiles.
  *
- * Like the moments pass, this is part of the wavefront pipeline's translation unit: this file includes ftn_moments.hip (which includes
- * ftn_gbuffer.hip and ftn_wavefront.hip) and the Makefile compiles it in its place.
+ * A unit of its own: of the pipeline it needs only RenderParams, DTile and MomentAcc.
  */
-#include "ftn_moments.hip"
 #include "ftn_adaptive.h"
 
 namespace ftn {

@@ -1,12 +1,14 @@
 /*
  * ftn_gbuffer.hip -- the first-hit G-buffer pass (include/fountain_hip_gbuffer.h) on the wavefront pipeline.
  *
- * The pass is part of the wavefront pipeline's translation unit: this file includes ftn_wavefront.hip and the Makefile compiles it in
- * its place, so that the driver shares that file's internals -- the scene's WavefrontState and its buffers, wf_reserve, trace4_prepare,
- * launch_trace, k_wf_reset, k_wf_generate -- without exporting them, and the sources of the beauty's kernels stay as they are.
+ * A unit of its own: the driver uses the wavefront pipeline through ftn_wf_internal.h (the scene's WavefrontState and its buffers, the
+ * pass plan, the traversal launches, the launchers of k_wf_reset and k_wf_generate), the kernels share ftn_wf_common.h with the beauty's.
  */
-#include "ftn_wavefront.hip"
+#include "ftn_wf_internal.h"
+#include "ftn_texture.h"
 #include "ftn_gbuffer.h"
+#include <algorithm>
+#include <cstring>
 
 namespace ftn {
 
@@ -96,18 +98,14 @@ __global__ void k_gb_reset(WfBuffers W, uint32_t out_ctr) {
     W.counters[CTR(out_ctr)] = 0;
 }
 
-/* one sample's record into every pixel of its box-filter footprint (wf_film_add): the own pixel in registers, others into the spill sums */
-__device__ inline void gb_film_add(const GbParams& G, const FilmCtxW& F, V2 p_film, float4 r0, float4 r1, float4 r2, int own_x, int own_y, float* acc, uint32_t* spill, uint32_t* bc_writes) {
-    const float pdx = p_film.x - 0.5f, pdy = p_film.y - 0.5f;
-    int p0x = f2i_sat(ceilf(pdx - F.radius[0])), p0y = f2i_sat(ceilf(pdy - F.radius[1]));
-    int p1x = f2i_sat(floorf(pdx + F.radius[0])) + 1, p1y = f2i_sat(floorf(pdy + F.radius[1])) + 1;
-    p0x = max(p0x, F.tpb[0]); p0y = max(p0y, F.tpb[1]); p1x = min(p1x, F.tpb[2]); p1y = min(p1y, F.tpb[3]);
+/* one sample's record into every pixel of its box-filter footprint (film_add): the own pixel in registers, others into the spill sums */
+__device__ inline void gb_film_add(const GbParams& G, const FilmCtx& F, V2 p_film, float4 r0, float4 r1, float4 r2, int own_x, int own_y, float* acc, uint32_t* spill, uint32_t* bc_writes) {
+    const FilmFootprint fp = film_footprint(F, p_film);
     const bool hit = r0.w != 0.0f;
     const float v[10] = {r0.x, r0.y, r0.z, r1.x, r1.y, r1.z, r2.x, r2.y, r2.z, r1.w};
     int touched = 0;
-    const size_t width = (size_t)(F.crop[2] - F.crop[0]);
-    for (int y = p0y; y < p1y; y++)
-        for (int x = p0x; x < p1x; x++) {
+    for (int y = fp.y0; y < fp.y1; y++)
+        for (int x = fp.x0; x < fp.x1; x++) {
             touched++;
             if (x == own_x && y == own_y) {
                 if (hit) {
@@ -118,7 +116,7 @@ __device__ inline void gb_film_add(const GbParams& G, const FilmCtxW& F, V2 p_fi
                 acc[11] += 1.0f;
                 continue;
             }
-            const size_t i = (size_t)(y - F.crop[1]) * width + (size_t)(x - F.crop[0]);
+            const size_t i = film_idx(F, x, y);
             float* a = reinterpret_cast<float*>(G.spillA + i);
             float* b = reinterpret_cast<float*>(G.spillB + i);
             float* c = reinterpret_cast<float*>(G.spillC + i);
@@ -141,28 +139,11 @@ __global__ void __launch_bounds__(256) k_gb_accumulate(RenderParams P, WfBuffers
     __shared__ float4 s_rec[256 * GB_ACC_CHUNK * 3];
     const uint32_t slot = blockIdx.x * 256u + threadIdx.x;
     uint32_t spill = 0, bc = 0;
-    bool valid = false, in_crop = false; int px = 0, py = 0; size_t ai = 0;
-    FilmCtxW F; float acc[12];
+    const FilmSlot fs = film_slot(P, W.n_slots, slot);
+    const bool valid = fs.valid, in_crop = fs.in_crop; const int px = fs.px, py = fs.py; const size_t ai = fs.ai;
+    float acc[12];
 #pragma unroll
-    for (int k = 0; k < 12; k++) acc[k] = 0.0f;
-    if (slot < W.n_slots) {
-        const DTile tile = P.tiles[slot >> 8];
-        px = tile.x0 + (int)(slot & 15u); py = tile.y0 + (int)((slot >> 4) & 15u);
-        if (px < tile.x1 && py < tile.y1) {
-            valid = true;
-            for (int i = 0; i < 4; i++) F.crop[i] = P.crop[i];
-            F.sb[0] = tile.x0; F.sb[1] = tile.y0; F.sb[2] = tile.x1; F.sb[3] = tile.y1; F.radius[0] = P.radius[0]; F.radius[1] = P.radius[1];
-            const int p0x = f2i_sat(ceilf((float)tile.x0 - 0.5f - P.radius[0])), p0y = f2i_sat(ceilf((float)tile.y0 - 0.5f - P.radius[1]));
-            const int p1x = f2i_sat(ceilf((float)tile.x1 - 0.5f + P.radius[0] + 1.0f)), p1y = f2i_sat(ceilf((float)tile.y1 - 0.5f - P.radius[1] + 1.0f));
-            F.tpb[0] = max(p0x, P.crop[0]); F.tpb[1] = max(p0y, P.crop[1]); F.tpb[2] = min(p1x, P.crop[2]); F.tpb[3] = min(p1y, P.crop[3]);
-            in_crop = px >= P.crop[0] && px < P.crop[2] && py >= P.crop[1] && py < P.crop[3];
-            ai = in_crop ? ((size_t)(py - P.crop[1]) * (size_t)(P.crop[2] - P.crop[0]) + (size_t)(px - P.crop[0])) : 0;
-            if (in_crop) {
-#pragma unroll
-                for (int k = 0; k < 12; k++) acc[k] = G.out[12 * ai + k];
-            }
-        }
-    }
+    for (int k = 0; k < 12; k++) acc[k] = in_crop ? G.out[12 * ai + k] : 0.0f;
     const size_t block_first = (size_t)blockIdx.x * 256u * W.samples;          /* first path of this workgroup's 256 slots */
     for (uint32_t s0 = 0; s0 < W.samples; s0 += GB_ACC_CHUNK) {
         const uint32_t n = W.samples - s0 < GB_ACC_CHUNK ? W.samples - s0 : GB_ACC_CHUNK;
@@ -178,7 +159,7 @@ __global__ void __launch_bounds__(256) k_gb_accumulate(RenderParams P, WfBuffers
                 /* the sample's film position: the first two draws of its stream, exactly as k_wf_generate made them */
                 Rng crng; crng.seed(indexed_key(P.seed, px, py, W.first_sample + s0 + k));
                 const V2 j = crng.next2();
-                gb_film_add(G, F, V2((float)px + j.x, (float)py + j.y), r[0], r[1], r[2], in_crop ? px : (-2147483647), py, acc, &spill, &bc);
+                gb_film_add(G, fs.F, V2((float)px + j.x, (float)py + j.y), r[0], r[1], r[2], in_crop ? px : FTN_OWN_NONE, py, acc, &spill, &bc);
             }
         }
         __syncthreads();
@@ -220,17 +201,11 @@ int wavefront_gbuffer(WavefrontState** state, const RenderParams& P, const std::
     const uint32_t n_slots = (uint32_t)tiles.size() * 256u;
     const uint32_t total_samples = P.last_sample - P.first_sample;
     if (n_slots == 0 || total_samples == 0) return FTN_OK;
-    if (tiles.size() > ((size_t)1 << 20)) { g_wf_err = "more than 2^20 tiles (2^28 pixel slots) in one call: render the film in several tile ranges"; return FTN_ERR_UNSUPPORTED; }
-    /* passes of up to 256 Mi samples, halved while the buffers do not fit (wavefront_render) */
-    uint32_t S = (uint32_t)std::max<size_t>(1, ((size_t)std::min<uint32_t>(knob("FTN_WF_PATHS_M", 256), 256u) << 20) / n_slots);
-    S = std::min(S, total_samples);
-    int rc = wf_reserve(st, (size_t)S * n_slots);
-    while (rc == FTN_ERR_OUT_OF_MEMORY && S > 1) {
-        wf_free(st); (void)hipGetLastError();
-        S = (S + 1) / 2;
-        rc = wf_reserve(st, (size_t)S * n_slots);
-    }
-    if (rc) { wf_free(st); return rc; }
+    /* the beauty's passes (wf_plan_passes) without the direct-lighting buffers: only camera rays are traced */
+    WfPassPlan plan;
+    int rc = wf_plan_passes(st, P, tiles.size() * 256u, total_samples, false, &plan);
+    if (rc) return rc;
+    const uint32_t S = plan.samples;
     if ((rc = trace4_prepare(st, P.S))) return rc;
     WfBuffers W = st->W;
     W.br = nullptr; W.pd = nullptr; W.pd_md = 0; W.pd_occ = 0; W.drain_sig = nullptr; W.drain_seq = 0; W.serial = 0; W.rng_replay = 0; W.mis_any = 0;
@@ -247,8 +222,8 @@ int wavefront_gbuffer(WavefrontState** state, const RenderParams& P, const std::
     for (uint32_t s0 = 0; s0 < total_samples; s0 += S) {
         const uint32_t Sp = std::min(S, total_samples - s0);
         W.n_slots = n_slots; W.samples = Sp; W.n_paths = Sp * n_slots; W.first_sample = P.first_sample + s0; W.seg_cap = (uint32_t)st->cap_paths;
-        hipLaunchKernelGGL(k_wf_reset, dim3(1), dim3(64), 0, stream, W, 0, 0, P.stats);     /* counters, queue lengths of the camera rays, camera_samples */
-        hipLaunchKernelGGL(k_wf_generate, dim3((W.n_paths + 255) / 256), dim3(256), 0, stream, P, W, 0);
+        launch_wf_new_pass(W, P.stats, stream);
+        launch_wf_generate(P, W, 0, stream);
         const unsigned tg = std::min<unsigned>(trace_grid_max, (2 * W.n_paths + 255) / 256);
         uint32_t n_q = Sp * valid;
         for (uint32_t r = 0;; r++) {
@@ -271,7 +246,7 @@ int wavefront_gbuffer(WavefrontState** state, const RenderParams& P, const std::
             n_q = st->host_counters[CTR(c_out)];
             if (n_q == 0) break;
             if (r == GB_MAX_PASS_THROUGH) {
-                g_wf_err = "a camera ray passed through more than 4096 null-material surfaces: the G-buffer would be incomplete";
+                wf_set_error("a camera ray passed through more than 4096 null-material surfaces: the G-buffer would be incomplete");
                 return FTN_ERR_INTERNAL;
             }
         }

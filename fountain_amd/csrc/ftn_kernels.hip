@@ -16,7 +16,7 @@
  * The traversal stack lives in LDS, lane-interleaved ([level][lane], conflict-free for ds_write/read_b32); its depth is
  * the BVH's depth, so LDS per workgroup = depth * 256 * 4 bytes.
  */
-#include "ftn_kernels.h"
+#include "ftn_film.h"
 #include "ftn_texture.h"
 
 namespace ftn {
@@ -169,8 +169,6 @@ __device__ inline Rgb path_li(Tracer<COUNT>& T, DRay ray, const DRayDiff& rd, Rn
  * specular_reflect / specular_transmit (integrator/mod.rs:39-178).  The recursion is unrolled for chains with at most one specular
  * branch per vertex (mirror, or no specular lobe at all); a BSDF with both specular lobes (specular glass) reports FTN_ERR_UNSUPPORTED. */
 #define FTN_DL_MAX 8
-#define FTN_OWN_SERIAL (-2147483647 - 1)   /* film_add: single-writer tile walk */
-#define FTN_OWN_NONE (-2147483647)         /* film_add: lane owns no crop pixel */
 template <bool COUNT, bool TEX>
 __device__ inline Rgb direct_li(Tracer<COUNT>& T, DRay ray, DRayDiff rd, Rng& rng, uint32_t max_depth, bool whitted, int* err) {
     const DScene& S = T.S;
@@ -255,48 +253,6 @@ __device__ inline Rgb direct_li(Tracer<COUNT>& T, DRay ray, DRayDiff rd, Rng& rn
     return li;
 }
 
-/* ------------------------------------------------------------------ Film::add_sample_to_tile: film.rs:136-172 (box filter: every table entry is 1.0) */
-struct FilmCtx {
-    int crop[4]; int tpb[4];     /* FilmTile::pixel_bounds of this tile (get_film_tile, film.rs:95-113) */
-    int sb[4];                   /* the tile's sample bounds */
-    float radius[2];
-    float4 *A, *B, *C;
-};
-__device__ inline size_t film_idx(const FilmCtx& F, int x, int y) { return (size_t)(y - F.crop[1]) * (size_t)(F.crop[2] - F.crop[0]) + (size_t)(x - F.crop[0]); }
-__device__ inline void atomic_add4(float4* p, Rgb c, float w) {
-    float* f = reinterpret_cast<float*>(p);
-    atomicAdd(f + 0, c.r); atomicAdd(f + 1, c.g); atomicAdd(f + 2, c.b); atomicAdd(f + 3, w);
-}
-/* Returns the number of pixels touched. own_(x,y): the pixel whose register accumulator `acc` belongs to the caller
- * (indexed mode); serial mode passes own_x = INT_MIN and writes in-tile pixels straight to A (single writer). */
-__device__ inline int film_add(const FilmCtx& F, V2 p_film, Rgb L, float sample_weight, int own_x, int own_y, float4* acc, uint32_t* bc_writes) {
-    float pdx = p_film.x - 0.5f, pdy = p_film.y - 0.5f;
-    int p0x = f2i_sat(ceilf(pdx - F.radius[0])), p0y = f2i_sat(ceilf(pdy - F.radius[1]));
-    int p1x = f2i_sat(floorf(pdx + F.radius[0])) + 1, p1y = f2i_sat(floorf(pdy + F.radius[1])) + 1;
-    p0x = max(p0x, F.tpb[0]); p0y = max(p0y, F.tpb[1]); p1x = min(p1x, F.tpb[2]); p1y = min(p1y, F.tpb[3]);
-    const Rgb contrib = L * sample_weight * 1.0f;
-    int touched = 0;
-    for (int y = p0y; y < p1y; y++)
-        for (int x = p0x; x < p1x; x++) {
-            touched++;
-            if (x == own_x && y == own_y) { acc->x += contrib.r; acc->y += contrib.g; acc->z += contrib.b; acc->w += 1.0f; continue; }
-            const bool in_tile = x >= F.sb[0] && x < F.sb[2] && y >= F.sb[1] && y < F.sb[3];
-            const size_t i = film_idx(F, x, y);
-            if (in_tile && own_x == FTN_OWN_SERIAL) { float4 v = F.A[i]; v.x += contrib.r; v.y += contrib.g; v.z += contrib.b; v.w += 1.0f; F.A[i] = v; }
-            else { atomic_add4(in_tile ? &F.B[i] : &F.C[i], contrib, 1.0f); (*bc_writes)++; }
-        }
-    return touched;
-}
-__device__ inline void make_film_ctx(const RenderParams& P, const DTile& t, FilmCtx* F) {
-    for (int i = 0; i < 4; i++) F->crop[i] = P.crop[i];
-    F->sb[0] = t.x0; F->sb[1] = t.y0; F->sb[2] = t.x1; F->sb[3] = t.y1;
-    F->radius[0] = P.radius[0]; F->radius[1] = P.radius[1];
-    int p0x = f2i_sat(ceilf((float)t.x0 - 0.5f - P.radius[0])), p0y = f2i_sat(ceilf((float)t.y0 - 0.5f - P.radius[1]));
-    int p1x = f2i_sat(ceilf((float)t.x1 - 0.5f + P.radius[0] + 1.0f)), p1y = f2i_sat(ceilf((float)t.y1 - 0.5f - P.radius[1] + 1.0f));   /* sic: -radius, film.rs:100 */
-    F->tpb[0] = max(p0x, P.crop[0]); F->tpb[1] = max(p0y, P.crop[1]); F->tpb[2] = min(p1x, P.crop[2]); F->tpb[3] = min(p1y, P.crop[3]);
-    F->A = P.accA; F->B = P.accB; F->C = P.accC;
-}
-
 /* ------------------------------------------------------------------ one camera sample: render_tile's inner loop body (mod.rs:244-274) */
 template <bool COUNT, bool TEX>
 __device__ inline void render_sample(const RenderParams& P, Tracer<COUNT>& T, const FilmCtx& F, Rng& rng, int px, int py, int own_x, int own_y,
@@ -311,7 +267,7 @@ __device__ inline void render_sample(const RenderParams& P, Tracer<COUNT>& T, co
     Rgb L = (P.integrator_kind != FTN_INTEGRATOR_PATH) ? direct_li<COUNT, TEX>(T, ray, rd, rng, P.max_depth, P.integrator_kind == FTN_INTEGRATOR_WHITTED, err)
                                                                   : path_li<COUNT, TEX>(T, ray, rd, rng, P.max_depth, P.rr_threshold, err);
     if (L.has_nans()) *err = FTN_ERR_NAN_RADIANCE;       /* check_radiance :285-287 */
-    int touched = film_add(F, p_film, L, 1.0f, own_x, own_y, acc, &T.lc.bc);
+    int touched = film_add(F, P.accA, P.accB, P.accC, p_film, L, own_x, own_y, acc, &T.lc.bc);
     T.lc.cam++;
     if (touched != 1) T.lc.spill++;
 }

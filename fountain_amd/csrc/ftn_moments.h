@@ -10,7 +10,7 @@ namespace ftn {
  * other pixels' samples from the same tile and from other tiles (zero unless the last call's DevStats::bc_writes said otherwise) */
 struct MomentAcc { float4 *own, *in_tile, *other_tile; };
 /* ftn_render's wavefront passes with the moments of every pass's samples beside them: P as ftn_render_device sets it up (P.accA/B/C
- * zeroed by the caller), the samples [P.first_sample, P.last_sample) in chunks that wavefront_render runs as one pass each.  Then
+ * zeroed by the caller), the samples [P.first_sample, P.last_sample) in wavefront_render's passes.  Then
  * launch_film_resolve (beauty) and launch_moments_merge (moments) finish the call. */
 int wavefront_moments(WavefrontState** state, const RenderParams& P, const std::vector<DTile>& tiles, bool count, bool count_production,
                       const MomentAcc& M, hipStream_t stream, WavefrontTimes* times);

@@ -1,34 +1,29 @@
 /*
  * ftn_moments.hip -- per-pixel second moments of the camera samples' radiance (include/fountain_hip_moments.h), beside the beauty.
  *
- * The pass is part of the wavefront pipeline's translation unit: this file includes ftn_gbuffer.hip (which includes ftn_wavefront.hip)
- * and the Makefile compiles it in its place, so that the driver shares the pipeline's internals -- WavefrontState and its per-path
- * radiance, wf_reserve, the pass size rules, FilmCtxW -- without exporting them, and the sources of the beauty's kernels stay as they are.
+ * A unit of its own: the driver is a wavefront_render call (ftn_wavefront.h) with a per-pass hook, and k_mo_accumulate shares the
+ * film context and the layout of a pass's buffers with the beauty's kernels through ftn_wf_common.h.
  */
-#include "ftn_gbuffer.hip"
+#include "ftn_wf_common.h"
 #include "ftn_moments.h"
+#include <algorithm>
 
 namespace ftn {
 
 /* ================================================================== second moments (include/fountain_hip_moments.h)
- * wavefront_render leaves the radiance of its last pass's samples in WfBuffers::rad (path id = slot * samples + s).  wavefront_moments
- * therefore calls it over chunks of the sample range that it runs as one pass each, and after each chunk k_mo_accumulate adds the
- * squares of those samples.  The beauty's accumulators are not cleared between chunks, so its kernels run exactly as in one ftn_render
- * call with passes of that size. */
+ * wavefront_render leaves the radiance of a pass's samples in WfBuffers::rad (path id = slot * samples + s) until the next pass
+ * overwrites it.  wavefront_moments hooks k_mo_accumulate behind every pass's k_wf_accumulate, on the same stream, to add the squares of
+ * those samples: the beauty's kernels run exactly as in ftn_render. */
 
-/* one sample's squares into every pixel of its box-filter footprint (wf_film_add's rule): the own pixel in registers, others into the
+/* one sample's squares into every pixel of its box-filter footprint (film_add's rule): the own pixel in registers, others into the
  * in-tile or other-tile sum by atomics */
-__device__ inline void mo_film_add(const MomentAcc& M, const FilmCtxW& F, V2 p_film, float4 q, int own_x, int own_y, float4* acc) {
-    const float pdx = p_film.x - 0.5f, pdy = p_film.y - 0.5f;
-    int p0x = f2i_sat(ceilf(pdx - F.radius[0])), p0y = f2i_sat(ceilf(pdy - F.radius[1]));
-    int p1x = f2i_sat(floorf(pdx + F.radius[0])) + 1, p1y = f2i_sat(floorf(pdy + F.radius[1])) + 1;
-    p0x = max(p0x, F.tpb[0]); p0y = max(p0y, F.tpb[1]); p1x = min(p1x, F.tpb[2]); p1y = min(p1y, F.tpb[3]);
-    const size_t width = (size_t)(F.crop[2] - F.crop[0]);
-    for (int y = p0y; y < p1y; y++)
-        for (int x = p0x; x < p1x; x++) {
+__device__ inline void mo_film_add(const MomentAcc& M, const FilmCtx& F, V2 p_film, float4 q, int own_x, int own_y, float4* acc) {
+    const FilmFootprint fp = film_footprint(F, p_film);
+    for (int y = fp.y0; y < fp.y1; y++)
+        for (int x = fp.x0; x < fp.x1; x++) {
             if (x == own_x && y == own_y) { acc->x += q.x; acc->y += q.y; acc->z += q.z; acc->w += q.w; continue; }
             const bool in_tile = x >= F.sb[0] && x < F.sb[2] && y >= F.sb[1] && y < F.sb[3];
-            float* f = reinterpret_cast<float*>((in_tile ? M.in_tile : M.other_tile) + ((size_t)(y - F.crop[1]) * width + (size_t)(x - F.crop[0])));
+            float* f = reinterpret_cast<float*>((in_tile ? M.in_tile : M.other_tile) + film_idx(F, x, y));
             atomicAdd(f + 0, q.x); atomicAdd(f + 1, q.y); atomicAdd(f + 2, q.z); atomicAdd(f + 3, q.w);
         }
 }
@@ -40,23 +35,10 @@ __device__ inline void mo_film_add(const MomentAcc& M, const FilmCtxW& F, V2 p_f
 __global__ void __launch_bounds__(256) k_mo_accumulate(RenderParams P, WfBuffers W, MomentAcc M) {
     __shared__ float4 s_rad[256 * MO_ACC_CHUNK];
     const uint32_t slot = blockIdx.x * 256u + threadIdx.x;
-    bool valid = false, in_crop = false; int px = 0, py = 0; size_t ai = 0;
-    FilmCtxW F; float4 acc = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    if (slot < W.n_slots) {
-        const DTile tile = P.tiles[slot >> 8];
-        px = tile.x0 + (int)(slot & 15u); py = tile.y0 + (int)((slot >> 4) & 15u);
-        if (px < tile.x1 && py < tile.y1) {
-            valid = true;
-            for (int i = 0; i < 4; i++) F.crop[i] = P.crop[i];
-            F.sb[0] = tile.x0; F.sb[1] = tile.y0; F.sb[2] = tile.x1; F.sb[3] = tile.y1; F.radius[0] = P.radius[0]; F.radius[1] = P.radius[1];
-            const int p0x = f2i_sat(ceilf((float)tile.x0 - 0.5f - P.radius[0])), p0y = f2i_sat(ceilf((float)tile.y0 - 0.5f - P.radius[1]));
-            const int p1x = f2i_sat(ceilf((float)tile.x1 - 0.5f + P.radius[0] + 1.0f)), p1y = f2i_sat(ceilf((float)tile.y1 - 0.5f - P.radius[1] + 1.0f));
-            F.tpb[0] = max(p0x, P.crop[0]); F.tpb[1] = max(p0y, P.crop[1]); F.tpb[2] = min(p1x, P.crop[2]); F.tpb[3] = min(p1y, P.crop[3]);
-            in_crop = px >= P.crop[0] && px < P.crop[2] && py >= P.crop[1] && py < P.crop[3];
-            ai = in_crop ? ((size_t)(py - P.crop[1]) * (size_t)(P.crop[2] - P.crop[0]) + (size_t)(px - P.crop[0])) : 0;
-            if (in_crop) acc = M.own[ai];
-        }
-    }
+    const FilmSlot fs = film_slot(P, W.n_slots, slot);
+    const bool valid = fs.valid, in_crop = fs.in_crop; const int px = fs.px, py = fs.py; const size_t ai = fs.ai;
+    float4 acc = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (in_crop) acc = M.own[ai];
     const size_t block_first = (size_t)blockIdx.x * 256u * W.samples;          /* first path of this workgroup's 256 slots */
     for (uint32_t s0 = 0; s0 < W.samples; s0 += MO_ACC_CHUNK) {
         const uint32_t n = W.samples - s0 < MO_ACC_CHUNK ? W.samples - s0 : MO_ACC_CHUNK;
@@ -75,7 +57,7 @@ __global__ void __launch_bounds__(256) k_mo_accumulate(RenderParams P, WfBuffers
                 /* the sample's film position: the first two draws of its stream, exactly as k_wf_generate made them */
                 Rng crng; crng.seed(indexed_key(P.seed, px, py, W.first_sample + s0 + k));
                 const V2 j = crng.next2();
-                mo_film_add(M, F, V2((float)px + j.x, (float)py + j.y), q, in_crop ? px : (-2147483647), py, &acc);
+                mo_film_add(M, fs.F, V2((float)px + j.x, (float)py + j.y), q, in_crop ? px : FTN_OWN_NONE, py, &acc);
             }
         }
         __syncthreads();
@@ -83,7 +65,7 @@ __global__ void __launch_bounds__(256) k_mo_accumulate(RenderParams P, WfBuffers
     if (valid && in_crop) M.own[ai] = acc;
 }
 
-/* after the last chunk: out += own + in-tile, then out += other-tile (the spill sums are only read when a sample left its own pixel) */
+/* after the last pass: out += own + in-tile, then out += other-tile (the spill sums are only read when a sample left its own pixel) */
 __global__ void __launch_bounds__(256) k_mo_merge(MomentAcc M, float4* __restrict__ out, size_t n, const DevStats* __restrict__ stats) {
     const bool spilled = stats->bc_writes != 0;
     for (size_t i = (size_t)blockIdx.x * 256u + threadIdx.x; i < n; i += (size_t)gridDim.x * 256u) {
@@ -108,61 +90,12 @@ void launch_moments_resolve(const float* pix, const float* m, size_t n, float* o
     hipLaunchKernelGGL(k_mo_resolve, dim3((unsigned)std::min<size_t>((n + 255) / 256, 4096)), dim3(256), 0, stream, pix, m, n, out4);
 }
 
+static void moments_pass(void* ctx, const RenderParams& P, const WfBuffers& W, hipStream_t stream) {
+    hipLaunchKernelGGL(k_mo_accumulate, dim3((W.n_slots + 255) / 256), dim3(256), 0, stream, P, W, *static_cast<const MomentAcc*>(ctx));
+}
 int wavefront_moments(WavefrontState** state, const RenderParams& P, const std::vector<DTile>& tiles, bool count, bool count_production,
                       const MomentAcc& M, hipStream_t stream, WavefrontTimes* times) {
-    knobs_begin();
-    { int rc0 = wf_state_init(state); if (rc0) return rc0; }
-    WavefrontState* st = *state;
-    const uint32_t n_slots = (uint32_t)tiles.size() * 256u;
-    const uint32_t total_samples = P.last_sample - P.first_sample;
-    if (n_slots == 0 || total_samples == 0) return FTN_OK;
-    if (tiles.size() > ((size_t)1 << 20)) { g_wf_err = "more than 2^20 tiles (2^28 pixel slots) in one call: render the film in several tile ranges"; return FTN_ERR_UNSUPPORTED; }
-    /* the chunk: the pass size wavefront_render picks (FTN_WF_PATHS_M, at most 2^28 paths, the direct-lighting / Whitted slot cap), and
-     * the wavefront reserved for it here, halved while it does not fit, so that wavefront_render finds it in place and runs one pass */
-    uint32_t S = (uint32_t)std::max<size_t>(1, ((size_t)std::min<uint32_t>(knob("FTN_WF_PATHS_M", 256), 256u) << 20) / n_slots);
-    S = std::min(S, total_samples);
-    const bool dl_mode = P.integrator_kind != FTN_INTEGRATOR_PATH, whitted = P.integrator_kind == FTN_INTEGRATOR_WHITTED;
-    uint32_t dl_levels = 0, dl_slots = 0;
-    if (dl_mode) {
-        if (whitted && P.S.n_lights > WF_WH_MAX_LIGHTS) { g_wf_err = "the wavefront pipeline runs WhittedIntegrator for up to 32 lights (one bit per light in a path's pending-light word)"; return FTN_ERR_UNSUPPORTED; }
-        dl_levels = std::max<uint32_t>(1u, std::min<uint32_t>(P.max_depth, WF_DL_MAX)); dl_slots = whitted ? std::max<uint32_t>(P.S.n_lights, 1u) : 1u;
-        const size_t cap = ((size_t)1 << 31) / std::max<uint32_t>(dl_slots, 2u) - 1u;
-        if ((size_t)n_slots > cap) { g_wf_err = "too many pixel slots for this many lights in one call: render the film in several tile ranges"; return FTN_ERR_UNSUPPORTED; }
-        S = (uint32_t)std::max<size_t>(1, std::min<size_t>(S, cap / n_slots));
-    }
-    auto reserve = [&](uint32_t samples) -> int {
-        int r = wf_reserve(st, (size_t)samples * n_slots);
-        if (!r && dl_mode) r = wf_reserve_dl(st, st->cap_paths, dl_levels, dl_slots, P.S.n_textures != 0);
-        return r;
-    };
-    int rc = reserve(S);
-    while (rc == FTN_ERR_OUT_OF_MEMORY && S > 1) {
-        wf_free(st); wf_free_dl(st); (void)hipGetLastError();
-        S = (S + 1) / 2;
-        rc = reserve(S);
-    }
-    if (rc) { wf_free(st); wf_free_dl(st); return rc; }
-    if (times) memset(times, 0, sizeof(*times));
-    for (uint32_t s0 = 0; s0 < total_samples; s0 += S) {
-        const uint32_t Sp = std::min(S, total_samples - s0);
-        RenderParams Pc = P;
-        Pc.first_sample = P.first_sample + s0; Pc.last_sample = Pc.first_sample + Sp;
-        WavefrontTimes t; memset(&t, 0, sizeof(t));
-        if ((rc = wavefront_render(state, Pc, tiles, count, stream, &t, count_production))) return rc;
-        if (st->cap_paths < (size_t)Sp * n_slots) {        /* it had to shrink the wavefront: WfBuffers::rad holds only its last pass */
-            g_wf_err = "the wavefront pipeline split a chunk of the moments pass into several passes";
-            return FTN_ERR_INTERNAL;
-        }
-        WfBuffers W = st->W;
-        W.n_slots = n_slots; W.samples = Sp; W.n_paths = Sp * n_slots; W.first_sample = Pc.first_sample;
-        hipLaunchKernelGGL(k_mo_accumulate, dim3((n_slots + 255) / 256), dim3(256), 0, stream, Pc, W, M);
-        if (times) {
-            times->trace_ms += t.trace_ms; times->trace_launches += t.trace_launches; times->any_ms += t.any_ms; times->any_launches += t.any_launches;
-            times->shade_ms += t.shade_ms; times->shade_launches += t.shade_launches; times->sort_ms += t.sort_ms; times->mis_any_rays += t.mis_any_rays;
-        }
-    }
-    WF_TRY(hipGetLastError());
-    return FTN_OK;
+    return wavefront_render(state, P, tiles, count, stream, times, count_production, moments_pass, const_cast<MomentAcc*>(&M));
 }
 
 }  // namespace ftn

@@ -24,11 +24,14 @@
  *
  * Small wavefronts (<= 32 Mi paths) run the any-hit trace of a bounce on a second stream beside the closest-hit trace.
  *
+ * Interfaces: ftn_wavefront.h is what the host library calls; ftn_wf_internal.h declares what the drivers of the other passes
+ * (ftn_gbuffer.hip) may use of this file's host side; ftn_wf_common.h holds the device-side pieces shared with their kernels.
+ *
  * All per-path arithmetic and the order of the RNG draws are those of the reference (and of the megakernel), so both
  * pipelines produce identical radiance.  Dominant kernel: k_wf_trace<false>; roofline = HBM (node + triangle fetches), in
  * practice the L2 -> L1 gather rate.
  */
-#include "ftn_wf_common.h"
+#include "ftn_wf_internal.h"
 #include "ftn_texture.h"
 #include <string>
 #include <cstdlib>
@@ -403,10 +406,6 @@ __global__ void __launch_bounds__(256) k_wf_classify(RenderParams P, WfBuffers W
 }
 
 /* ------------------------------------------------------------------ shade */
-__device__ inline DHit load_hit(const WfBuffers& W, uint32_t r) {
-    const float4 h = W.hit[r]; DHit o; o.t = h.x; o.b0 = h.y; o.b1 = h.z; o.b2 = h.w; o.prim = W.hit_prim[r]; return o;
-}
-
 #ifndef FTN_SHADE_MIN_WAVES
 #define FTN_SHADE_MIN_WAVES 1
 #endif
@@ -960,32 +959,6 @@ __global__ void k_wf_reset(WfBuffers W, int mode, int in_q, DevStats* stats) {
 }
 
 /* ------------------------------------------------------------------ accumulate: add_sample_to_tile in sample order */
-struct FilmCtxW { int crop[4]; int tpb[4]; int sb[4]; float radius[2]; };
-#define WF_OWN_SERIAL (-2147483647 - 1)
-__device__ inline void wf_film_add(const RenderParams& P, const FilmCtxW& F, V2 p_film, Rgb L, int own_x, int own_y, float4* acc, uint32_t* spill, uint32_t* bc_writes) {
-    float pdx = p_film.x - 0.5f, pdy = p_film.y - 0.5f;
-    int p0x = f2i_sat(ceilf(pdx - F.radius[0])), p0y = f2i_sat(ceilf(pdy - F.radius[1]));
-    int p1x = f2i_sat(floorf(pdx + F.radius[0])) + 1, p1y = f2i_sat(floorf(pdy + F.radius[1])) + 1;
-    p0x = max(p0x, F.tpb[0]); p0y = max(p0y, F.tpb[1]); p1x = min(p1x, F.tpb[2]); p1y = min(p1y, F.tpb[3]);
-    const Rgb contrib = L * 1.0f * 1.0f;                     /* radiance * sample_weight * filter_weight (box: 1.0) */
-    int touched = 0;
-    const size_t width = (size_t)(F.crop[2] - F.crop[0]);
-    for (int y = p0y; y < p1y; y++)
-        for (int x = p0x; x < p1x; x++) {
-            touched++;
-            if (x == own_x && y == own_y) { acc->x += contrib.r; acc->y += contrib.g; acc->z += contrib.b; acc->w += 1.0f; continue; }
-            const bool in_tile = x >= F.sb[0] && x < F.sb[2] && y >= F.sb[1] && y < F.sb[3];
-            if (in_tile && own_x == WF_OWN_SERIAL) {         /* tile-serial: the tile's one writer adds in-tile samples straight into A, in stream order (film_add, ftn_kernels.hip) */
-                float4* a = P.accA + ((size_t)(y - F.crop[1]) * width + (size_t)(x - F.crop[0]));
-                float4 v = *a; v.x += contrib.r; v.y += contrib.g; v.z += contrib.b; v.w += 1.0f; *a = v;
-                continue;
-            }
-            float* f = reinterpret_cast<float*>((in_tile ? P.accB : P.accC) + ((size_t)(y - F.crop[1]) * width + (size_t)(x - F.crop[0])));
-            atomicAdd(f + 0, contrib.r); atomicAdd(f + 1, contrib.g); atomicAdd(f + 2, contrib.b); atomicAdd(f + 3, 1.0f);
-            (*bc_writes)++;
-        }
-    if (touched != 1) (*spill)++;
-}
 /* One thread per pixel slot adds its samples in sample order (film.rs:127-130 is order dependent in the last bit).  The samples of a
  * slot are neighbours in memory (path id = slot * samples + s), so a thread reading its own run would touch one cache line per lane and
  * load; the workgroup stages 8 samples of its 256 slots through LDS with coalesced loads instead. */
@@ -994,23 +967,10 @@ __global__ void __launch_bounds__(256) k_wf_accumulate(RenderParams P, WfBuffers
     __shared__ float4 s_rad[256 * WF_ACC_CHUNK];
     const uint32_t slot = blockIdx.x * 256u + threadIdx.x;
     uint32_t spill = 0, bc = 0, cam = 0; int err = 0;
-    bool valid = false, in_crop = false; int px = 0, py = 0; size_t ai = 0;
-    FilmCtxW F; float4 acc = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    if (slot < W.n_slots) {
-        const DTile tile = P.tiles[slot >> 8];
-        px = tile.x0 + (int)(slot & 15u); py = tile.y0 + (int)((slot >> 4) & 15u);
-        if (px < tile.x1 && py < tile.y1) {
-            valid = true;
-            for (int i = 0; i < 4; i++) F.crop[i] = P.crop[i];
-            F.sb[0] = tile.x0; F.sb[1] = tile.y0; F.sb[2] = tile.x1; F.sb[3] = tile.y1; F.radius[0] = P.radius[0]; F.radius[1] = P.radius[1];
-            int p0x = f2i_sat(ceilf((float)tile.x0 - 0.5f - P.radius[0])), p0y = f2i_sat(ceilf((float)tile.y0 - 0.5f - P.radius[1]));
-            int p1x = f2i_sat(ceilf((float)tile.x1 - 0.5f + P.radius[0] + 1.0f)), p1y = f2i_sat(ceilf((float)tile.y1 - 0.5f - P.radius[1] + 1.0f));
-            F.tpb[0] = max(p0x, P.crop[0]); F.tpb[1] = max(p0y, P.crop[1]); F.tpb[2] = min(p1x, P.crop[2]); F.tpb[3] = min(p1y, P.crop[3]);
-            in_crop = px >= P.crop[0] && px < P.crop[2] && py >= P.crop[1] && py < P.crop[3];
-            ai = in_crop ? ((size_t)(py - P.crop[1]) * (size_t)(P.crop[2] - P.crop[0]) + (size_t)(px - P.crop[0])) : 0;
-            if (in_crop) acc = P.accA[ai];
-        }
-    }
+    const FilmSlot fs = film_slot(P, W.n_slots, slot);
+    const bool valid = fs.valid, in_crop = fs.in_crop; const int px = fs.px, py = fs.py; const size_t ai = fs.ai;
+    float4 acc = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (in_crop) acc = P.accA[ai];
     const size_t block_first = (size_t)blockIdx.x * 256u * W.samples;          /* first path of this workgroup's 256 slots */
     for (uint32_t s0 = 0; s0 < W.samples; s0 += WF_ACC_CHUNK) {
         const uint32_t n = W.samples - s0 < WF_ACC_CHUNK ? W.samples - s0 : WF_ACC_CHUNK;
@@ -1028,7 +988,7 @@ __global__ void __launch_bounds__(256) k_wf_accumulate(RenderParams P, WfBuffers
                 /* the sample's film position: the first two draws of its stream, exactly as k_wf_generate made them (sampler/mod.rs:41-48) */
                 Rng crng; crng.seed(indexed_key(P.seed, px, py, W.first_sample + s0 + k));
                 const V2 j = crng.next2();
-                wf_film_add(P, F, V2((float)px + j.x, (float)py + j.y), L, in_crop ? px : (-2147483647), py, &acc, &spill, &bc);
+                if (film_add(fs.F, P.accA, P.accB, P.accC, V2((float)px + j.x, (float)py + j.y), L, in_crop ? px : FTN_OWN_NONE, py, &acc, &bc) != 1) spill++;
                 cam++;
             }
         }
@@ -1063,14 +1023,9 @@ __global__ void __launch_bounds__(256) k_wf_serial_advance(RenderParams P, WfBuf
             const float4 l = W.rad[t]; const float2 pf = W.ser_pfilm[t];
             Rgb L(l.x, l.y, l.z);
             if (L.has_nans()) err = FTN_ERR_NAN_RADIANCE;
-            FilmCtxW F;
-            for (int i = 0; i < 4; i++) F.crop[i] = P.crop[i];
-            F.sb[0] = tile.x0; F.sb[1] = tile.y0; F.sb[2] = tile.x1; F.sb[3] = tile.y1; F.radius[0] = P.radius[0]; F.radius[1] = P.radius[1];
-            const int p0x = f2i_sat(ceilf((float)tile.x0 - 0.5f - P.radius[0])), p0y = f2i_sat(ceilf((float)tile.y0 - 0.5f - P.radius[1]));
-            const int p1x = f2i_sat(ceilf((float)tile.x1 - 0.5f + P.radius[0] + 1.0f)), p1y = f2i_sat(ceilf((float)tile.y1 - 0.5f - P.radius[1] + 1.0f));
-            F.tpb[0] = max(p0x, P.crop[0]); F.tpb[1] = max(p0y, P.crop[1]); F.tpb[2] = min(p1x, P.crop[2]); F.tpb[3] = min(p1y, P.crop[3]);
+            FilmCtx F; make_film_ctx(P, tile, &F);
             float4 none = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-            wf_film_add(P, F, V2(pf.x, pf.y), L, WF_OWN_SERIAL, 0, &none, &spill, &bc);
+            if (film_add(F, P.accA, P.accB, P.accC, V2(pf.x, pf.y), L, FTN_OWN_SERIAL, 0, &none, &bc) != 1) spill++;
             cam = 1;
             if (++cur.y == P.spp) { cur.y = 0; cur.x++; }
             start = cur.x < npix;
@@ -1112,6 +1067,7 @@ __global__ void __launch_bounds__(256) k_wf_serial_advance(RenderParams P, WfBuf
 /* ================================================================== host driver */
 static thread_local std::string g_wf_err;
 const char* wavefront_error() { return g_wf_err.c_str(); }
+void wf_set_error(const std::string& msg) { g_wf_err = msg; }
 
 /* ------------------------------------------------------------------ coherence sort of the secondary-ray queues
  * After a bounce the queues hold rays in shading order: origins of neighbouring entries are still close, directions are not.
@@ -1137,27 +1093,7 @@ __global__ void __launch_bounds__(256) k_wf_ray_keys(DScene S, WfBuffers W, cons
     keys[i] = (m << 3) | oct;
 }
 
-struct WavefrontState {
-    void* sort_tmp = nullptr; size_t sort_tmp_bytes = 0;
-    size_t cap_paths = 0;
-    void* mem[40]; int n_mem = 0;
-    WfBuffers W;
-    float4* br = nullptr; float4* pd = nullptr;          /* WfBuffers::br, WfBuffers::pd */
-    hipEvent_t ev[64]; int n_ev = 0;
-    hipStream_t side = nullptr; hipEvent_t ev_ready = nullptr, ev_side = nullptr;     /* the any-hit launches run beside the closest-hit ones */
-    uint32_t* drain_sig = nullptr; uint32_t drain_seq = 0;                              /* signal memory for hipStreamWaitValue32 (NULL: not supported) */
-    uint32_t* host_counters = nullptr;    /* pinned */
-    int n_cu = 256;
-    /* four-box traversal (ftn_trace4.hip): launch plan of the current call and the global spill areas behind the LDS stacks */
-    /* buffers of the direct-lighting / Whitted mode (grow-only): level terms, and shadow-ray records / results / queue sized for one ray per light */
-    void* dl_mem[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; size_t dl_paths = 0; uint32_t dl_levels = 0, dl_slots = 0; bool dl_tex = false;
-    Trace4Plan t4; bool t4_on = false, t8_on = false, q64_on = false;
-    void* ser_mem[4] = {nullptr, nullptr, nullptr, nullptr}; size_t ser_paths = 0; bool ser_tex = false; uint32_t* ser_host = nullptr;      /* tile-serial sampler on the queues: cursor, film position, retired flag, differentials */
-    void* t4_spill_c = nullptr; void* t4_spill_a = nullptr; size_t t4_spill_c_bytes = 0, t4_spill_a_bytes = 0;
-};
-#define WF_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { g_wf_err = std::string(#expr ": ") + hipGetErrorString(e_); return e_ == hipErrorOutOfMemory ? FTN_ERR_OUT_OF_MEMORY : FTN_ERR_NO_DEVICE; } } while (0)
-
-static void wf_free(WavefrontState* st) { for (int i = 0; i < st->n_mem; i++) (void)hipFree(st->mem[i]); st->n_mem = 0; st->cap_paths = 0; }
+void wf_free(WavefrontState* st) { for (int i = 0; i < st->n_mem; i++) (void)hipFree(st->mem[i]); st->n_mem = 0; st->cap_paths = 0; }
 void wavefront_destroy(WavefrontState* st) {
     if (!st) return;
     wf_free(st);
@@ -1180,7 +1116,7 @@ template <class T> static int wf_alloc(WavefrontState* st, T** p, size_t n) {
     st->mem[st->n_mem++] = (void*)*p;
     return FTN_OK;
 }
-static int wf_reserve(WavefrontState* st, size_t n) {
+int wf_reserve(WavefrontState* st, size_t n) {
     if (n <= st->cap_paths) return FTN_OK;
     wf_free(st);
     WfBuffers& W = st->W; int rc;
@@ -1197,8 +1133,8 @@ static int wf_reserve(WavefrontState* st, size_t n) {
  * once per launch of the bounce loop */
 #include <unordered_map>
 static thread_local std::unordered_map<std::string, std::pair<bool, uint32_t>> g_knobs;
-static void knobs_begin() { g_knobs.clear(); }
-static uint32_t knob(const char* name, uint32_t def) {
+void knobs_begin() { g_knobs.clear(); }
+uint32_t knob(const char* name, uint32_t def) {
     auto it = g_knobs.find(name);
     if (it == g_knobs.end()) { const char* v = getenv(name); it = g_knobs.emplace(name, std::make_pair(v != nullptr, v ? (uint32_t)atoi(v) : 0u)).first; }
     return it->second.first ? it->second.second : def;
@@ -1228,7 +1164,7 @@ static uint32_t g_probe_bounce = 0;
 #endif
 /* Sizes the four-box kernels' launches for this call (LDS levels -> occupancy, persistent grid) and makes sure their spill areas exist.
  * FTN_TRACE4=0 or a scene without four-box records: the two-record kernels run. */
-static int trace4_prepare(WavefrontState* st, const DScene& S) {
+int trace4_prepare(WavefrontState* st, const DScene& S) {
     st->t4_on = S.quad != nullptr && knob("FTN_TRACE4", 1) != 0;
     if (!st->t4_on) return FTN_OK;
     st->t4 = trace4_plan(S, st->n_cu, knob("FTN_T4_ENTRIES", 0), knob("FTN_T4_ENTRIES_ANY", 0), knob("FTN_T4_WG", 0), knob("FTN_T4_WG_ANY", 0), knob("FTN_T8_WG", 0), knob("FTN_T8_ENTRIES", 0));
@@ -1247,8 +1183,8 @@ static int trace4_prepare(WavefrontState* st, const DScene& S) {
 
 /* count: 0 = production kernels, 1 = counting build of the REFERENCE walk (node / primitive tallies equal the oracle's), 2 = counting
  * build of the production kernels (what bench.py's byte model uses).  n_queue: upper bound of the queue's length (sizes the grid). */
-static void launch_trace(WavefrontState* st, bool any, int count, bool spheres, unsigned grid, size_t lds, hipStream_t stream, const RenderParams& P, const WfBuffers& W,
-                         const uint32_t* queue, const uint32_t* count_ptr, uint32_t* head, uint32_t max_rays, bool camera_rays = false) {
+void launch_trace(WavefrontState* st, bool any, int count, bool spheres, unsigned grid, size_t lds, hipStream_t stream, const RenderParams& P, const WfBuffers& W,
+                  const uint32_t* queue, const uint32_t* count_ptr, uint32_t* head, uint32_t max_rays, bool camera_rays) {
     if (st->t4_on && count != 1) {     /* four-box records */
         const Trace4Plan& T = st->t4;
         const bool oct = any && st->t8_on, q64 = !any && st->q64_on;
@@ -1307,8 +1243,8 @@ static void launch_trace(WavefrontState* st, bool any, int count, bool spheres, 
 }
 
 /* buffers of k_wf_shade_dl for n paths, `levels` chain levels and `slots` shadow rays per path; tex: the differentials of textured scenes */
-static void wf_free_dl(WavefrontState* st) { for (void*& m : st->dl_mem) { if (m) (void)hipFree(m); m = nullptr; } st->dl_paths = 0; st->dl_levels = 0; st->dl_slots = 0; st->dl_tex = false; }
-static int wf_reserve_dl(WavefrontState* st, size_t n, uint32_t levels, uint32_t slots, bool tex) {
+void wf_free_dl(WavefrontState* st) { for (void*& m : st->dl_mem) { if (m) (void)hipFree(m); m = nullptr; } st->dl_paths = 0; st->dl_levels = 0; st->dl_slots = 0; st->dl_tex = false; }
+int wf_reserve_dl(WavefrontState* st, size_t n, uint32_t levels, uint32_t slots, bool tex) {
     if (n <= st->dl_paths && levels <= st->dl_levels && slots <= st->dl_slots && (!tex || st->dl_tex)) return FTN_OK;
     wf_free_dl(st);
     const size_t sl = std::max<uint32_t>(slots, 2u);                       /* (direct lighting: shadow results at [0, n), MIS-any results at [n, 2n)) */
@@ -1324,7 +1260,7 @@ static int wf_reserve_dl(WavefrontState* st, size_t n, uint32_t levels, uint32_t
     return FTN_OK;
 }
 
-static int wf_state_init(WavefrontState** state) {
+int wf_state_init(WavefrontState** state) {
     if (*state) return FTN_OK;
     *state = new WavefrontState();
     for (int i = 0; i < 64; i++) { WF_TRY(hipEventCreate(&(*state)->ev[i])); (*state)->n_ev = i + 1; }
@@ -1346,6 +1282,53 @@ static int wf_state_init(WavefrontState** state) {
     WF_TRY(hipHostMalloc((void**)&(*state)->host_counters, 16 * 32 * sizeof(uint32_t)));
     hipDeviceProp_t prop; int dev = 0; WF_TRY(hipGetDevice(&dev)); WF_TRY(hipGetDeviceProperties(&prop, dev));
     (*state)->n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+    return FTN_OK;
+}
+
+void launch_wf_new_pass(const WfBuffers& W, DevStats* stats, hipStream_t stream) { hipLaunchKernelGGL(k_wf_reset, dim3(1), dim3(64), 0, stream, W, 0, 0, stats); }
+void launch_wf_generate(const RenderParams& P, const WfBuffers& W, int write_state, hipStream_t stream) {
+    hipLaunchKernelGGL(k_wf_generate, dim3((W.n_paths + 255) / 256), dim3(256), 0, stream, P, W, write_state);
+}
+
+/* ------------------------------------------------------------------ the pass plan (ftn_wf_internal.h)
+ * Samples per pass: up to 256 Mi paths in flight (~88 GB of path state and queues out of 288 GB; the ids, queue indices and sort
+ * counts are 32-bit: 2^28 paths is also their limit).  Bigger wavefronts are faster per ray: the sorted queues hold more rays per
+ * cell of space (more lanes of a wave share node records) and every launch's drain -- about 0.5 ms whatever its size -- is paid
+ * once for more work.  Measured on the config-5 scene, per sample per pixel: 16 Mi paths 29.7 ms, 32 Mi 27.8, 64 Mi 26.7,
+ * 128 Mi 25.1, 256 Mi 24.5 (FTN_WF_PATHS_M, in Mi paths).  If the GPU has less to give, the pass is halved. */
+static int wf_refuse_slots(size_t n_slots) {
+    if (n_slots <= ((size_t)1 << 28)) return FTN_OK;
+    g_wf_err = "more than 2^20 tiles (2^28 pixel slots) in one call: render the film in several tile ranges";
+    return FTN_ERR_UNSUPPORTED;
+}
+int wf_plan_passes(WavefrontState* st, const RenderParams& P, size_t n_slots, uint32_t total_samples, bool dl, WfPassPlan* plan) {
+    int rc = wf_refuse_slots(n_slots);
+    if (rc) return rc;
+    uint32_t S = (uint32_t)std::max<size_t>(1, ((size_t)std::min<uint32_t>(knob("FTN_WF_PATHS_M", 256), 256u) << 20) / n_slots);
+    S = std::min(S, total_samples);
+    const bool whitted = P.integrator_kind == FTN_INTEGRATOR_WHITTED;
+    uint32_t dl_levels = 0, dl_slots = 0;
+    if (dl) {
+        if (whitted && P.S.n_lights > WF_WH_MAX_LIGHTS) { g_wf_err = "the wavefront pipeline runs WhittedIntegrator for up to 32 lights (one bit per light in a path's pending-light word)"; return FTN_ERR_UNSUPPORTED; }
+        dl_levels = std::max<uint32_t>(1u, std::min<uint32_t>(P.max_depth, WF_DL_MAX)); dl_slots = whitted ? std::max<uint32_t>(P.S.n_lights, 1u) : 1u;
+        /* a shadow ray's queue entry is its slot p + l * n_paths, and bit 31 marks MIS rays: slots * paths stays below 2^31 */
+        const size_t cap = ((size_t)1 << 31) / std::max<uint32_t>(dl_slots, 2u) - 1u;
+        S = (uint32_t)std::max<size_t>(1, std::min<size_t>(S, cap / n_slots));
+        if (n_slots > cap) { g_wf_err = "too many pixel slots for this many lights in one call: render the film in several tile ranges"; return FTN_ERR_UNSUPPORTED; }
+    }
+    auto reserve = [&](uint32_t samples) -> int {
+        int r = wf_reserve(st, (size_t)samples * n_slots);
+        if (!r && dl) r = wf_reserve_dl(st, st->cap_paths, dl_levels, dl_slots, P.S.n_textures != 0);
+        return r;
+    };
+    rc = reserve(S);
+    while (rc == FTN_ERR_OUT_OF_MEMORY && S > 1) {            /* the wavefront does not fit next to what else lives on this GPU: smaller passes */
+        wf_free(st); wf_free_dl(st); (void)hipGetLastError();
+        S = (S + 1) / 2;
+        rc = reserve(S);
+    }
+    if (rc) { wf_free(st); wf_free_dl(st); return rc; }
+    plan->samples = S; plan->dl_levels = dl_levels; plan->dl_slots = dl_slots;
     return FTN_OK;
 }
 
@@ -1521,7 +1504,7 @@ static int wavefront_render_serial(WavefrontState* st, const RenderParams& P, ui
 }
 
 int wavefront_render(WavefrontState** state, const RenderParams& P0, const std::vector<DTile>& tiles, bool count, hipStream_t stream, WavefrontTimes* times,
-                     bool count_production) {
+                     bool count_production, WfPassHook hook, void* hook_ctx) {
     knobs_begin();
     { int rc0 = wf_state_init(state); if (rc0) return rc0; }
     WavefrontState* st = *state;
@@ -1530,43 +1513,18 @@ int wavefront_render(WavefrontState** state, const RenderParams& P0, const std::
     if (n_slots == 0) return FTN_OK;
     const uint32_t total_samples = P.last_sample - P.first_sample;
     if (total_samples == 0) return FTN_OK;
-    if (tiles.size() > ((size_t)1 << 20)) { g_wf_err = "more than 2^20 tiles (2^28 pixel slots) in one call: render the film in several tile ranges"; return FTN_ERR_UNSUPPORTED; }
+    int rc;
     if (P.sampler_kind != FTN_SAMPLER_INDEXED) {
+        if ((rc = wf_refuse_slots(tiles.size() * 256u))) return rc;
         if (P.integrator_kind != FTN_INTEGRATOR_PATH) { g_wf_err = "the tile-serial sampler runs on the queues for PathIntegrator"; return FTN_ERR_UNSUPPORTED; }
         return wavefront_render_serial(st, P, (uint32_t)tiles.size(), count, count_production, stream, times);
     }
-    /* samples per pass: up to 256 Mi paths in flight (~88 GB of path state and queues out of 288 GB; the ids, queue indices and sort
-     * counts are 32-bit: 2^28 paths is also their limit).  Bigger wavefronts are faster per ray: the sorted queues hold more rays per
-     * cell of space (more lanes of a wave share node records) and every launch's drain -- about 0.5 ms whatever its size -- is paid
-     * once for more work.  Measured on the config-5 scene, per sample per pixel: 16 Mi paths 29.7 ms, 32 Mi 27.8, 64 Mi 26.7,
-     * 128 Mi 25.1, 256 Mi 24.5 (FTN_WF_PATHS_M, in Mi paths).  If the GPU has less to give, the pass is halved (below). */
-    uint32_t S = (uint32_t)std::max<size_t>(1, ((size_t)std::min<uint32_t>(knob("FTN_WF_PATHS_M", 256), 256u) << 20) / n_slots);
-    S = std::min(S, total_samples);
     const int count_mode = count ? (count_production ? 2 : 1) : 0;
     const bool dl_mode = P.integrator_kind != FTN_INTEGRATOR_PATH;          /* DirectLightingIntegrator / WhittedIntegrator: k_wf_shade_dl */
     const bool whitted = P.integrator_kind == FTN_INTEGRATOR_WHITTED;
-    const bool dl_tex = dl_mode && P.S.n_textures != 0;
-    uint32_t dl_levels = 0, dl_slots = 0;
-    if (dl_mode) {
-        if (whitted && P.S.n_lights > WF_WH_MAX_LIGHTS) { g_wf_err = "the wavefront pipeline runs WhittedIntegrator for up to 32 lights (one bit per light in a path's pending-light word)"; return FTN_ERR_UNSUPPORTED; }
-        dl_levels = std::max<uint32_t>(1u, std::min<uint32_t>(P.max_depth, WF_DL_MAX)); dl_slots = whitted ? std::max<uint32_t>(P.S.n_lights, 1u) : 1u;
-        /* a shadow ray's queue entry is its slot p + l * n_paths, and bit 31 marks MIS rays: slots * paths stays below 2^31 */
-        const size_t cap = ((size_t)1 << 31) / std::max<uint32_t>(dl_slots, 2u) - 1u;
-        S = (uint32_t)std::max<size_t>(1, std::min<size_t>(S, cap / n_slots));
-        if ((size_t)n_slots > cap) { g_wf_err = "too many pixel slots for this many lights in one call: render the film in several tile ranges"; return FTN_ERR_UNSUPPORTED; }
-    }
-    auto reserve = [&](uint32_t samples) -> int {
-        int r = wf_reserve(st, (size_t)samples * n_slots);
-        if (!r && dl_mode) r = wf_reserve_dl(st, st->cap_paths, dl_levels, dl_slots, dl_tex);
-        return r;
-    };
-    int rc = reserve(S);
-    while (rc == FTN_ERR_OUT_OF_MEMORY && S > 1) {            /* the wavefront does not fit next to what else lives on this GPU: smaller passes */
-        wf_free(st); wf_free_dl(st); (void)hipGetLastError();
-        S = (S + 1) / 2;
-        rc = reserve(S);
-    }
-    if (rc) { wf_free(st); wf_free_dl(st); return rc; }
+    WfPassPlan plan;
+    if ((rc = wf_plan_passes(st, P, tiles.size() * 256u, total_samples, dl_mode, &plan))) return rc;
+    const uint32_t S = plan.samples;
     if ((rc = trace4_prepare(st, P.S))) return rc;
     if (dl_mode) { st->W.dlA = (float4*)st->dl_mem[0]; st->W.dlB = (float4*)st->dl_mem[1]; st->W.whT = (float4*)st->dl_mem[2]; st->W.dfd = (float4*)st->dl_mem[7]; }
     WfBuffers W = st->W;
@@ -1746,6 +1704,7 @@ int wavefront_render(WavefrontState** state, const RenderParams& P0, const std::
         }
         if (W.mis_any) mis_any_rays += st->host_counters[CTR(10)];   /* the last poll of the pass saw the pass's total */
         hipLaunchKernelGGL(k_wf_accumulate, dim3((n_slots + 255) / 256), dim3(256), 0, stream, P, W);
+        if (hook) hook(hook_ctx, P, W, stream);
     }
     return FTN_OK;
     };

@@ -1,11 +1,13 @@
 /*
  * ftn_wf_common.h -- device-side declarations shared by the wavefront pipeline's translation units (ftn_wavefront.hip: generate /
  * classify / shade / accumulate and the reference-order traversal kernels; ftn_trace4.hip: the production traversal kernels over
- * 128-byte four-box records): path-state bits, the SoA buffers of a wavefront, queue helpers, the leaf primitive test.
+ * 128-byte four-box records; ftn_gbuffer.hip and ftn_moments.hip: the passes beside the beauty): path-state bits, the SoA buffers of a
+ * wavefront, queue helpers, the hit record, the leaf primitive test, and through ftn_film.h the film context of the accumulate kernels.
  */
 #ifndef FTN_WF_COMMON_H
 #define FTN_WF_COMMON_H
 #include "ftn_wavefront.h"
+#include "ftn_film.h"
 
 namespace ftn {
 
@@ -131,6 +133,11 @@ __device__ inline void load_queued_ray(const WfBuffers& W, uint32_t rid, float4*
     const uint32_t pid = rid & ~WF_MIS_BIT;
     if (ANY && !(rid & WF_MIS_BIT)) { *a = W.sh[2 * (size_t)pid]; *b = W.sh[2 * (size_t)pid + 1]; *slot = pid; }
     else { const uint32_t r = (rid & WF_MIS_BIT) ? pid + W.n_paths : pid; *a = W.ray[2 * (size_t)r]; *b = W.ray[2 * (size_t)r + 1]; *slot = r; }
+}
+
+/* the closest hit of ray r as the traversal kernels left it */
+__device__ inline DHit load_hit(const WfBuffers& W, uint32_t r) {
+    const float4 h = W.hit[r]; DHit o; o.t = h.x; o.b0 = h.y; o.b1 = h.z; o.b2 = h.w; o.prim = W.hit_prim[r]; return o;
 }
 
 /* one primitive of a leaf against the ray: Triangle::intersect's hit test (triangle.rs:183-268) with the per-ray permutation

@@ -1,0 +1,70 @@
+/*
+ * ftn_wf_internal.h -- what the driver of a pass on the wavefront pipeline (ftn_gbuffer.hip) may use of ftn_wavefront.hip beyond the
+ * public ftn_wavefront.h: the scene's WavefrontState and its buffers, the knobs, the pass plan, the traversal launches and launchers
+ * for the two kernels every pass starts with.  Declarations only, all of hidden visibility: the library exports the C ABI alone.
+ */
+#ifndef FTN_WF_INTERNAL_H
+#define FTN_WF_INTERNAL_H
+#include "ftn_wf_common.h"
+#include <string>
+
+#pragma GCC visibility push(hidden)
+namespace ftn {
+
+struct WavefrontState {
+    void* sort_tmp = nullptr; size_t sort_tmp_bytes = 0;
+    size_t cap_paths = 0;
+    void* mem[40]; int n_mem = 0;
+    WfBuffers W;
+    float4* br = nullptr; float4* pd = nullptr;          /* WfBuffers::br, WfBuffers::pd */
+    hipEvent_t ev[64]; int n_ev = 0;
+    hipStream_t side = nullptr; hipEvent_t ev_ready = nullptr, ev_side = nullptr;     /* the any-hit launches run beside the closest-hit ones */
+    uint32_t* drain_sig = nullptr; uint32_t drain_seq = 0;                              /* signal memory for hipStreamWaitValue32 (NULL: not supported) */
+    uint32_t* host_counters = nullptr;    /* pinned */
+    int n_cu = 256;
+    /* buffers of the direct-lighting / Whitted mode (grow-only): level terms, and shadow-ray records / results / queue sized for one ray per light */
+    void* dl_mem[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; size_t dl_paths = 0; uint32_t dl_levels = 0, dl_slots = 0; bool dl_tex = false;
+    /* four-box traversal (ftn_trace4.hip): launch plan of the current call and the global spill areas behind the LDS stacks */
+    Trace4Plan t4; bool t4_on = false, t8_on = false, q64_on = false;
+    void* ser_mem[4] = {nullptr, nullptr, nullptr, nullptr}; size_t ser_paths = 0; bool ser_tex = false; uint32_t* ser_host = nullptr;      /* tile-serial sampler on the queues: cursor, film position, retired flag, differentials */
+    void* t4_spill_c = nullptr; void* t4_spill_a = nullptr; size_t t4_spill_c_bytes = 0, t4_spill_a_bytes = 0;
+};
+
+/* the text wavefront_error() returns on this thread */
+void wf_set_error(const std::string& msg);
+#define WF_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { wf_set_error(std::string(#expr ": ") + hipGetErrorString(e_)); return e_ == hipErrorOutOfMemory ? FTN_ERR_OUT_OF_MEMORY : FTN_ERR_NO_DEVICE; } } while (0)
+
+/* tuning knobs (environment overrides, for experiments only): the environment is read once per entry-point call (knobs_begin), not
+ * once per launch of the bounce loop */
+void knobs_begin();
+uint32_t knob(const char* name, uint32_t def);
+
+int wf_state_init(WavefrontState** state);
+int wf_reserve(WavefrontState* st, size_t n_paths);
+void wf_free(WavefrontState* st);
+/* buffers of k_wf_shade_dl for n paths, `levels` chain levels and `slots` shadow rays per path; tex: the differentials of textured scenes */
+int wf_reserve_dl(WavefrontState* st, size_t n, uint32_t levels, uint32_t slots, bool tex);
+void wf_free_dl(WavefrontState* st);
+
+/* The pass plan of a call over n_slots pixel slots and total_samples samples of each: how many samples one pass takes (FTN_WF_PATHS_M,
+ * at most 2^28 paths; with dl, the direct-lighting / Whitted cap on slots x paths), halved while the buffers do not fit, and those
+ * buffers reserved (dl: wf_reserve_dl's too).  Refuses more than 2^28 slots and, with dl, more than 32 lights under WhittedIntegrator
+ * and more slots than the lights leave room for. */
+struct WfPassPlan { uint32_t samples, dl_levels, dl_slots; };
+int wf_plan_passes(WavefrontState* st, const RenderParams& P, size_t n_slots, uint32_t total_samples, bool dl, WfPassPlan* plan);
+
+/* Sizes the four-box kernels' launches for this call and makes sure their spill areas exist */
+int trace4_prepare(WavefrontState* st, const DScene& S);
+/* count: 0 = production kernels, 1 = counting build of the REFERENCE walk (node / primitive tallies equal the oracle's), 2 = counting
+ * build of the production kernels (what bench.py's byte model uses).  max_rays: upper bound of the queue's length (sizes the grid). */
+void launch_trace(WavefrontState* st, bool any, int count, bool spheres, unsigned grid, size_t lds, hipStream_t stream, const RenderParams& P, const WfBuffers& W,
+                  const uint32_t* queue, const uint32_t* count_ptr, uint32_t* head, uint32_t max_rays, bool camera_rays = false);
+
+/* the first two launches of a pass: k_wf_reset in mode 0 (counters, queue lengths of the camera rays, camera_samples) and k_wf_generate
+ * with their launch parameters (a kernel is launched from the unit that defines it) */
+void launch_wf_new_pass(const WfBuffers& W, DevStats* stats, hipStream_t stream);
+void launch_wf_generate(const RenderParams& P, const WfBuffers& W, int write_state, hipStream_t stream);
+
+}  // namespace ftn
+#pragma GCC visibility pop
+#endif

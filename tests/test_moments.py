@@ -232,6 +232,26 @@ def test_chunks_splits_and_device_path(gpu, monkeypatch):
     assert np.array_equal(bits(out.cpu().numpy()), bits(M.resolve(gpu, one, m_one)))
 
 
+@pytest.mark.parametrize("integ_cls", [DirectLightingIntegrator, WhittedIntegrator])
+def test_chunks_direct_lighting_and_whitted(gpu, monkeypatch, integ_cls):
+    """the direct-lighting / Whitted branch of the pass plan through the moments driver: FTN_WF_PATHS_M=1 on a 256^2 film gives passes
+    of 16 samples (2^20 paths / 65,536 slots), 20 spp as 16 + 4, equal to one pass and to ftn_render bit for bit"""
+    spp, seed = 20, 8
+    b, cam, res = scenes.cornell(gpu, res=256)
+    scene = b.create_scene()
+    integ = integ_cls(4)
+    smp = RandomSampler(spp, seed, indexed=True)
+    _, one, m_one, st1 = M.render_moments(gpu, None, cam, res, integ, smp, scene=scene)
+    px_r, st_r = beauty(gpu, scene, cam, GR.film(gpu, res), integ, smp)
+    assert np.array_equal(bits(one.pixels), bits(px_r)) and counters(st1) == counters(st_r)
+    monkeypatch.setenv("FTN_WF_PATHS_M", "1")
+    _, many, m_many, st = M.render_moments(gpu, None, cam, res, integ, smp, scene=scene)
+    px_r2, st_r2 = beauty(gpu, scene, cam, GR.film(gpu, res), integ, smp)
+    assert np.array_equal(bits(many.pixels), bits(px_r2)) and counters(st) == counters(st_r2)
+    assert st["trace_launches"] > st1["trace_launches"]
+    assert np.array_equal(bits(many.pixels), bits(one.pixels)) and np.array_equal(bits(m_many), bits(m_one))
+
+
 # ------------------------------------------------------------------ 5. statistics
 def test_variance_matches_the_spread_of_the_means(gpu):
     """Cornell, 32^2, 8 spp, 48 seeds: the mean predicted variance of the Y mean, summed over the pixels, against the variance of the Y
