@@ -195,6 +195,20 @@ class ftn_adaptive_info(C.Structure):
 
 FTN_ADAPTIVE_ABI_VERSION = 1  # include/fountain_hip_adaptive.h (an extension with a version of its own)
 
+
+class ftn_temporal_pixel(C.Structure):
+    """include/fountain_hip_temporal.h: one pixel of temporal history (accumulated colour, history length, accumulated variances)."""
+    _fields_ = [("u", c_f * 3), ("n", c_f), ("nu", c_f * 4)]
+
+
+class ftn_temporal_params(C.Structure):
+    """include/fountain_hip_temporal.h: parameters of temporal accumulation (ftn_temporal_params_default fills the defaults)."""
+    _fields_ = [("flags", c_u32), ("alpha_min", c_f), ("normal_tol", c_f), ("plane_tol", c_f), ("albedo_eps", c_f), ("albedo_tol", c_f),
+                ("reserved", c_u32 * 2)]
+
+
+FTN_TEMPORAL_ABI_VERSION = 1  # include/fountain_hip_temporal.h (an extension with a version of its own)
+
 FTN_ABI_VERSION = 3          # include/fountain_hip.h; Backend() refuses a product library that reports another one
 
 # Expected sizes (bytes) -- asserted against the header by the C side's static_asserts and tests/test_abi.py
@@ -204,6 +218,7 @@ SIZES = {
     "ftn_film_desc": 32, "ftn_sampler_desc": 24, "ftn_integrator_desc": 16, "ftn_tile_range": 16,
     "ftn_render_options": 16, "ftn_stats": 152, "ftn_scene_memory": 96, "ftn_texture": 48, "ftn_image": 24, "ftn_material_textures": 32,
     "ftn_gbuffer_pixel": 48, "ftn_denoise_params": 32, "ftn_denoise_guided_params": 32, "ftn_moment_pixel": 16, "ftn_adaptive_params": 16, "ftn_adaptive_info": 24,
+    "ftn_temporal_pixel": 32, "ftn_temporal_params": 32,
 }
 
 # Every function the header declares (name -> None); used by the symbol-export test.
@@ -257,4 +272,11 @@ MOMENTS_FUNCTIONS = [
 # adaptive sampling, so these have no orc_* twin either).
 ADAPTIVE_FUNCTIONS = [
     "ftn_adaptive_params_default", "ftn_render_adaptive", "ftn_render_adaptive_device", "ftn_adaptive_converged", "ftn_adaptive_abi_version",
+]
+
+# Every function the extension header include/fountain_hip_temporal.h declares (kept apart from the lists above: the reference renders
+# single frames, so these have no orc_* twin either).
+TEMPORAL_FUNCTIONS = [
+    "ftn_temporal_params_default", "ftn_temporal_accumulate", "ftn_temporal_accumulate_device", "ftn_temporal_accumulate_cpu",
+    "ftn_temporal_abi_version",
 ]

@@ -1,0 +1,144 @@
+/*
+ * ftn_temporal_host.cpp -- C entry points of include/fountain_hip_temporal.h.
+ *
+ * The per-pixel code is ftn_temporal.h's, shared with the kernel; error reporting, device selection and the host thread budget are the host
+ * library's (ftn_host_internal.h).
+ */
+#include "ftn_host_internal.h"
+#include "ftn_temporal.h"
+
+#include <cstring>
+
+using namespace ftn;
+
+namespace {
+
+/* the refusals every entry point shares (the buffers' pointers are checked by the callers); fills the frame's constants */
+static int temporal_check(const ftn_camera_desc* cur, const ftn_film_desc* film, int32_t w, int32_t h, const ftn_camera_desc* prev,
+                          const void* prev_gb12, const void* prev_history, const ftn_temporal_params* p, TpFrame* F) {
+    if (!cur || !film || !p) return fail(FTN_ERR_INVALID_ARGUMENT, "null argument");
+    const int n_prev = (prev != nullptr) + (prev_gb12 != nullptr) + (prev_history != nullptr);
+    if (n_prev != 0 && n_prev != 3)
+        return fail(FTN_ERR_INVALID_ARGUMENT, "prev_camera, prev_gb12 and prev_history must be all null (the first frame) or all given");
+    if (w <= 0 || h <= 0) return fail(FTN_ERR_INVALID_ARGUMENT, "image width and height must be positive");
+    if ((int64_t)w * (int64_t)h >= ((int64_t)1 << 31)) return fail(FTN_ERR_INVALID_ARGUMENT, "w * h must be below 2^31 pixels");
+    if ((int64_t)film->crop[2] - (int64_t)film->crop[0] != w || (int64_t)film->crop[3] - (int64_t)film->crop[1] != h)
+        return fail(FTN_ERR_INVALID_ARGUMENT, "the film's crop is not w x h pixels");
+    if (p->flags & ~(uint32_t)FTN_DENOISE_DEMODULATE) return fail(FTN_ERR_INVALID_ARGUMENT, "unknown ftn_temporal_params.flags bits");
+    if (p->reserved[0] != 0 || p->reserved[1] != 0) return fail(FTN_ERR_INVALID_ARGUMENT, "ftn_temporal_params.reserved must be 0");
+    if (!(p->alpha_min >= 0.0f && p->alpha_min <= 1.0f)) return fail(FTN_ERR_INVALID_ARGUMENT, "ftn_temporal_params.alpha_min must be in 0..1");
+    for (float t : {p->normal_tol, p->plane_tol, p->albedo_tol})
+        if (!(t >= 0.0f) || !dn_finite(t)) return fail(FTN_ERR_INVALID_ARGUMENT, "a tolerance of ftn_temporal_params is negative or not finite");
+    if (!(p->albedo_eps >= 0.0f) || !dn_finite(p->albedo_eps)) return fail(FTN_ERR_INVALID_ARGUMENT, "ftn_temporal_params.albedo_eps is negative or not finite");
+    F->cur = tp_camera(*cur);
+    F->prev = tp_camera(prev ? *prev : *cur);
+    F->same_view = prev && tp_same_view(F->cur, F->prev);
+    F->w = w; F->h = h; F->x0 = film->crop[0]; F->y0 = film->crop[1];
+    F->flags = p->flags;
+    F->alpha_min = p->alpha_min; F->normal_tol = p->normal_tol; F->plane_tol = p->plane_tol; F->albedo_eps = p->albedo_eps; F->albedo_tol = p->albedo_tol;
+    return FTN_OK;
+}
+
+static bool overlaps(const void* a, size_t na, const void* b, size_t nb) {
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    return a0 < b0 + nb && b0 < a0 + na;
+}
+
+}  // namespace
+
+extern "C" {
+
+static_assert(sizeof(ftn_temporal_params) == 32 && sizeof(ftn_temporal_pixel) == 32, "ABI");
+int ftn_temporal_abi_version(void) { return FTN_TEMPORAL_ABI_VERSION; }
+
+void ftn_temporal_params_default(ftn_temporal_params* p) {
+    if (!p) return;
+    p->flags = FTN_DENOISE_DEMODULATE;
+    p->alpha_min = 0.4f;
+    p->normal_tol = 0.01f;
+    p->plane_tol = 1e-3f;
+    p->albedo_eps = 1e-3f;
+    p->albedo_tol = 0.01f;
+    p->reserved[0] = p->reserved[1] = 0;
+}
+
+int ftn_temporal_accumulate_device(const void* rgb, const void* gb12, const void* var4, const ftn_camera_desc* cur_camera, const ftn_film_desc* film,
+                                   int32_t w, int32_t h, const ftn_camera_desc* prev_camera, const void* prev_gb12, const void* prev_history,
+                                   const ftn_temporal_params* p, void* out_history, void* out_rgb, void* out_var4, void* stream) {
+    if (!rgb || !gb12 || !var4 || !out_history || !out_rgb || !out_var4) return fail(FTN_ERR_INVALID_ARGUMENT, "null argument");
+    TpFrame F;
+    int rc = temporal_check(cur_camera, film, w, h, prev_camera, prev_gb12, prev_history, p, &F); if (rc) return rc;
+    const size_t n = (size_t)w * (size_t)h;
+    struct Range { const void* p; size_t bytes; };
+    const Range in[5] = {{rgb, 12 * n}, {gb12, 48 * n}, {var4, 16 * n}, {prev_gb12, 48 * n}, {prev_history, 32 * n}};
+    const Range out[3] = {{out_history, 32 * n}, {out_rgb, 12 * n}, {out_var4, 16 * n}};
+    for (int o = 0; o < 3; o++) {
+        for (const Range& i : in)
+            if (i.p && overlaps(out[o].p, out[o].bytes, i.p, i.bytes)) return fail(FTN_ERR_INVALID_ARGUMENT, "an output overlaps an input");
+        for (int o2 = o + 1; o2 < 3; o2++)
+            if (overlaps(out[o].p, out[o].bytes, out[o2].p, out[o2].bytes)) return fail(FTN_ERR_INVALID_ARGUMENT, "two outputs overlap");
+    }
+    if ((uintptr_t)out_history % 16 || (uintptr_t)prev_history % 16 || (uintptr_t)rgb % 4 || (uintptr_t)gb12 % 4 || (uintptr_t)var4 % 4 ||
+        (uintptr_t)prev_gb12 % 4 || (uintptr_t)out_rgb % 4 || (uintptr_t)out_var4 % 4)
+        return fail(FTN_ERR_INVALID_ARGUMENT, "misaligned buffer: the histories need 16 bytes, the images 4");
+    if (ftn_device_count() <= 0) return fail(FTN_ERR_NO_DEVICE, "no HIP device available: the fountain HIP path needs an AMD GPU (there is no CPU fallback)");
+    const hipError_t e = launch_temporal((const float*)rgb, (const float*)gb12, (const float*)var4, (const float*)prev_gb12, (const float4*)prev_history,
+                                         F, (float4*)out_history, (float*)out_rgb, (float*)out_var4, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(FTN_ERR_INTERNAL, std::string("temporal accumulation launch: ") + hipGetErrorString(e));
+    return FTN_OK;
+}
+
+int ftn_temporal_accumulate(const float* rgb, const float* gb12, const float* var4, const ftn_camera_desc* cur_camera, const ftn_film_desc* film,
+                            int32_t w, int32_t h, const ftn_camera_desc* prev_camera, const float* prev_gb12, const ftn_temporal_pixel* prev_history,
+                            const ftn_temporal_params* p, ftn_temporal_pixel* out_history, float* out_rgb, float* out_var4, int32_t device) {
+    if (!rgb || !gb12 || !var4 || !out_history || !out_rgb || !out_var4) return fail(FTN_ERR_INVALID_ARGUMENT, "null argument");
+    TpFrame F;
+    int rc = temporal_check(cur_camera, film, w, h, prev_camera, prev_gb12, prev_history, p, &F); if (rc) return rc;
+    if (ftn_device_count() <= 0) return fail(FTN_ERR_NO_DEVICE, "no HIP device available: the fountain HIP path needs an AMD GPU (there is no CPU fallback)");
+    if ((rc = set_device(device))) return rc;
+    const size_t n = (size_t)w * (size_t)h;
+    DevBuf<float> d_rgb, d_gb, d_var, d_pgb, d_out, d_ovar;
+    DevBuf<ftn_temporal_pixel> d_ph, d_oh;
+    struct Release { DevBuf<float>* f[6]; DevBuf<ftn_temporal_pixel>* t[2];
+                     ~Release() { for (auto* b : f) b->release(); for (auto* b : t) b->release(); } } keep{{&d_rgb, &d_gb, &d_var, &d_pgb, &d_out, &d_ovar}, {&d_ph, &d_oh}};
+    if ((rc = d_rgb.upload(rgb, 3 * n)) || (rc = d_gb.upload(gb12, 12 * n)) || (rc = d_var.upload(var4, 4 * n))) return rc;
+    if (prev_history && ((rc = d_pgb.upload(prev_gb12, 12 * n)) || (rc = d_ph.upload(prev_history, n)))) return rc;
+    HIP_TRY(hipMalloc((void**)&d_oh.p, n * sizeof(ftn_temporal_pixel)));
+    HIP_TRY(hipMalloc((void**)&d_out.p, 3 * n * sizeof(float)));
+    HIP_TRY(hipMalloc((void**)&d_ovar.p, 4 * n * sizeof(float)));
+    if ((rc = ftn_temporal_accumulate_device(d_rgb.p, d_gb.p, d_var.p, cur_camera, film, w, h, prev_camera, d_pgb.p, d_ph.p, p, d_oh.p, d_out.p,
+                                             d_ovar.p, nullptr))) return rc;
+    HIP_TRY(hipMemcpy(out_history, d_oh.p, n * sizeof(ftn_temporal_pixel), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out_rgb, d_out.p, 3 * n * sizeof(float), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out_var4, d_ovar.p, 4 * n * sizeof(float), hipMemcpyDeviceToHost));
+    return FTN_OK;
+}
+
+int ftn_temporal_accumulate_cpu(const float* rgb, const float* gb12, const float* var4, const ftn_camera_desc* cur_camera, const ftn_film_desc* film,
+                                int32_t w, int32_t h, const ftn_camera_desc* prev_camera, const float* prev_gb12, const ftn_temporal_pixel* prev_history,
+                                const ftn_temporal_params* p, ftn_temporal_pixel* out_history, float* out_rgb, float* out_var4) {
+    if (!rgb || !gb12 || !var4 || !out_history || !out_rgb || !out_var4) return fail(FTN_ERR_INVALID_ARGUMENT, "null argument");
+    TpFrame F;
+    int rc = temporal_check(cur_camera, film, w, h, prev_camera, prev_gb12, prev_history, p, &F); if (rc) return rc;
+    const size_t n = (size_t)w * (size_t)h;
+    /* (the outputs may alias the inputs on the host path: every pixel is computed into buffers of the call's own first) */
+    std::vector<float4> hist(2 * n), prev_copy;
+    std::vector<float> out(3 * n), ovar(4 * n);
+    const float4* prev = (const float4*)prev_history;
+    if (prev_history && (uintptr_t)prev_history % 16) {           /* float4 loads want 16 bytes; a host caller need not give them */
+        prev_copy.resize(2 * n);
+        memcpy(prev_copy.data(), prev_history, n * sizeof(ftn_temporal_pixel));
+        prev = prev_copy.data();
+    }
+    parallel_for(n, [&](size_t i0, size_t i1) {
+        for (size_t i = i0; i < i1; i++)
+            tp_accumulate_pixel(rgb, gb12, var4, prev_gb12, prev, F, (int)(i % (size_t)w), (int)(i / (size_t)w), hist.data(),
+                                out.data(), ovar.data());
+    });
+    memcpy(out_history, hist.data(), n * sizeof(ftn_temporal_pixel));
+    memcpy(out_rgb, out.data(), 3 * n * sizeof(float));
+    memcpy(out_var4, ovar.data(), 4 * n * sizeof(float));
+    return FTN_OK;
+}
+
+}  /* extern "C" */

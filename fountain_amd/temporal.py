@@ -1,0 +1,237 @@
+"""Temporal reprojection and accumulation (include/fountain_hip_temporal.h) for frames of one static scene under a moving camera: each
+frame's resolved beauty, resolved G-buffer (fountain_amd/gbuffer.py) and variance of the mean (fountain_amd/moments.py) are blended with
+the history of the frames before it, fetched where the previous camera saw the pixel's surface.  The accumulated image and variance go
+into the variance-guided filter (fountain_amd/denoise.py) unchanged.
+
+  temporal_params(be, **fields)                                          ftn_temporal_params_default, then the given fields
+  temporal_accumulate(be, rgb, gb12, var4, camera, film, prev=None, params=None, device=-1)   host arrays, accumulated on the GPU
+  temporal_accumulate_cpu(be, rgb, gb12, var4, camera, film, prev=None, params=None)          the host twin, bit-identical to the GPU
+  temporal_accumulate_torch(be, rgb, gb12, var4, camera, film, out_history, out_rgb, out_var4, prev=None, params=None)
+                                                                         float32 CUDA tensors on the current stream, caller buffers
+  TemporalAccumulator(be).push(rgb, gb12, var4, camera, film)            keeps the history and the previous frame between calls
+
+rgb is [H, W, 3], gb12 [H, W, 12], var4 [H, W, 4]; history is [H, W, 8] (ftn_temporal_pixel: u r, g, b, the history length n, then the
+variances of u in r, g, b and of Y).  `camera` has a .desc (PerspectiveCamera, or a PbrtScene's camera), `film` is the Film the frame
+was rendered on (its crop is H x W).  `prev` is None for the first frame, else (previous camera, previous gb12, previous history).  The
+host calls return (history, rgb, var4) as new arrays.  The reference renders single frames, so the CPU oracle has no twin of these calls.
+
+`python -m fountain_amd.temporal f0.pbrt f1.pbrt ... -o out.exr --samples N [--alpha-min A] [--denoise-guided]` renders the files as
+successive frames of one static scene (the first file's; every file gives its frame's camera), frame k with sampler seed k, and writes
+out_<k>.exr (the frame alone), out_<k>_accumulated.exr and, with --denoise-guided, out_<k>_denoised_guided.exr: the variance-guided filter
+over the accumulated image and variance.  It needs at least 2 samples per pixel and files whose films agree.
+"""
+import ctypes as C
+import sys
+
+import numpy as np
+
+from . import _abi as A
+from ._nontwin import check_tensor as _check_tensor, checked_lib
+
+
+def _lib(be):
+    return checked_lib(be, "temporal accumulation has no oracle twin: the reference renders single frames", "temporal", "ftn_temporal_abi_version",
+                       A.FTN_TEMPORAL_ABI_VERSION)
+
+
+def temporal_params(be, **fields):
+    """ftn_temporal_params_default, then the given fields."""
+    p = A.ftn_temporal_params()
+    _lib(be).ftn_temporal_params_default(C.byref(p))
+    for k, v in fields.items():
+        if k not in dict(A.ftn_temporal_params._fields_) or k == "reserved":
+            raise TypeError("ftn_temporal_params has no field %r" % k)
+        setattr(p, k, v)
+    return p
+
+
+def _params(be, params):
+    if params is None:
+        return temporal_params(be)
+    if isinstance(params, dict):
+        return temporal_params(be, **params)
+    if not isinstance(params, A.ftn_temporal_params):
+        raise TypeError("params must be None, a dict or an ftn_temporal_params")
+    return params
+
+
+def _desc(obj, typ, what):
+    d = obj if isinstance(obj, typ) else getattr(obj, "desc", None)
+    if not isinstance(d, typ):
+        raise TypeError("%s must be a %s or carry one as .desc" % (what, typ.__name__))
+    return d
+
+
+def _prev(prev):
+    if prev is None:
+        return None
+    if not isinstance(prev, (tuple, list)) or len(prev) != 3 or any(x is None for x in prev):
+        raise ValueError("prev must be None (the first frame) or (previous camera, previous gb12, previous history)")
+    return prev
+
+
+def _host_frame(rgb, gb12, var4, prev):
+    rgb = np.ascontiguousarray(rgb, dtype=np.float32)
+    gb12 = np.ascontiguousarray(gb12, dtype=np.float32)
+    var4 = np.ascontiguousarray(var4, dtype=np.float32)
+    if rgb.ndim != 3 or rgb.shape[-1] != 3 or gb12.shape != rgb.shape[:2] + (12,) or var4.shape != rgb.shape[:2] + (4,):
+        raise ValueError("expected rgb [H, W, 3], gb12 [H, W, 12] and var4 [H, W, 4], got %r, %r and %r" % (rgb.shape, gb12.shape, var4.shape))
+    prev = _prev(prev)
+    if prev is not None:
+        pgb = np.ascontiguousarray(prev[1], dtype=np.float32)
+        ph = np.ascontiguousarray(prev[2], dtype=np.float32)
+        if pgb.shape != gb12.shape or ph.shape != rgb.shape[:2] + (8,):
+            raise ValueError("expected a previous gb12 %r and a previous history %r, got %r and %r"
+                             % (gb12.shape, rgb.shape[:2] + (8,), pgb.shape, ph.shape))
+        prev = (_desc(prev[0], A.ftn_camera_desc, "the previous camera"), pgb, ph)
+    return rgb, gb12, var4, prev
+
+
+def _host_call(be, fn, rgb, gb12, var4, camera, film, prev, params, tail):
+    p = _params(be, params)
+    cam, fd = _desc(camera, A.ftn_camera_desc, "camera"), _desc(film, A.ftn_film_desc, "film")
+    rgb, gb12, var4, prev = _host_frame(rgb, gb12, var4, prev)
+    h, w = rgb.shape[:2]
+    hist, out, ovar = np.empty((h, w, 8), np.float32), np.empty_like(rgb), np.empty_like(var4)
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p)
+    pc, pg, ph = (C.byref(prev[0]), ptr(prev[1]), ptr(prev[2])) if prev is not None else (None, None, None)
+    be.check(fn(ptr(rgb), ptr(gb12), ptr(var4), C.byref(cam), C.byref(fd), C.c_int32(w), C.c_int32(h), pc, pg, ph, C.byref(p),
+                ptr(hist), ptr(out), ptr(ovar), *tail))
+    return hist, out, ovar
+
+
+def temporal_accumulate(be, rgb, gb12, var4, camera, film, prev=None, params=None, device=-1):
+    """ftn_temporal_accumulate: host arrays, accumulated on GPU `device` (-1 = the current one); returns (history, rgb, var4)."""
+    return _host_call(be, _lib(be).ftn_temporal_accumulate, rgb, gb12, var4, camera, film, prev, params, (C.c_int32(device),))
+
+
+def temporal_accumulate_cpu(be, rgb, gb12, var4, camera, film, prev=None, params=None):
+    """ftn_temporal_accumulate_cpu: the host twin (same bits as the GPU); returns (history, rgb, var4)."""
+    return _host_call(be, _lib(be).ftn_temporal_accumulate_cpu, rgb, gb12, var4, camera, film, prev, params, ())
+
+
+def temporal_accumulate_torch(be, rgb, gb12, var4, camera, film, out_history, out_rgb, out_var4, prev=None, params=None):
+    """ftn_temporal_accumulate_device: rgb [H, W, 3], gb12 [H, W, 12], var4 [H, W, 4] -> out_history [H, W, 8], out_rgb [H, W, 3] and
+    out_var4 [H, W, 4], contiguous float32 CUDA tensors on one device, on its current stream; prev = (previous camera, previous gb12
+    tensor, previous history tensor) or None.  The call allocates nothing, so it can be captured in a graph.  Returns (out_history,
+    out_rgb, out_var4)."""
+    import torch
+    lib = _lib(be)
+    p = _params(be, params)
+    cam, fd = _desc(camera, A.ftn_camera_desc, "camera"), _desc(film, A.ftn_film_desc, "film")
+    if not isinstance(rgb, torch.Tensor) or rgb.dim() != 3:
+        raise ValueError("expected a contiguous float32 CUDA tensor rgb [H, W, 3]")
+    h, w = rgb.shape[:2]
+    prev = _prev(prev)
+    tensors = [(rgb, 3), (gb12, 12), (var4, 4), (out_history, 8), (out_rgb, 3), (out_var4, 4)] + ([(prev[1], 12), (prev[2], 8)] if prev is not None else [])
+    for t, k in tensors:
+        _check_tensor(t, (h, w, k))
+        if t.device != rgb.device:
+            raise ValueError("every tensor must live on the device of rgb")
+    pc, pg, ph = (C.byref(_desc(prev[0], A.ftn_camera_desc, "the previous camera")), C.c_void_p(prev[1].data_ptr()), C.c_void_p(prev[2].data_ptr())) \
+        if prev is not None else (None, None, None)
+    stream = torch.cuda.current_stream(rgb.device).cuda_stream
+    be.check(lib.ftn_temporal_accumulate_device(C.c_void_p(rgb.data_ptr()), C.c_void_p(gb12.data_ptr()), C.c_void_p(var4.data_ptr()), C.byref(cam),
+                                                C.byref(fd), C.c_int32(w), C.c_int32(h), pc, pg, ph, C.byref(p), C.c_void_p(out_history.data_ptr()),
+                                                C.c_void_p(out_rgb.data_ptr()), C.c_void_p(out_var4.data_ptr()), C.c_void_p(stream)))
+    return out_history, out_rgb, out_var4
+
+
+class TemporalAccumulator:
+    """The state a frame sequence carries: the history, the previous frame's G-buffer and its camera.  push() accumulates one frame on
+    the GPU (on the host twin with cpu=True) and returns (accumulated rgb, accumulated var4); reset() forgets the history, so the next
+    frame is a first frame.  A frame of another size resets by itself."""
+
+    def __init__(self, be, params=None, device=-1, cpu=False):
+        self.be, self.device, self.cpu = be, device, cpu
+        self.params = _params(be, params)
+        self.reset()
+
+    def reset(self):
+        self.history = None             # [H, W, 8] after the first push
+        self.prev_gb12 = None
+        self.prev_camera = None
+        self.frames = 0
+
+    def push(self, rgb, gb12, var4, camera, film):
+        cam = _desc(camera, A.ftn_camera_desc, "camera")
+        if self.history is not None and self.history.shape[:2] != np.shape(rgb)[:2]:
+            self.reset()
+        prev = None if self.history is None else (self.prev_camera, self.prev_gb12, self.history)
+        if self.cpu:
+            hist, out, ovar = temporal_accumulate_cpu(self.be, rgb, gb12, var4, cam, film, prev, self.params)
+        else:
+            hist, out, ovar = temporal_accumulate(self.be, rgb, gb12, var4, cam, film, prev, self.params, self.device)
+        keep = A.ftn_camera_desc()
+        C.memmove(C.byref(keep), C.byref(cam), C.sizeof(cam))
+        self.history, self.prev_gb12, self.prev_camera = hist, np.array(gb12, dtype=np.float32), keep
+        self.frames += 1
+        return out, ovar
+
+
+def frame_paths(filename, k):
+    """out.exr, k -> (out_<k>.exr, out_<k>_accumulated.exr, out_<k>_denoised_guided.exr)"""
+    base = filename[:-4] if filename.endswith(".exr") else filename
+    return "%s_%d.exr" % (base, k), "%s_%d_accumulated.exr" % (base, k), "%s_%d_denoised_guided.exr" % (base, k)
+
+
+def main(argv=None):
+    import argparse
+    ap = argparse.ArgumentParser(prog="fountain_amd.temporal")
+    ap.add_argument("scene_files", nargs="+", help="one .pbrt file per frame: the first one's scene, every file's camera")
+    ap.add_argument("-o", "--output", dest="image_name", default=None)
+    ap.add_argument("--samples", type=int, default=None)
+    ap.add_argument("--gpu", type=int, default=0)
+    ap.add_argument("--max-depth", type=int, default=5)
+    ap.add_argument("--rr-threshold", type=float, default=1.0)
+    ap.add_argument("--alpha-min", type=float, default=None, help="floor of the current frame's blend weight, 0..1 (default: the library's)")
+    ap.add_argument("--denoise-guided", action="store_true",
+                    help="also write <name>_<k>_denoised_guided.exr: the variance-guided filter over the accumulated image and variance")
+    opts = ap.parse_args(argv)
+    if opts.samples is not None and opts.samples < 2:
+        print("error: temporal accumulation needs at least 2 samples per pixel: a pixel's variance is unknown below that (here %d)" % opts.samples,
+              file=sys.stderr)
+        return 2
+    if opts.alpha_min is not None and not 0.0 <= opts.alpha_min <= 1.0:
+        print("error: --alpha-min must be in 0..1", file=sys.stderr)
+        return 2
+    from .api import PathIntegrator, PbrtScene, RandomSampler, default_backend, write_exr
+    from .denoise import denoise_guided
+    from .gbuffer import CHANNELS, render_gbuffer
+    from .moments import render_moments
+    be = default_backend()
+    frames = [PbrtScene(f, be) for f in opts.scene_files]
+    first = frames[0]
+    spp = opts.samples or first.samples_per_pixel
+    if spp < 2:
+        print("error: temporal accumulation needs at least 2 samples per pixel: a pixel's variance is unknown below that (here %d)" % spp, file=sys.stderr)
+        return 2
+    for f, name in zip(frames[1:], opts.scene_files[1:]):
+        if bytes(f._film_desc) != bytes(first._film_desc):
+            print("error: %s has another film than %s: the frames of a sequence share resolution and crop" % (name, opts.scene_files[0]), file=sys.stderr)
+            return 2
+    filename = opts.image_name or first.film_name
+    if ".exr" not in filename:
+        raise SystemExit("output must be an .exr file")
+    scene = first.create_scene(device=opts.gpu)
+    radiance = PathIntegrator.new(opts.max_depth, opts.rr_threshold)
+    acc = TemporalAccumulator(be, None if opts.alpha_min is None else dict(alpha_min=opts.alpha_min), device=opts.gpu)
+    for k, f in enumerate(frames):
+        sampler = RandomSampler.new_with_seed(spp, k, indexed=True)
+        var4, film, _, _ = render_moments(be, None, f.camera, None, radiance, sampler, scene=scene, film=f.film(), device=opts.gpu)
+        img, _ = film.into_spectrum_buffer()
+        res, _, _ = render_gbuffer(be, None, f.camera, None, sampler, scene=scene, film=f.film(), device=opts.gpu)
+        gb12 = np.concatenate([res[c] for c in CHANNELS], axis=-1)
+        out, ovar = acc.push(img, gb12, var4, f.camera, film)
+        plain, accumulated, denoised = frame_paths(filename, k)
+        write_exr(plain, img, be)
+        write_exr(accumulated, out, be)
+        if opts.denoise_guided:
+            write_exr(denoised, denoise_guided(be, out, gb12, ovar, device=opts.gpu), be)
+        print("frame %d: %s, %s%s (mean history length %.2f)" % (k, plain, accumulated, ", " + denoised if opts.denoise_guided else "",
+                                                                  float(acc.history[..., 3].mean())), file=sys.stderr)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
