@@ -209,6 +209,16 @@ class ftn_temporal_params(C.Structure):
 
 FTN_TEMPORAL_ABI_VERSION = 1  # include/fountain_hip_temporal.h (an extension with a version of its own)
 
+class ftn_filter_desc(C.Structure):
+    """include/fountain_hip_filter.h: a reconstruction filter (ftn_filter_init fills the defaults of a kind)."""
+    _fields_ = [("kind", c_u32), ("radius", c_f * 2), ("param", c_f * 2), ("reserved", c_u32 * 3)]
+
+
+FTN_FILTER_BOX, FTN_FILTER_TRIANGLE, FTN_FILTER_GAUSSIAN, FTN_FILTER_MITCHELL, FTN_FILTER_SINC = range(5)
+FTN_FILTER_TABLE_WIDTH = 16
+FTN_FILTER_MAX_RADIUS = 8.0
+FTN_FILTER_ABI_VERSION = 1  # include/fountain_hip_filter.h (an extension with a version of its own)
+
 FTN_ABI_VERSION = 3          # include/fountain_hip.h; Backend() refuses a product library that reports another one
 
 # Expected sizes (bytes) -- asserted against the header by the C side's static_asserts and tests/test_abi.py
@@ -218,7 +228,7 @@ SIZES = {
     "ftn_film_desc": 32, "ftn_sampler_desc": 24, "ftn_integrator_desc": 16, "ftn_tile_range": 16,
     "ftn_render_options": 16, "ftn_stats": 152, "ftn_scene_memory": 96, "ftn_texture": 48, "ftn_image": 24, "ftn_material_textures": 32,
     "ftn_gbuffer_pixel": 48, "ftn_denoise_params": 32, "ftn_denoise_guided_params": 32, "ftn_moment_pixel": 16, "ftn_adaptive_params": 16, "ftn_adaptive_info": 24,
-    "ftn_temporal_pixel": 32, "ftn_temporal_params": 32,
+    "ftn_temporal_pixel": 32, "ftn_temporal_params": 32, "ftn_filter_desc": 32,
 }
 
 # Every function the header declares (name -> None); used by the symbol-export test.
@@ -280,3 +290,17 @@ TEMPORAL_FUNCTIONS = [
     "ftn_temporal_params_default", "ftn_temporal_accumulate", "ftn_temporal_accumulate_device", "ftn_temporal_accumulate_cpu",
     "ftn_temporal_abi_version",
 ]
+
+# Every function the extension header include/fountain_hip_filter.h declares (kept apart from the lists above: the reference's only
+# filter is the box, so these have no orc_* twin either), with its prototype: name -> argument types (every one returns int).
+_RENDER_ARGS = [C.c_void_p] * 8
+FILTER_PROTOTYPES = {
+    "ftn_filter_init": [c_u32, C.c_void_p],
+    "ftn_filter_table": [C.c_void_p, C.c_void_p],
+    "ftn_render_filtered": _RENDER_ARGS + [C.c_void_p, C.c_void_p],
+    "ftn_render_filtered_device": _RENDER_ARGS + [C.c_void_p, C.c_void_p, C.c_void_p],
+    "ftn_filter_accumulate_samples": [C.c_void_p, C.c_void_p, C.c_size_t] + [C.c_void_p] * 6,
+    "ftn_pbrt_filter": [C.c_void_p, C.c_void_p],
+    "ftn_filter_abi_version": [],
+}
+FILTER_FUNCTIONS = sorted(FILTER_PROTOTYPES)

@@ -5,10 +5,11 @@
  * Every number goes through the same ftn_* constructors the rest of the library uses, so a parsed file and a scene assembled
  * call by call are bit-identical.  Reference quirks kept: `ReverseOrientation` sets (does not toggle) the flag (pbrt.rs:203-205);
  * plastic reads "ks" in lower case (constructors.rs:232); point/distant lights ignore the CTM; Integrator / PixelFilter /
- * Accelerator statements are ignored (pbrt.rs:528-530); ObjectBegin/End are unimplemented in the reference -> FTN_ERR_UNSUPPORTED.
+ * Accelerator statements are ignored (pbrt.rs:528-530; PixelFilter is remembered for ftn_pbrt_filter alone); ObjectBegin/End are unimplemented in the reference -> FTN_ERR_UNSUPPORTED.
  * Texture statements: checkerboard (spectrum / float), uv and imagemap (OpenEXR files) as in pbrt.rs:362-385.
  */
 #include "../../include/fountain_hip.h"
+#include "../../include/fountain_hip_filter.h"
 
 #include <cmath>
 #include <cstdio>
@@ -62,6 +63,7 @@ struct ftn_pbrt {
     /* header */
     ftn_transform header_tf, camera_tf; ParamSet camera_params, sampler_params, film_params; bool has_camera = false;
     ftn_camera_desc camera; ftn_film_desc film; int spp = 16;
+    bool has_filter = false; std::string filter_name; ParamSet filter_params;      /* the PixelFilter statement, kept for ftn_pbrt_filter alone */
     /* world */
     std::vector<GState> gs; std::vector<ftn_transform> tf;
     std::map<std::string, int> named_materials;
@@ -383,7 +385,8 @@ int parse(ftn_pbrt* S, const std::string& path) {
         if (w == "Camera") { S->camera_params = ps; S->camera_params["name"].s = {type}; S->camera_tf = S->header_tf; S->has_camera = true; }
         else if (w == "Sampler") S->sampler_params = ps;
         else if (w == "Film") S->film_params = ps;
-        else if (w == "PixelFilter" || w == "Integrator" || w == "Accelerator") { /* ignored: pbrt.rs:528-530 */ }
+        else if (w == "PixelFilter") { S->has_filter = true; S->filter_name = type; S->filter_params = ps; }      /* ignored by everything but ftn_pbrt_filter: pbrt.rs:528-530 */
+        else if (w == "Integrator" || w == "Accelerator") { /* ignored: pbrt.rs:528-530 */ }
         else if (w == "Material") { int m; if ((rc = add_material(S, type, ps, &m))) return rc; S->gs.back().material = m; }
         else if (w == "MakeNamedMaterial") {
             auto it = ps.find("type"); if (it == ps.end() || it->second.s.empty()) return fail(S, FTN_ERR_INVALID_ARGUMENT, "MakeNamedMaterial needs a string type");
@@ -512,6 +515,21 @@ const ftn_film_desc* ftn_pbrt_film(const ftn_pbrt* s) { return &s->film; }
 int ftn_pbrt_samples_per_pixel(const ftn_pbrt* s) { return s->spp; }
 const char* ftn_pbrt_film_name(const ftn_pbrt* s) { return s->film_name.c_str(); }
 const char* ftn_pbrt_last_error(void) { return g_pbrt_err.c_str(); }
+/* the PixelFilter statement as a filter description (include/fountain_hip_filter.h): PBRT's xwidth / ywidth are the radii */
+int ftn_pbrt_filter(const ftn_pbrt* s, ftn_filter_desc* out) {
+    if (!s || !out) return FTN_ERR_INVALID_ARGUMENT;
+    if (!s->has_filter) return 0;
+    static const char* const names[5] = {"box", "triangle", "gaussian", "mitchell", "sinc"};
+    uint32_t kind = 0;
+    while (kind < 5 && s->filter_name != names[kind]) kind++;
+    if (kind == 5 || ftn_filter_init(kind, out)) { g_pbrt_err = "UnknownName(" + s->filter_name + ")"; return FTN_ERR_INVALID_ARGUMENT; }
+    const ParamSet& ps = s->filter_params;
+    out->radius[0] = getf(ps, "xwidth", out->radius[0]); out->radius[1] = getf(ps, "ywidth", out->radius[1]);
+    if (kind == FTN_FILTER_GAUSSIAN) out->param[0] = getf(ps, "alpha", out->param[0]);
+    if (kind == FTN_FILTER_MITCHELL) { out->param[0] = getf(ps, "B", out->param[0]); out->param[1] = getf(ps, "C", out->param[1]); }
+    if (kind == FTN_FILTER_SINC) out->param[0] = getf(ps, "tau", out->param[0]);
+    return 1;
+}
 /* PLY reader on its own (constructors.rs:94-190): fills caller arrays after a sizing call with NULL outputs */
 int ftn_ply_load(const char* path, uint32_t* n_vertices, uint32_t* n_triangles, float* P, float* N, float* UV, uint32_t* indices, int* has_normals, int* has_uvs) {
     ftn_pbrt tmp; Mesh m;

@@ -20,6 +20,11 @@ unchanged.  It has the needs of --gbuffer and at least 2 samples per pixel, and 
 8, at most the samples per pixel), then twice as many, and so on up to --samples, until the estimated relative standard error of
 each of its pixels' mean luminance is at most T.  It writes <name>_spp.exr beside the image: each pixel's final sample count in R, G and B.  --variance works with it (from
 the same moments); --gbuffer, --denoise, --exact-stream and more than one GPU do not.
+--pixel-filter {scene,box,triangle,gaussian,mitchell,sinc} renders the image through a reconstruction filter (fountain_amd/filters.py):
+`scene` takes the file's PixelFilter statement (an error if it has none), the others the defaults of that filter; --filter-width X [Y]
+sets the radius.  A wide filter mixes the samples of neighbouring pixels, so --gbuffer, --denoise, --denoise-guided, --variance and
+--adaptive, which assume that a pixel's samples are its own, are refused with it, as are --exact-stream and more than one GPU.
+Without the option the image is the reference's: a box of radius 0.5, whatever the file says.
 """
 import argparse
 import sys
@@ -48,7 +53,21 @@ def main(argv=None):
     ap.add_argument("--adaptive", type=float, default=None, metavar="T",
                     help="per-tile adaptive sampling up to --samples: stop a tile once its pixels' relative standard error is at most T; also writes <name>_spp.exr")
     ap.add_argument("--min-samples", type=int, default=None, help="with --adaptive: the samples every tile gets first (default 8)")
+    ap.add_argument("--pixel-filter", default=None, choices=["scene", "box", "triangle", "gaussian", "mitchell", "sinc"],
+                    help="render through this reconstruction filter (scene: the file's PixelFilter statement)")
+    ap.add_argument("--filter-width", type=float, nargs="+", default=None, metavar="X", help="with --pixel-filter: the filter's radius, X [Y]")
     opts = ap.parse_args(argv)
+    if opts.filter_width is not None and (opts.pixel_filter is None or len(opts.filter_width) > 2):
+        print("error: --filter-width X [Y] belongs to --pixel-filter", file=sys.stderr)
+        return 2
+    if opts.pixel_filter is not None:
+        for flag, on in (("--gbuffer", opts.gbuffer), ("--denoise", opts.denoise), ("--denoise-guided", opts.denoise_guided), ("--variance", opts.variance),
+                         ("--adaptive", opts.adaptive is not None), ("--exact-stream", opts.exact_stream),
+                         ("more than one GPU (--gpus)", opts.gpus is not None and opts.gpus > 1)):
+            if on:
+                print("error: --pixel-filter does not work with %s: a filtered pixel holds samples of its neighbours, and the filtered film renders"
+                      " on one GPU with the default sampler" % flag, file=sys.stderr)
+                return 2
     if opts.min_samples is not None and opts.adaptive is None:
         print("error: --min-samples belongs to --adaptive", file=sys.stderr)
         return 2
@@ -76,9 +95,9 @@ def main(argv=None):
         # started plainly: start the N ranks as a child process (before anything here has touched HIP) and hand back its exit code
         return spawn_ranks(opts.gpus, sys.argv[1:] if argv is None else list(argv), module="fountain_amd.render")
     world, rank = (env_world[0], env_world[1]) if env_world is not None else (1, 0)
-    if (opts.gbuffer or opts.denoise or opts.variance or opts.denoise_guided or opts.adaptive is not None) and world > 1:
+    if (opts.gbuffer or opts.denoise or opts.variance or opts.denoise_guided or opts.adaptive is not None or opts.pixel_filter is not None) and world > 1:
         flag = "--gbuffer" if opts.gbuffer else "--denoise" if opts.denoise else "--variance" if opts.variance else \
-            "--denoise-guided" if opts.denoise_guided else "--adaptive"
+            "--denoise-guided" if opts.denoise_guided else "--adaptive" if opts.adaptive is not None else "--pixel-filter"
         print("error: %s renders on one GPU, not under a launcher of %d ranks" % (flag, world), file=sys.stderr)
         return 2
     if opts.gpus is not None and opts.gpus != world:
@@ -104,6 +123,18 @@ def main(argv=None):
         if not 2 <= opts.min_samples <= n_max:
             print("error: --adaptive needs 2 <= --min-samples <= samples per pixel (here %d and %d)" % (opts.min_samples, n_max), file=sys.stderr)
             return 2
+    filt = None
+    if opts.pixel_filter is not None:
+        from .filters import Filter
+        if opts.pixel_filter == "scene":
+            filt = Filter.from_pbrt(parsed)
+            if filt is None:
+                print("error: --pixel-filter scene, but %s has no PixelFilter statement" % opts.scene_file, file=sys.stderr)
+                return 2
+            if opts.filter_width is not None:
+                filt.desc.radius[0], filt.desc.radius[1] = opts.filter_width[0], opts.filter_width[-1]
+        else:
+            filt = Filter(opts.pixel_filter, None if opts.filter_width is None else (opts.filter_width[0], opts.filter_width[-1]), be=be)
     scene = parsed.create_scene(device=opts.gpu)
     film = parsed.film()
     integrator = SamplerIntegrator(parsed.camera, PathIntegrator.new(opts.max_depth, opts.rr_threshold))
@@ -130,6 +161,10 @@ def main(argv=None):
         dist.destroy_process_group()
         if rank != 0:
             return 0
+    elif filt is not None:
+        from .filters import filtered_film, render_filtered
+        film = filtered_film(be, filt, film=film)
+        _, _, st = render_filtered(be, None, parsed.camera, None, integrator.radiance, sampler, filt, scene=scene, film=film, device=opts.gpu)
     elif opts.adaptive is not None:
         # each tile at its own sample count, with the moments that decided it beside the beauty
         from .adaptive import params, render_adaptive
