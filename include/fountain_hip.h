@@ -477,6 +477,17 @@ int ftn_test_texture_eval(const ftn_scene* scene, int32_t texture, const float* 
 #define FTN_TEST_BSDF_OUT 16
 int ftn_test_bsdf(const ftn_scene* scene, int32_t material, uint32_t flags, int allow_multiple_lobes, int specialised,
                   const float* rows_in, size_t n, float* rows_out);
+/* Light hook: Light::sample_incident_radiance, Light::pdf_incident_radiance and the emitted radiance ON THE DEVICE for n synthetic
+ * reference points and light `light` of the scene (Scene::new's order: the explicit lights, then the area lights in BVH primitive order).
+ * rows_in (HOST memory), 15 floats per row: the reference point's p[3], p_err[3], n[3] and time (what spawn_ray reads), a world-space
+ * direction wi[3], the sample u[2].  rows_out, 24 floats per row: from the sample at u [0..2] radiance, [3..5] wi, [6] pdf, [7..9] p1.p,
+ * [10..12] p1.p_err, [13..15] p1.n, [16] p1.time; [17] the pdf of the input wi; [18] the pdf of the sample's own wi; [19..21] for an
+ * infinite light its emitted radiance along the input wi, for an area light L(p1, -wi of the sample), else 0; [22..23] 0.
+ * via_env0 = 1 reads the copy of the light that scenes lit by ONE infinite light keep in the kernel arguments, as the shading kernels
+ * specialised for such scenes do (refused for every other scene): the rows must not differ.  n == 0 does nothing.                 */
+#define FTN_TEST_LIGHT_IN 15
+#define FTN_TEST_LIGHT_OUT 24
+int ftn_test_light(const ftn_scene* scene, int32_t light, int via_env0, const float* rows_in, size_t n, float* rows_out);
 
 /* ------------------------------------------------------------------ misc */
 const char* ftn_last_error(void);

@@ -400,6 +400,27 @@ int orc_test_bsdf(const orc_scene* s, int32_t material, uint32_t flags, int allo
     }
     return FTN_OK;
 }
+// ---- lights (orc_scene.hpp, orc_shapes.hpp): the twin of ftn_test_light (fountain_hip.h has the row layouts); `via_env0` has no meaning here
+int orc_test_light(const orc_scene* s, int32_t light, int /*via_env0*/, const float* in15, size_t n, float* out24) {
+    if (!s || !in15 || !out24) return fail(FTN_ERR_INVALID_ARGUMENT, "null argument");
+    if (light < 0 || (size_t)light >= s->data.lights.size()) return fail(FTN_ERR_INVALID_ARGUMENT, "light index out of range");
+    const Light& L = s->data.lights[light];
+    for (size_t i = 0; i < n; i++) {
+        const float* r = in15 + 15 * i; float* o = out24 + 24 * i;
+        SurfaceHit ref; ref.p = Vec3(r[0], r[1], r[2]); ref.p_err = Vec3(r[3], r[4], r[5]); ref.n = Vec3(r[6], r[7], r[8]); ref.time = r[9];
+        const Vec3 wi(r[10], r[11], r[12]); const Vec2 u(r[13], r[14]);
+        const LiSample ls = L.sample_incident_radiance(ref, u);
+        Spectrum le(0.0f);
+        if (L.kind == Light::INFINITE) { Ray ray; ray.origin = ref.p; ray.dir = wi; le = L.environment_emitted_radiance(ray); }
+        else if (L.kind == Light::AREA) le = L.area_emitted_radiance(ls.p1, -ls.wi);
+        o[0] = ls.radiance[0]; o[1] = ls.radiance[1]; o[2] = ls.radiance[2]; o[3] = ls.wi.x; o[4] = ls.wi.y; o[5] = ls.wi.z; o[6] = ls.pdf;
+        o[7] = ls.p1.p.x; o[8] = ls.p1.p.y; o[9] = ls.p1.p.z; o[10] = ls.p1.p_err.x; o[11] = ls.p1.p_err.y; o[12] = ls.p1.p_err.z;
+        o[13] = ls.p1.n.x; o[14] = ls.p1.n.y; o[15] = ls.p1.n.z; o[16] = ls.p1.time;
+        o[17] = L.pdf_incident_radiance(ref, wi); o[18] = L.pdf_incident_radiance(ref, ls.wi);
+        o[19] = le[0]; o[20] = le[1]; o[21] = le[2]; o[22] = 0.0f; o[23] = 0.0f;
+    }
+    return FTN_OK;
+}
 // MIPMap::lookup_trilinear_width on an image built by MIPMap::new (custom = 0) or new_custom (custom = 1): rows of {s, t, width}
 void orc_kat_mipmap_lookup(uint32_t w, uint32_t h, const float* texels, int wrap, int custom, const float* st_width3, size_t n, float* out3) {
     MIPMap m;

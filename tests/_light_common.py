@@ -1,0 +1,830 @@
+"""Shared by tests/test_light_cpu.py (the oracle) and tests/test_light.py (the device): the light configurations, the rows fed to the
+light hook (ftn_test_light / orc_test_light), the measured tolerances and the property checks, so that both sides face the same seeds and
+the same bounds."""
+import ctypes as C
+from concurrent.futures import ThreadPoolExecutor
+
+import numpy as np
+
+import _light_ref as R
+from _bsdf_common import wilson_hilferty
+from fountain_amd import SceneBuilder, _abi as A
+
+f32 = np.float32
+PI = np.pi
+NIN, NOUT = A.FTN_TEST_LIGHT_IN, A.FTN_TEST_LIGHT_OUT
+COLUMNS = dict(radiance=slice(0, 3), wi=slice(3, 6), pdf=6, p1_p=slice(7, 10), p1_perr=slice(10, 13), p1_n=slice(13, 16), p1_time=16, pdf_in=17, pdf_s=18,
+               le=slice(19, 22))
+
+# ---- measured tolerances.  Metric: |got - want| / max(|want|, FLOOR) per component over every output of the hook, rows flagged
+# fragile by the restatement left out.  Measured with the libm oracle against the binary64 restatement on the CPU over every configuration of
+# test_oracle_matches_the_restatement: 99.9th percentile MEASURED_P999, maximum MEASURED_MAX.  The bounds are 4 x the measurement: the
+# deterministic math is within 1 ulp of libm in sin / cos / acos / atan2, and rounding differs per input set.
+FLOOR = 1.0e-3
+MEASURED_P999, MEASURED_MAX = 1.92e-4, 3.11e-2        # env_sq128 (the sample's pdf next to a pole) / sph_scaled (pdf_from_ref of a ray close to the limb)
+TOL_P999, TOL_MAX = 4.0 * MEASURED_P999, 4.0 * MEASURED_MAX
+MEASURED_FRAGILE_SHARE = 0.0040              # largest share of rows left out in one configuration of that test (sph_scaled), libm oracle
+MAX_FRAGILE_SHARE = 0.005
+# the share of a triangle's edge table whose rays are not finite to begin with (NaN, infinite, zero or overflowing direction or origin: 43.5 % to 44.9 %
+# of its rows by construction): no more rows than that may ever fall under undefined_by_the_reference, and none of the random rows
+MAX_UNDEFINED_SHARE = 0.45
+
+
+# ---------------------------------------------------------------- configurations
+def _matte_ball(b):
+    """what every scene without triangles holds besides its lights, so that the world's bounding sphere is not empty"""
+    b.attribute_begin(); b.translate((0.3, -0.2, 0.1)); b.shape("sphere", radius=1.0); b.attribute_end()
+
+
+def _env_texels(w, h, seed):
+    """random texels in [0.05, 1) under a smooth bright lobe: every cell has a share, no share is negligible"""
+    rng = np.random.default_rng(seed)
+    t = rng.uniform(0.05, 1.0, (h, w, 3))
+    y, x = np.meshgrid((np.arange(h) + 0.5) / h, (np.arange(w) + 0.5) / w, indexing="ij")
+    lobe = 1.0 + 6.0 * np.exp(-((x - 0.3) ** 2 + (y - 0.4) ** 2) / 0.02)
+    return (t * lobe[:, :, None]).astype(f32)
+
+
+def _plateau_texels():
+    """65 x 65: texel rows 29..35 and texel columns 59..64 are black, so the distribution's rows 30..35 and columns 60..64 are 0: the marginal CDF
+    is flat across entry 32, every conditional CDF is flat across entry 64 and ends flat (u.x = 1 then lands in a cell of probability 0)"""
+    t = _env_texels(65, 65, 65)
+    t[29:36, :, :] = 0.0
+    t[:, 59:65, :] = 0.0
+    return t
+
+
+def _one(t, value, at=(7, 11)):
+    t = t.copy(); t[at[0], at[1], :] = value
+    return t
+
+
+ENV_MAPS = {
+    "env_uniform": None,
+    "env_sq2": _env_texels(2, 2, 2), "env_sq31": _env_texels(31, 31, 31), "env_sq32": _env_texels(32, 32, 32), "env_sq33": _env_texels(33, 33, 33),
+    "env_sq40": _env_texels(40, 40, 40),                      # (a tail block of the coarse tables with more than one entry)
+    "env_sq64": _env_texels(64, 64, 64), "env_sq65": _env_texels(65, 65, 66), "env_sq128": _env_texels(128, 128, 128),
+    "env_3x5": _env_texels(3, 5, 35), "env_33x64": _env_texels(33, 64, 3364), "env_64x33": _env_texels(64, 33, 6433),
+    "env_rotated": _env_texels(32, 32, 77),
+    "env_plateau": _plateau_texels(),
+    "env_zero": np.zeros((32, 32, 3), f32),
+    "env_huge": _one(_env_texels(33, 33, 34), 1.0e30),
+    "env_nan": _one(_env_texels(31, 31, 30), np.nan),          # (31 is no power of two: compute_distribution reads level 0 alone, _light_ref.py)
+}
+SQUARE_ENVS = [k for k, v in ENV_MAPS.items() if v is None or v.shape[0] == v.shape[1]]
+MONOTONE_ENVS = [k for k in ENV_MAPS if k != "env_nan"]
+WELL_FORMED_ENVS = [k for k in ENV_MAPS if k not in ("env_nan", "env_zero", "env_huge")]
+ENV_VARIANTS = {"default": {}, "no_cells": {"FTN_ENV_CELLS": "0"}, "no_coarse": {"FTN_NO_COARSE_CDF": "1"}}
+
+TRI_P = [(-1.0, -1.0, 0.0), (1.0, -1.0, 0.25), (0.0, 1.0, 0.5)]
+TRIANGLES = {
+    "tri_plain": dict(P=TRI_P),
+    "tri_normals_against": dict(P=TRI_P, N=[(0.1, 0.2, -1.0), (-0.2, 0.1, -0.9), (0.3, -0.1, -1.1)]),         # the winding's normal has z > 0
+    "tri_reversed": dict(P=TRI_P, reverse=True),
+    "tri_flipped": dict(P=TRI_P, mirror=True),                                                                # a handedness-swapping transform: GF_FLIP
+    "tri_uv": dict(P=TRI_P, uv=[(0.0, 0.0), (1.0, 0.0), (0.0, 1.0)]),
+    "tri_uv_degenerate": dict(P=TRI_P, uv=[(0.5, 0.5), (0.5, 0.5), (0.5, 0.5)]),
+    "tri_normals_uv": dict(P=TRI_P, N=[(0.1, 0.2, 1.0), (-0.2, 0.1, 0.9), (0.3, -0.1, 1.1)], uv=[(0.0, 0.0), (1.0, 0.0), (0.0, 1.0)]),
+    "tri_sliver": dict(P=[(0.0, 0.0, 0.0), (1.0e-6, 0.0, 0.0), (0.0, 2.0e-6, 0.0)]),                          # area 1e-12
+    "tri_far": dict(P=[(10000.0, 12000.0, 9000.0), (12500.0, 10000.0, 9500.0), (10500.0, 13000.0, 11000.0)]),
+}
+TRI_VARIANTS = {"srec": {}, "no_srec": {"FTN_SREC": "0"}, "dense": {}}       # triangle-only with shading records / without / beside a sphere
+
+SPHERES = {
+    "sph_full": dict(radius=1.5, at=(0.5, -1.0, 2.0)),
+    "sph_partial": dict(radius=1.0, at=(0.5, -1.0, 2.0), zmin=-0.3, zmax=0.7, phimax=250.0),
+    "sph_reversed": dict(radius=1.5, at=(0.5, -1.0, 2.0), reverse=True),
+    "sph_scaled": dict(radius=1.0, at=(0.5, -1.0, 2.0), rotate=(35.0, (1.0, 2.0, 3.0)), scale=(1.5, 0.7, 1.1)),
+}
+DELTAS = ["point_alone", "distant_alone", "point_among", "distant_among"]
+EMIT = (5.0, 4.0, 3.0)
+
+
+def _add_triangle(b, spec, emit=True):
+    b.attribute_begin()
+    if spec.get("mirror"):
+        b.scale(1.0, 1.0, -1.0)
+    if spec.get("reverse"):
+        b.reverse_orientation()
+    if emit:
+        b.area_light_source("diffuse", L=EMIT)
+    b.shape("trianglemesh", P=spec["P"], N=spec.get("N"), uv=spec.get("uv"), indices=[0, 1, 2])
+    b.attribute_end()
+
+
+def _add_sphere(b, spec):
+    b.attribute_begin()
+    b.translate(spec["at"])
+    if "rotate" in spec:
+        b.rotate(*spec["rotate"])
+    if "scale" in spec:
+        b.scale(*spec["scale"])
+    if spec.get("reverse"):
+        b.reverse_orientation()
+    b.area_light_source("diffuse", L=EMIT)
+    b.shape("sphere", radius=spec["radius"], zmin=spec.get("zmin", -spec["radius"]), zmax=spec.get("zmax", spec["radius"]), phimax=spec.get("phimax", 360.0))
+    b.attribute_end()
+
+
+def _add_env(b, name):
+    b.attribute_begin()
+    if name == "env_rotated":
+        b.rotate(40.0, (1.0, 1.0, 0.3))
+    if ENV_MAPS[name] is None:
+        b.light_source("infinite", L=(1.0, 2.0, 3.0))
+    else:
+        b.light_source("infinite", texels=ENV_MAPS[name])
+    b.attribute_end()
+
+
+def build(be, name, variant="default", among=False):
+    """-> (SceneBuilder, index of the light under test).  among: the light is one of several (infinite lights: a point light comes first)"""
+    b = SceneBuilder(be)
+    if name in ENV_MAPS:
+        if among:
+            b.light_source("point", from_=(3.0, 2.0, 1.0), I=(10.0, 8.0, 6.0))
+        _add_env(b, name)
+        _matte_ball(b)
+        return b, (1 if among else 0)
+    if name in TRIANGLES:
+        _add_triangle(b, TRIANGLES[name])
+        if variant == "dense":
+            _matte_ball(b)
+        return b, 0
+    if name in SPHERES:
+        _add_sphere(b, SPHERES[name])
+        return b, 0
+    if name == "point_alone":
+        b.light_source("point", from_=(1.0, 2.0, 3.0), I=(10.0, 8.0, 6.0))
+    elif name == "distant_alone":
+        b.light_source("distant", from_=(0.0, 0.0, 0.0), to=(1.0, -2.0, 0.5), L=(3.0, 2.0, 1.0))
+    else:                                             # point, distant, a constant infinite light and an emitting triangle in one scene
+        b.light_source("point", from_=(1.0, 2.0, 3.0), I=(10.0, 8.0, 6.0))
+        b.light_source("distant", from_=(0.0, 0.0, 0.0), to=(1.0, -2.0, 0.5), L=(3.0, 2.0, 1.0))
+        _add_env(b, "env_uniform")
+        _add_triangle(b, dict(P=[(4.0, 0.0, 0.0), (6.0, 0.0, 1.0), (5.0, 3.0, 0.0)]))
+    _matte_ball(b)
+    return b, (1 if name == "distant_among" else 0)
+
+
+def variants_of(name):
+    return list(ENV_VARIANTS) if name in SQUARE_ENVS else list(TRI_VARIANTS) if name in TRIANGLES else ["default"]
+
+
+ALL_NAMES = DELTAS + list(TRIANGLES) + list(SPHERES) + list(ENV_MAPS)
+
+
+class Hook:
+    """the light hook of one backend on one configuration.  The build knobs of a variant are read when the scene is created: they are set
+    through `monkeypatch` around create_scene alone (the oracle has no knobs)."""
+
+    def __init__(self, be, name, variant="default", among=False, monkeypatch=None):
+        self.be, self.name = be, name
+        self.builder, self.light = build(be, name, variant, among)
+        knobs = {**ENV_VARIANTS, **TRI_VARIANTS}[variant]
+        if be.is_oracle or monkeypatch is None:
+            assert be.is_oracle or not knobs
+            self.scene = self.builder.create_scene()
+        else:
+            with monkeypatch.context() as mp:
+                for k in ("FTN_ENV_CELLS", "FTN_NO_COARSE_CDF", "FTN_SREC"):
+                    mp.delenv(k, raising=False)
+                for k, v in knobs.items():
+                    mp.setenv(k, v)
+                self.scene = self.builder.create_scene()
+        self.fn = be.lib.orc_test_light if be.is_oracle else be.lib.ftn_test_light
+        self.fn.argtypes = A.TEST_LIGHT_ARGTYPES
+        self.fn.restype = C.c_int
+        self._desc = None
+
+    @property
+    def desc(self):
+        """the restatement's view of the light under test"""
+        if self._desc is None:
+            self._desc = R.describe(self.builder)[self.light]
+        return self._desc
+
+    def raw(self, rows, via_env0=0):
+        rows = np.ascontiguousarray(rows, f32).reshape(-1, NIN)
+        n = rows.shape[0]
+        out = np.empty((n, NOUT), f32)
+
+        def part(lo, hi):
+            return self.fn(self.scene.handle, self.light, int(via_env0), rows[lo:hi].ctypes.data_as(C.c_void_p), hi - lo, out[lo:hi].ctypes.data_as(C.c_void_p))
+        if self.be.is_oracle and n >= 65536:          # the oracle walks the rows on the calling thread: split them over a few
+            cuts = np.linspace(0, n, 9).astype(int)
+            with ThreadPoolExecutor(8) as ex:
+                rcs = list(ex.map(lambda k: part(cuts[k], cuts[k + 1]), range(8)))
+        else:
+            rcs = [part(0, n)]
+        for rc in rcs:
+            self.be.check(rc)
+        return out
+
+    def __call__(self, rows, via_env0=0):
+        return unpack(self.raw(rows, via_env0))
+
+
+def unpack(out):
+    return {k: out[:, c] for k, c in COLUMNS.items()}
+
+
+# ---------------------------------------------------------------- rows
+def unit(rng, n):
+    v = rng.normal(size=(n, 3))
+    return v / np.linalg.norm(v, axis=1, keepdims=True)
+
+
+def make_rows(p, wi, u, n=None, p_err=None, time=0.0):
+    p, wi, u = np.atleast_2d(p), np.atleast_2d(wi), np.atleast_2d(u)
+    m = max(len(p), len(wi), len(u))
+    rows = np.zeros((m, NIN), f32)
+    rows[:, 0:3] = p
+    rows[:, 3:6] = 0.0 if p_err is None else p_err
+    rows[:, 6:9] = (0.0, 0.0, 1.0) if n is None else n
+    rows[:, 9] = time
+    rows[:, 10:13] = wi
+    rows[:, 13:15] = u
+    return rows
+
+
+def light_frame(desc):
+    """-> (centre, size) of what the reference points are spread around"""
+    if desc["kind"] == "area":
+        s = desc["shape"]
+        if isinstance(s, R.Triangle):
+            c = s.p.mean(axis=0)
+            return c, float(np.max(np.linalg.norm(s.p - c, axis=1)))
+        return R.tf_point(s.o2w, np.zeros(3)), s.r * float(np.max(np.linalg.norm(s.o2w[:3, :3], axis=0)))
+    if desc["kind"] == "point":
+        return desc["p"], 1.0
+    return np.zeros(3), 1.0
+
+
+def random_rows(desc, seed, n):
+    """reference points spread around the light (for a sphere: 30 % outside, 40 % inside, 30 % on the surface with the surface's normal and
+    an error box a thousandth of the radius; from outside, one uniform sample in a hundred lies on the limb, where binary32 decides hit or miss), random normals (a tenth of them zero), error boxes of a few gamma(7) |p|, u in [0, 1)^2, wi half
+    random and half aimed at the light"""
+    rng = np.random.default_rng(seed)
+    centre, size = light_frame(desc)
+    p = centre + unit(rng, n) * (size * rng.uniform(0.5, 4.0, n))[:, None]
+    nrm = unit(rng, n)
+    p_err = np.abs(p) * (R.gamma(7) * rng.uniform(0.0, 4.0, (n, 1)))
+    if desc["kind"] == "area" and isinstance(desc["shape"], R.Sphere):
+        s = desc["shape"]
+        w = rng.random(n)
+        inside, on = w < 0.40, (w >= 0.40) & (w < 0.70)
+        obj = unit(rng, n) * s.r
+        p = np.where(inside[:, None], R.tf_point(s.o2w, obj * rng.uniform(0.0, 0.9, (n, 1))), p)
+        surf_n = R.normalize(obj @ s.o2w_inv[:3, :3]) * np.where(rng.random(n) < 0.5, -1.0, 1.0)[:, None]
+        p = np.where(on[:, None], R.tf_point(s.o2w, obj), p)
+        nrm = np.where(on[:, None], surf_n, nrm)
+        p_err = np.where(on[:, None], 1.0e-3 * s.r, p_err)
+        far_out = ~inside & ~on
+        p = np.where(far_out[:, None], centre + unit(rng, n) * (size * rng.uniform(1.2, 6.0, n))[:, None], p)
+    else:
+        nrm[rng.random(n) < 0.1] = 0.0
+    wi = unit(rng, n)
+    aimed = rng.random(n) < 0.5
+    if desc["kind"] == "area":
+        if isinstance(desc["shape"], R.Sphere):       # into the ball, not at its surface: a tenth of the surface is limb from where the point stands
+            target = R.tf_point(desc["shape"].o2w, unit(rng, n) * (0.9 * desc["shape"].r * rng.random((n, 1)) ** (1.0 / 3.0)))
+        else:
+            target = desc["shape"].sample(rng.random((n, 2)))["p"]
+        wi = np.where(aimed[:, None], R.normalize(target - p.astype(f32).astype(np.float64)), wi)
+    u = rng.random((n, 2)).astype(f32)
+    u = np.minimum(u, np.nextafter(f32(1.0), f32(0.0)))
+    return make_rows(p, wi, u, n=nrm, p_err=p_err, time=rng.random(n))
+
+
+def rel_err(got, want, floor=FLOOR):
+    got, want = np.asarray(got, np.float64), np.asarray(want, np.float64)
+    with np.errstate(all="ignore"):
+        e = np.abs(got - want) / np.maximum(np.abs(want), floor)
+    both_nan = np.isnan(got) & np.isnan(want)
+    both_inf = np.isinf(got) & (got == want)
+    e = np.where(both_nan | both_inf, 0.0, e)
+    return np.where(np.isnan(e), np.inf, e)          # NaN on one side only: an infinite error
+
+
+def bits(a):
+    return np.ascontiguousarray(a, f32).view(np.uint32)
+
+
+def same_bits_or_both_nan(a, b):
+    a, b = np.ascontiguousarray(a, f32), np.ascontiguousarray(b, f32)
+    return (a.view(np.uint32) == b.view(np.uint32)) | (np.isnan(a) & np.isnan(b))
+
+
+def undefined_by_the_reference(desc, rows, got, want):
+    """-> mask over (row, column) of what the reference's text does not define.  A triangle's edge functions are NaN for a ray with a NaN or an
+    overflowing origin or direction, and sign_differs (triangle.rs:428-434) then decides hit or miss by the NaNs' sign bits, which IEEE 754 leaves to
+    the implementation (x86 and the GPU differ, and so may two compilations for one of them).  There the pdf is the miss's 0 or the hit's NaN, on
+    either side; every other column is still compared.  Only a ray that is not finite to begin with can get there: the mask is confined to rows whose
+    direction (the input wi for light_pdf, the restated sample's wi for the other two) is not a finite non-zero vector or whose reference point is NaN,
+    infinite or beyond 1e18, and is empty for every other light."""
+    mask = np.zeros(got.shape, bool)
+    if desc["kind"] != "area" or not isinstance(desc["shape"], R.Triangle):
+        return mask
+    ev = R.evaluate(desc, rows)
+    r = np.asarray(rows, np.float64)
+    with np.errstate(all="ignore"):
+        bad_p = ~np.isfinite(r[:, 0:9]).all(axis=1) | (np.abs(r[:, 0:3]).max(axis=1) > 1.0e18)
+        bad_in = bad_p | ~np.isfinite(r[:, 10:13]).all(axis=1) | ~(np.abs(r[:, 10:13]).max(axis=1) > 0.0) | (np.abs(r[:, 10:13]).max(axis=1) > 1.0e18)
+        bad_s = bad_p | ~np.isfinite(ev["wi"]).all(axis=1)
+    either = lambda a: (a == 0.0) | np.isnan(a)
+    for col, rows_of in ((COLUMNS["pdf"], ev["nan_edges_s"] & bad_s), (COLUMNS["pdf_s"], ev["nan_edges_s"] & bad_s), (COLUMNS["pdf_in"], ev["nan_edges_in"] & bad_in)):
+        mask[:, col] = rows_of & either(got[:, col]) & either(want[:, col])
+    return mask
+
+
+# ---------------------------------------------------------------- layer 1: against the restatement
+def compare_with_restatement(hook, rows):
+    """-> (errors over the compared values, share of rows left out).  Asserts the discrete outcomes on the rows that are compared: a sample
+    accepted or pdf 0, hit or miss of pdf_from_ref; the CDF cell of an infinite light's sample, recovered from the returned wi.  A NaN on one side
+    only is an infinite error."""
+    want = R.evaluate(hook.desc, rows)
+    got = hook(rows)
+    ok = ~want["fragile"]
+    errs = []
+    if hook.desc["kind"] == "infinite":              # the cell: floor of (d0 nu, d1 nv) from wi, where that is 1e-3 of a cell inside and off the poles
+        x, y, sth = env_cell_coordinates(hook.desc, got["wi"])
+        with np.errstate(invalid="ignore"):
+            firm = ok & np.isfinite(x) & np.isfinite(y) & (np.abs(x - np.round(x)) >= 1.0e-3) & (np.abs(y - np.round(y)) >= 1.0e-3) & (sth >= 5.0e-3)
+        assert firm.mean() >= 0.9, (hook.name, firm.mean())           # (env_nan: every sample lies in row 0, a twentieth of them next to the pole)
+        cell = np.stack([np.floor(x[firm]), np.floor(y[firm])], axis=1).astype(np.int64)
+        assert np.array_equal(cell, want["cell"][firm]), (hook.name, int((cell != want["cell"][firm]).any(axis=1).sum()))
+    for key in ("pdf", "pdf_in", "pdf_s"):
+        k = ok & ~want.get("fragile_s", np.zeros(len(ok), bool)) if key == "pdf_s" else ok
+        zero_got, zero_want = got[key][k] == 0.0, want[key][k] == 0.0
+        assert np.array_equal(zero_got, zero_want), (hook.name, key, int((zero_got != zero_want).sum()))
+        errs.append(rel_err(got[key][k], want[key][k]))
+    # a bilinear lookup's rounding error is relative to the largest of the four texels it blends ((1 - ds) cancels next to a texel's centre), not to
+    # its result: the floor of that row is FLOOR x that texel (never below FLOOR)
+    for key in ("radiance", "wi", "p1_p", "p1_perr", "p1_n", "p1_time", "le"):
+        floor = FLOOR
+        if hook.desc["kind"] == "infinite" and key in ("radiance", "le"):
+            floor = FLOOR * np.maximum(1.0, want[key + "_scale"][ok])[:, None]
+        errs.append(rel_err(got[key][ok], want[key][ok], floor).ravel())
+    return np.concatenate(errs), 1.0 - ok.mean()
+
+
+# ---------------------------------------------------------------- layer 2: properties (no one's reading of the reference involved)
+def env_cell_coordinates(desc, wi):
+    """the continuous cell coordinates (x in [0, nu), y in [0, nv)) of world directions in an infinite light's map"""
+    env = desc["env"]
+    w = R.normalize(R.tf_vector(env.w2l, np.asarray(wi, np.float64)))
+    return R.spherical_phi(w) / (2.0 * PI) * env.distribution.nu, R.spherical_theta(w) / PI * env.distribution.nv, np.sqrt(np.maximum(0.0, 1.0 - w[:, 2] ** 2))
+
+
+def check_sample_pdf_agreement(hook, n=200000, seed=41):
+    """light_pdf(ref, s.wi) against s.pdf.  Area lights: bit for bit, both are pdf_from_ref on the same inputs.  Infinite lights: within TOL_MAX
+    wherever the sampled direction lies firmly inside a cell of the map (5e-4 of a cell from its inner edges): only there do the cell the sample
+    was drawn from and the cell the pdf derives from the direction have to be the same one.  Next to the poles (sin(theta) < 5e-3) the pdf's
+    theta = acos(z) has lost its digits (a relative 6e-8 / sin^2 in its sine).  The share of the rows left out for either reason is capped."""
+    rows = random_rows(hook.desc, seed, n)
+    o = hook(rows)
+    kind = hook.desc["kind"]
+    if kind == "area":
+        assert np.array_equal(bits(o["pdf_s"]), bits(o["pdf"])), hook.name
+        return 0.0
+    if kind != "infinite":
+        assert np.all(o["pdf"] == 1.0) and np.all(o["pdf_s"] == 0.0) and np.all(o["pdf_in"] == 0.0), hook.name
+        return 0.0
+    x, y, sth = env_cell_coordinates(hook.desc, o["wi"])
+    dist = hook.desc["env"].distribution
+    off_x = (np.abs(x - np.round(x)) >= 5.0e-4) | (np.round(x) <= 0) | (np.round(x) >= dist.nu)          # (the outer edges clamp: no other cell there)
+    off_y = (np.abs(y - np.round(y)) >= 5.0e-4) | (np.round(y) <= 0) | (np.round(y) >= dist.nv)
+    firm = off_x & off_y & (sth >= 5.0e-3)
+    left_out = 1.0 - firm.mean()
+    assert left_out <= MAX_FRAGILE_SHARE, (hook.name, left_out)
+    err = rel_err(o["pdf_s"][firm], o["pdf"][firm])
+    assert err.max() <= TOL_MAX, (hook.name, err.max())
+    return left_out
+
+
+def near_south_pole(desc, wi):
+    """directions within 1.4e-3 rad of the -z axis of an infinite light's map (see check_south_pole_quirk)"""
+    w = R.normalize(R.tf_vector(desc["env"].w2l, np.asarray(wi, np.float64)))
+    return w[:, 2] <= -(1.0 - 1.0e-6)
+
+
+def check_sanity(hook, n=200000, seed=42):
+    """radiance and pdf finite and >= 0 on finite inputs (but for the pdf of a direction at the south pole of an infinite light's map, which is
+    pinned apart); delta lights: pdf 1 from the sample, 0 from light_pdf; wi is a unit vector.
+    pdf == 0 means "no sample" to every caller, and they test it in three ways: `pdf > 0.0 && !radiance.is_black()` (integrator/mod.rs:322),
+    `radiance.is_black() || pdf == 0.0` (whitted.rs:47) and `light_pdf == 0.0` on the MIS side.  With every pdf finite and >= 0 the three decide
+    alike -- no NaN slips past `== 0.0`, no negative value fails `> 0.0` while passing `== 0.0` -- and what a caller that does go on consumes
+    (radiance, wi, p1) is finite on every row, those with pdf == 0 included.  For an area light pdf == 0 is a re-intersection that missed the
+    light: rows with pdf == 0 and those with pdf > 0 both occur, and the sample's pdf and light_pdf of its direction are 0 together."""
+    rows = random_rows(hook.desc, seed, n)
+    o = hook(rows)
+    if hook.desc["kind"] == "infinite":
+        south_in, south_s = near_south_pole(hook.desc, rows[:, 10:13]), near_south_pole(hook.desc, o["wi"])
+        assert south_s.mean() <= MAX_FRAGILE_SHARE and south_in.mean() <= MAX_FRAGILE_SHARE
+        o["pdf_in"], o["pdf_s"] = o["pdf_in"][~south_in], o["pdf_s"][~south_s]
+    for key in ("radiance", "pdf", "pdf_in", "pdf_s", "le", "wi", "p1_p", "p1_perr", "p1_n"):
+        assert np.all(np.isfinite(o[key])), (hook.name, key)
+    for key in ("radiance", "pdf", "pdf_in", "pdf_s", "le", "p1_perr"):
+        assert np.all(o[key] >= 0.0), (hook.name, key)
+    if hook.desc["kind"] in ("point", "distant"):
+        assert np.all(o["pdf"] == 1.0) and np.all(o["pdf_in"] == 0.0) and np.all(o["pdf_s"] == 0.0), hook.name
+    else:
+        assert (o["pdf"] > 0.0).any() and (o["pdf_in"] > 0.0).any(), hook.name
+    wl = np.linalg.norm(o["wi"].astype(np.float64), axis=1)
+    assert np.all(np.abs(wl - 1.0) <= 1.0e-5), hook.name
+    if hook.desc["kind"] == "area":
+        assert np.array_equal(o["pdf"] == 0.0, o["pdf_s"] == 0.0), hook.name
+        if hook.name not in ("tri_sliver",):          # (from ten sizes away every ray to a sample hits the sliver)
+            assert (o["pdf"] == 0.0).any() or isinstance(hook.desc["shape"], R.Triangle), hook.name
+        assert (o["pdf_in"] == 0.0).any() and (o["pdf_in"] > 0.0).any(), hook.name
+
+
+def check_south_pole_quirk(hook):
+    """infinite.rs:142-154 takes theta = acos(w.z) and tests theta.sin() == 0.0.  At w.z = -1 (any direction within 3.4e-4 rad of the map's -z axis,
+    after rounding) theta is binary32's pi, which lies ABOVE pi: its sine is -8.74e-8, not 0, and the pdf comes out NEGATIVE and huge, where the
+    north pole (theta = 0) gives the 0 the test is there for.  Reproduced, not fixed (found by the sanity property)."""
+    env = hook.desc["env"]
+    local = np.array([[0.0, 0.0, -1.0], [1.0e-4, 0.0, -1.0], [0.0, -2.0e-4, -1.0], [0.0, 0.0, 1.0]])
+    rows = make_rows([0.0, 0.0, 0.0], R.tf_vector(env.l2w, local), [0.5, 0.5])
+    o = hook(rows)
+    dist = env.distribution
+    phi = np.array([0.0, 0.0, 1.5 * PI])
+    iu = np.clip((phi / (2.0 * PI) * dist.nu).astype(int), 0, dist.nu - 1)
+    want = dist.func[dist.nv - 1, iu] / dist.marg.integral / (2.0 * PI * PI * np.sin(np.float64(f32(PI))))
+    assert np.all(want < -1.0e4) and np.all(o["pdf_in"][:3] < 0.0)
+    assert rel_err(o["pdf_in"][:3], want).max() <= TOL_MAX
+    assert o["pdf_in"][3] == 0.0
+
+
+HIST_N = 4000000
+HIST_CASES = ["env_sq2", "env_sq33", "env_sq40", "env_sq64", "env_sq128", "env_3x5", "env_64x33", "env_rotated", "env_plateau", "tri_plain", "tri_far", "sph_full", "sph_scaled"]
+
+
+def chi_square(counts, expect):
+    """Pearson chi-square of a histogram against expected counts that sum to the number of samples; cells below 5 expected samples are pooled.
+    -> (chi2, dof, the 1 - 1e-7 quantile by Wilson-Hilferty)"""
+    counts, expect = np.asarray(counts, np.float64).ravel(), np.asarray(expect, np.float64).ravel()
+    big = expect >= 5.0
+    obs, exp = list(counts[big]), list(expect[big])
+    if expect[~big].sum() >= 5.0:
+        obs.append(counts[~big].sum()); exp.append(expect[~big].sum())
+    else:
+        assert counts[~big].sum() <= 5.0 + 5.0 * np.sqrt(5.0)          # (next to nothing is expected there)
+    obs, exp = np.array(obs), np.array(exp)
+    chi2 = float(np.sum((obs - exp) ** 2 / exp))
+    dof = len(exp) - 1
+    return chi2, dof, float(wilson_hilferty(dof, 1.0e-7))
+
+
+def check_histogram(hook, seed=43):
+    """where the samples go.  Infinite light: the sampled directions binned into the map's own cells (blocks of 4 x 4 cells for 128^2); the expected
+    share of a cell is its function value over the sum, in binary64 from the texels -- exact, no quadrature.  Triangle: the sample's barycentric
+    coordinates mapped back to the unit square (sampling.rs:48-51 inverted), uniform there.  Sphere: (z, phi) in object space, uniform."""
+    desc = hook.desc
+    rng = np.random.default_rng(seed)
+    u = np.minimum(rng.random((HIST_N, 2)).astype(f32), np.nextafter(f32(1.0), f32(0.0)))
+    centre, size = light_frame(desc)
+    o = hook(make_rows(centre + np.array([0.3, 2.0, 1.1]) * size, [0.0, 0.0, 1.0], u))
+    if desc["kind"] == "infinite":
+        dist = desc["env"].distribution
+        x, y, _ = env_cell_coordinates(desc, o["wi"])
+        ix, iy = np.clip(x.astype(int), 0, dist.nu - 1), np.clip(y.astype(int), 0, dist.nv - 1)
+        blk = 4 if dist.nu * dist.nv > 5000 else 1
+        nbx, nby = dist.nu // blk, dist.nv // blk
+        counts = np.bincount((iy // blk) * nbx + ix // blk, minlength=nbx * nby)
+        func = dist.func.reshape(nby, blk, nbx, blk).sum(axis=(1, 3))
+        expect = HIST_N * func / func.sum()
+    elif isinstance(desc["shape"], R.Triangle):
+        p0, p1, p2 = desc["shape"].p
+        sol = np.linalg.lstsq(np.stack([p0 - p2, p1 - p2], axis=1), (o["p1_p"].astype(np.float64) - p2).T, rcond=None)[0]
+        b0, b1 = sol[0], sol[1]
+        u0, u1 = (1.0 - b0) ** 2, b1 / np.maximum(1.0 - b0, 1.0e-30)
+        k = 16
+        counts = np.bincount(np.clip((u0 * k).astype(int), 0, k - 1) * k + np.clip((u1 * k).astype(int), 0, k - 1), minlength=k * k)
+        expect = np.full(k * k, HIST_N / (k * k))
+    else:
+        s = desc["shape"]
+        obj = R.tf_point(s.w2o, o["p1_p"].astype(np.float64))
+        z = obj[:, 2] / s.r
+        phi = np.mod(np.arctan2(obj[:, 1], obj[:, 0]), 2.0 * PI)
+        k = 16
+        counts = np.bincount(np.clip(((z + 1.0) * 0.5 * k).astype(int), 0, k - 1) * k + np.clip((phi / (2.0 * PI) * k).astype(int), 0, k - 1), minlength=k * k)
+        expect = np.full(k * k, HIST_N / (k * k))
+    chi2, dof, quant = chi_square(counts, expect)
+    print("histogram %-14s chi2 %.1f dof %d quantile %.1f z %.2f" % (hook.name, chi2, dof, quant, (chi2 - dof) / np.sqrt(2.0 * dof)))
+    assert chi2 <= quant, (hook.name, chi2, dof, quant)
+    return chi2, dof, quant
+
+
+# ---- the estimator radiance * max(0, n . wi) / pdf integrates to a closed form
+EST_N = 1000000
+EST_CASES = ["tri_plain", "tri_reversed", "tri_flipped", "tri_far", "sph_full", "env_uniform", "env_sq33", "env_rotated"]
+
+
+def lambert_polygon(p, n, verts):
+    """irradiance per unit radiance of a polygon wholly above the horizon of (p, n): 1/2 |sum_i theta_i n . (v_i x v_i+1) / |v_i x v_i+1||"""
+    v = R.normalize(verts - p)
+    total = 0.0
+    for i in range(len(v)):
+        a, b = v[i], v[(i + 1) % len(v)]
+        c = np.cross(a, b)
+        total += np.arccos(np.clip(np.dot(a, b), -1.0, 1.0)) * np.dot(n, c / np.linalg.norm(c))
+    return 0.5 * abs(total)
+
+
+def env_irradiance(env, n, k):
+    """sum over a k x 2k midpoint grid in (theta, phi) of Le cos sin(theta) dtheta dphi, binary64"""
+    th = (np.arange(k) + 0.5) * PI / k
+    ph = (np.arange(2 * k) + 0.5) * PI / k
+    T, P = np.meshgrid(th, ph, indexing="ij")
+    local = np.stack([np.sin(T) * np.cos(P), np.sin(T) * np.sin(P), np.cos(T)], axis=-1).reshape(-1, 3)
+    world = R.tf_vector(env.l2w, local)
+    le, _ = env.Le(world)
+    cos = np.maximum(0.0, world @ n)
+    return (le * (cos * np.sin(T).ravel())[:, None]).sum(axis=0) * (PI / k) ** 2
+
+
+def check_estimator(hook, seed=44):
+    """-> (mean, analytic value, 5 sigma) per channel.  The reference point sees the emitting side of the whole light above its horizon."""
+    desc = hook.desc
+    rng = np.random.default_rng(seed)
+    u = np.minimum(rng.random((EST_N, 2)).astype(f32), np.nextafter(f32(1.0), f32(0.0)))
+    quad_check = None
+    if desc["kind"] == "infinite":
+        p = np.array([0.2, 0.1, -0.3])
+        n = R.normalize(np.array([0.3, -0.5, 0.8]))
+        if hook.name == "env_uniform":
+            want = PI * np.array([1.0, 2.0, 3.0])
+        else:
+            k = 16 * max(desc["env"].w, desc["env"].h)
+            want, coarse = env_irradiance(desc["env"], n, 2 * k), env_irradiance(desc["env"], n, k)
+            quad_check = np.abs(want - coarse)
+    else:
+        s = desc["shape"]
+        centre, size = light_frame(desc)
+        if isinstance(s, R.Triangle):
+            ng = R.normalize(np.cross(s.p[1] - s.p[0], s.p[2] - s.p[0]))
+            side = s.sample(np.array([[0.3, 0.3]]))["n"][0]             # the emitting side
+            p = centre + side * (1.5 * size) + np.cross(ng, s.p[1] - s.p[0]) * 0.2
+            n = R.normalize(centre - p + 0.3 * size * np.array([0.2, -0.1, 0.15]))
+            p = p.astype(f32).astype(np.float64)
+            want = lambert_polygon(p, n, s.p) * np.array(EMIT)
+        else:
+            d = 3.0 * s.r
+            away = R.normalize(np.array([0.4, 0.7, -0.6]))
+            p = (centre + away * d).astype(f32).astype(np.float64)
+            n = R.normalize(-away + 0.3 * R.normalize(np.cross(away, [0.0, 0.0, 1.0])))
+            dd = np.linalg.norm(centre - p)
+            want = PI * (s.r / dd) ** 2 * np.dot(n, (centre - p) / dd) * np.array(EMIT)         # pi L (R / d)^2 cos(theta)
+    o = hook(make_rows(p, [0.0, 0.0, 1.0], u, n=n))
+    pdf = o["pdf"].astype(np.float64)
+    cos = np.maximum(0.0, o["wi"].astype(np.float64) @ n)
+    with np.errstate(all="ignore"):
+        est = np.where((pdf > 0.0)[:, None], o["radiance"].astype(np.float64) * (cos / pdf)[:, None], 0.0)
+    mean = est.mean(axis=0)
+    five_sigma = 5.0 * est.std(axis=0) / np.sqrt(EST_N)
+    print("estimator %-14s mean %s analytic %s 5 sigma %s" % (hook.name, mean, want, five_sigma))
+    if quad_check is not None:
+        assert np.all(quad_check <= 0.1 * five_sigma), (hook.name, quad_check, five_sigma, "the quadrature has not converged")
+    assert np.all(np.abs(mean - want) <= five_sigma), (hook.name, mean, want, five_sigma)
+    return mean, want, five_sigma
+
+
+# ---- pinned reference quirks
+def check_far_side_sphere_quirk(hook):
+    """a sample on the far side of a sphere gets the pdf of the NEAR hit (pdf_from_ref re-intersects along wi and takes the first hit,
+    shapes/mod.rs:55-66) and radiance 0 (diffuse.rs:44-50: the far side faces away): reproduced, not fixed"""
+    s = hook.desc["shape"]
+    centre, _ = light_frame(hook.desc)
+    p = (centre + np.array([0.0, 0.0, 3.0 * s.r])).astype(f32)
+    rng = np.random.default_rng(45)
+    rows = make_rows(p, [0.1, 0.2, -0.97], rng.random((20000, 2)).astype(f32))
+    o = hook(rows)
+    want = R.evaluate(hook.desc, rows)
+    to_sample = o["p1_p"].astype(np.float64) - p
+    far = (np.linalg.norm(to_sample, axis=1) > np.sqrt(9.0 - 1.0) * s.r * 1.01) & ~want["fragile"]       # beyond the tangent distance
+    assert far.sum() > 5000
+    assert np.all(want["which_s"][far] == 0) and np.all(want["hit_s"][far])
+    assert np.all(o["radiance"][far] == 0.0) and np.all(o["pdf"][far] > 0.0)
+    assert rel_err(o["pdf"][far], want["pdf"][far]).max() <= TOL_MAX
+    # plain geometry: the first point of the line from p along wi on the sphere, its pdf t^2 / (|n . wi| 4 pi r^2), and it lies before the sample
+    wi = o["wi"][far].astype(np.float64)
+    pc = p.astype(np.float64) - centre
+    bq = wi @ pc
+    t = -bq - np.sqrt(bq * bq - (pc @ pc - s.r * s.r))
+    nrm = (pc + wi * t[:, None]) / s.r
+    near = t * t / (np.abs(dot3(nrm, wi)) * 4.0 * PI * s.r * s.r)
+    assert np.all(t < np.linalg.norm(to_sample[far], axis=1) * 0.999)
+    assert rel_err(o["pdf"][far], near).max() <= TOL_MAX
+
+
+def dot3(a, b): return np.sum(a * b, axis=1)
+
+
+def check_zero_map_pdf_quirk(hook):
+    """u.x = 1 on the plateau map ends in the row's last cell, whose function value is 0: map_pdf == 0, unimplemented!() in the reference
+    (infinite.rs:101-103), pdf 0 here"""
+    rows = make_rows([0.0, 0.0, 0.0], [0.0, 0.0, 1.0], [[1.0, 0.3], [1.0, 0.7], [2.0, 0.1]])
+    want = R.evaluate(hook.desc, rows)
+    assert np.all(want["unimplemented"]) and np.all(want["cell"][:, 0] == 64)
+    o = hook(rows)
+    assert np.all(o["pdf"] == 0.0) and np.all(np.isfinite(o["wi"]))
+
+
+def check_search_underflow_quirk(hook):
+    """u < 0 or NaN: not even cdf[0] = 0 is <= u, search_sorted's `first` is 0 and `(first - 1)` underflows a usize (sampling.rs:80): a panic in
+    a debug build of the reference, size - 2 -- the LAST cell -- after wrapping in a release one.  Here the search returns cell 0: pinned as what this
+    project does, not as the reference's behaviour."""
+    rows = make_rows([0.0, 0.0, 0.0], [0.0, 0.0, 1.0], [[-0.25, 0.3], [0.3, -0.25], [np.nan, 0.3], [0.3, np.nan]])
+    want = R.evaluate(hook.desc, rows)
+    assert np.all(want["underflow"])
+    assert np.all(want["cell"][[0, 2], 0] == 0) and np.all(want["cell"][[1, 3], 1] == 0)
+    o = hook(rows)
+    finite = [0, 1]                                   # (du = u - 0 is negative there: a direction just outside cell 0, still finite)
+    assert rel_err(o["wi"][finite], want["wi"][finite]).max() <= TOL_MAX
+    assert np.array_equal(np.isnan(o["wi"]), np.isnan(want["wi"]))
+
+
+def check_black_map_quirk(hook):
+    """an all-zero map: func_integral == 0 in every row and in the marginal (sampling.rs:95-100 then makes the CDFs linear), so
+    sample_continuous divides 0 by 0 (sampling.rs:129): map_pdf is NaN, passes the `== 0.0` test of infinite.rs:101 and the pdf is NaN, from
+    the sample and from pdf_incident_radiance alike; the radiance is 0.  Reproduced, not fixed (found by the restatement)."""
+    rows = random_rows(hook.desc, 46, 1000)
+    want = R.evaluate(hook.desc, rows)
+    o = hook(rows)
+    assert np.all(np.isnan(want["pdf"])) and np.all(np.isnan(o["pdf"]))
+    firm = ~want["fragile"]
+    assert np.all(np.isnan(o["pdf_in"][firm])) and np.all(o["radiance"] == 0.0) and np.all(o["le"] == 0.0)
+
+
+def check_refusals(be, via_env0_refused=True):
+    """null pointers, a light index out of range, via_env0 on a scene that is not lit by one infinite light alone; n == 0 is a no-op"""
+    h = Hook(be, "point_among")
+    rows = random_rows(h.desc, 3, 8)
+    out = np.full((8, NOUT), 7.0, f32)
+    pr, po = rows.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)
+    bad = [(None, 0, 0, pr, 8, po), (h.scene.handle, 0, 0, None, 8, po), (h.scene.handle, 0, 0, pr, 8, None), (h.scene.handle, -1, 0, pr, 8, po),
+           (h.scene.handle, 4, 0, pr, 8, po), (h.scene.handle, 10000, 0, pr, 8, po)]
+    if via_env0_refused:
+        bad.append((h.scene.handle, 2, 1, pr, 8, po))
+    codes = [h.fn(*args) for args in bad]
+    assert all(rc == A.FTN_ERR_INVALID_ARGUMENT for rc in codes), codes
+    assert np.all(out == 7.0)
+    assert h.fn(h.scene.handle, 0, 0, pr, 0, po) == A.FTN_OK and np.all(out == 7.0)
+    assert h.fn(h.scene.handle, 3, 0, pr, 8, po) == A.FTN_OK and not np.any(out == 7.0)
+    return codes
+
+
+# ---------------------------------------------------------------- the edge table (tests/test_light.py: bit for bit; tests/test_light_cpu.py: that it reaches its edges)
+def below(x): return np.nextafter(f32(x), f32(-np.inf))
+def above(x): return np.nextafter(f32(x), f32(np.inf))
+
+
+SPECIAL_U = [f32(0.0), below(1.0), f32(0.5), f32(1.0), above(1.0), f32(-0.25), f32(1.5), f32(1.0e30), f32(-1.0e30), f32(np.inf), f32(-np.inf), f32(np.nan)]
+CDF_WINDOW = 12         # binary32 neighbours on each side of a binary64 CDF entry: the binary32 entry itself is among them (asserted on the oracle)
+
+
+def window(values):
+    """every binary32 within CDF_WINDOW ulps of each value"""
+    out = []
+    for v in np.asarray(values, np.float64):
+        x = f32(v)
+        lo = x
+        for _ in range(CDF_WINDOW):
+            lo = below(lo)
+        for _ in range(2 * CDF_WINDOW + 1):
+            out.append(lo); lo = above(lo)
+    return np.array(out, f32)
+
+
+def env_cdf_rows(desc):
+    """-> (rows with u.y across every entry of the marginal CDF, rows with u.x across every entry of one conditional CDF, that conditional's row).
+    The reference point and wi are fixed; each entry comes with its binary32 neighbours."""
+    dist = desc["env"].distribution
+    row = dist.nv // 3
+    mid = f32(0.5 * (dist.marg.cdf[row] + dist.marg.cdf[row + 1]))
+    uy = window(dist.marg.cdf[np.isfinite(dist.marg.cdf)])
+    if not np.isfinite(dist.marg.cdf).all():          # a NaN texel: the marginal CDF is 0, NaN, NaN, ...: the search ends in row 0 whatever u.y is
+        row, mid = 0, f32(0.5)
+        uy = np.concatenate([uy, np.array([0.25, 0.75], f32)])
+    ux = window(dist.cond[row].cdf[np.isfinite(dist.cond[row].cdf)])
+    a = make_rows([0.1, 0.2, 0.3], [0.3, -0.5, 0.8], np.stack([np.full(len(uy), f32(0.37)), uy], axis=1))
+    b = make_rows([0.1, 0.2, 0.3], [0.3, -0.5, 0.8], np.stack([ux, np.full(len(ux), mid)], axis=1))
+    return a, b, row
+
+
+def edge_directions(desc):
+    """world-space wi: the poles of an infinite light's map, its seam, every cell edge, the axes, zero, NaN, infinities, overflowing and tiny lengths"""
+    big, tiny, nan, inf = 3.0e20, 1.0e-30, np.nan, np.inf
+    d = [(0, 0, 1), (0, 0, -1), (1, 0, 0), (-1, 0, 0), (0, 1, 0), (0, -1, 0), (0, 0, 0), (-0.0, -0.0, -0.0), (nan, 0, 1), (0, nan, 0), (nan, nan, nan),
+         (inf, 0, 0), (0, -inf, 1), (inf, inf, inf), (big, big, 0), (0, 0, big), (tiny, 0, 0), (0, tiny, tiny), (1, -0.0, 0), (1, tiny, 0), (1, -tiny, 0),
+         (1, 0, tiny), (tiny, tiny, 1), (0.6, 0.0, 0.8), (0.0, 0.6, -0.8)]
+    d = [np.array(v, np.float64) for v in d]
+    if desc["kind"] == "infinite":
+        env = desc["env"]
+        nu, nv = env.distribution.nu, env.distribution.nv
+        local = []
+        for i in range(nu + 1):                       # phi on every cell edge, three heights
+            for th in (0.3 * PI, 0.5 * PI, 0.9 * PI):
+                ph = 2.0 * PI * i / nu
+                local.append((np.sin(th) * np.cos(ph), np.sin(th) * np.sin(ph), np.cos(th)))
+        for j in range(nv + 1):                       # theta on every cell edge, two azimuths
+            for ph in (0.2, 4.0):
+                th = PI * j / nv
+                local.append((np.sin(th) * np.cos(ph), np.sin(th) * np.sin(ph), np.cos(th)))
+        local += [(0, 0, 1), (0, 0, -1), (1, 0, 0), (1, -1e-30, 0)]
+        d += list(R.tf_vector(env.l2w, np.array(local, np.float64)))
+    return np.array(d, np.float64).astype(f32)
+
+
+def edge_points(desc):
+    """reference points (p, n, p_err): on the light, in its plane, at its centre, 1e-30 and 3e20 away; n zero, along and against; p_err zero, usual, huge"""
+    centre, size = light_frame(desc)
+    # (no NaN point: the origin of its ray goes through next_float_up / next_float_down, err_float.rs:12-30, which add 1 to a NaN's BITS -- what comes
+    # out, a NaN or -0, depends on the payload, which IEEE 754 leaves to the implementation)
+    pts = [centre, centre + 1.0e-30, centre + np.array([3.0e20, 0.0, 0.0]), centre + np.array([0.0, -3.0e20, 3.0e20]), centre + np.array([0.3, 2.0, 1.1]) * size,
+           np.zeros(3)]
+    normal = np.array([0.0, 0.0, 1.0])
+    if desc["kind"] == "area":
+        s = desc["shape"]
+        if isinstance(s, R.Triangle):
+            p0, p1, p2 = s.p
+            normal = R.normalize(np.cross(p1 - p0, p2 - p0))
+            pts += [p0, p1, p2, 0.5 * (p0 + p1), 0.5 * (p1 + p2), 0.5 * (p2 + p0), centre + 3.0 * (p1 - p0), centre + 0.5 * (p0 - centre) + 2.0 * (p2 - p1),
+                    centre + normal * size, centre - normal * size, centre + normal * 1.0e-6 * size]
+        else:
+            on = R.tf_point(s.o2w, s.r * np.array([[0, 0, 1.0], [0, 0, -1.0], [1.0, 0, 0], [0.6, 0.0, 0.8], [0.0, -1.0, 0.0]]))
+            normal = R.normalize(on[3] - centre)
+            pts += list(on) + [centre + (on[3] - centre) * 3.0, centre + (on[3] - centre) * 0.5, centre + (on[0] - centre) * 1.000001]
+    out = []
+    for p in pts:
+        for n in (np.zeros(3), normal, -normal):
+            for p_err in (0.0, R.gamma(7) * np.abs(p), 1.0e10):
+                out.append((p, n, np.broadcast_to(p_err, 3)))
+    return out
+
+
+def edge_rows(desc):
+    dirs = edge_directions(desc)
+    centre, size = light_frame(desc)
+    us = [(a, b) for a in SPECIAL_U for b in SPECIAL_U]
+    rows = []
+    if desc["kind"] == "infinite":
+        a, b, _ = env_cdf_rows(desc)
+        rows += [a, b]
+        rows.append(make_rows([0.1, 0.2, 0.3], [0.3, -0.5, 0.8], np.array(us, f32)))
+        rows.append(make_rows([0.1, 0.2, 0.3], dirs, [0.5, 0.5]))
+        for p, n, p_err in edge_points(desc)[::4]:
+            rows.append(make_rows(p, dirs[:25], [0.3, 0.6], n=n, p_err=p_err))
+        return np.concatenate(rows)
+    pts = edge_points(desc)
+    aimed = []
+    if desc["kind"] == "area":
+        s = desc["shape"]
+        targets = list(s.p) + [0.5 * (s.p[0] + s.p[1]), s.p.mean(axis=0)] if isinstance(s, R.Triangle) else [centre, R.tf_point(s.o2w, [0.0, 0.0, s.r])]
+    else:
+        targets = [centre]
+    u_few = np.array([(0.0, 0.0), (below(1.0), below(1.0)), (0.5, 0.5), (0.0, 0.5), (1.0, 1.0), (np.nan, 0.5), (-1.0, 2.0), (0.25, below(1.0))], f32)
+    for p, n, p_err in pts:
+        with np.errstate(all="ignore"):
+            w = np.concatenate([dirs, np.array([R.normalize(t - p) for t in targets]).astype(f32), np.array([R.normalize(p - t) for t in targets[:1]]).astype(f32)])
+        for u in u_few:
+            rows.append(make_rows(p, w, u, n=n, p_err=p_err))
+    rows.append(make_rows(centre + np.array([0.3, 2.0, 1.1]) * size, [0.0, 0.0, 1.0], np.array(us, f32)))
+    return np.concatenate(rows)
+
+
+def check_env_table_reaches_its_edges(hook):
+    """on the oracle, for an infinite light: each window of consecutive binary32 around a CDF entry straddles the entry as the library holds it.  Just
+    below the entry the sample sits at the top of cell k - 1, at and above it at the bottom of cell k; the direction is the same either way, what
+    tells them apart is the pdf: pdf x 2 pi^2 sin(theta) x the marginal's integral is the function value of the cell the search ended in.  That cell
+    changes inside the window and not at its ends, so the entry itself and the floats just below and above it are in the table.
+    -> the entries checked (entries between two cells that both have a share and whose function values differ by more than 5 %)"""
+    desc = hook.desc
+    dist = desc["env"].distribution
+    a, b, row = env_cdf_rows(desc)
+    checked = []
+    width = 2 * CDF_WINDOW + 1
+    for rows, axis, cdf in ((a, 1, dist.marg.cdf), (b, 0, dist.cond[row].cdf)):
+        o = hook(rows)
+        x, y, sth = env_cell_coordinates(desc, o["wi"])
+        ident = o["pdf"].astype(np.float64) * 2.0 * PI * PI * sth * dist.marg.integral
+        n = len(cdf) - 1
+        for k in range(1, n):
+            if not (cdf[k] - cdf[k - 1] > 1.0e-4 / n and cdf[k + 1] - cdf[k] > 1.0e-4 / n):
+                continue                              # a plateau on one side: the search skips it
+            w = slice(k * width, (k + 1) * width)
+            assert np.all(np.abs((y if axis == 1 else x)[w] - k) < 0.01), (hook.name, axis, k)
+            if axis == 1:
+                other = np.clip(np.floor(x[w]).astype(int), 0, dist.nu - 1)
+                f_lo, f_hi = dist.func[k - 1, other], dist.func[k, other]
+            else:
+                f_lo, f_hi = dist.func[row, k - 1], dist.func[row, k]
+            if np.any(np.abs(f_lo - f_hi) <= 0.05 * np.maximum(f_lo, f_hi)):
+                continue
+            in_hi = np.abs(ident[w] - f_hi) < np.abs(ident[w] - f_lo)
+            first = int(np.argmax(in_hi))
+            assert in_hi.any() and not in_hi.all() and np.all(in_hi[first:]) and 1 <= first <= width - 2, (hook.name, axis, k, in_hi)
+            checked.append((axis, k))
+    return checked
