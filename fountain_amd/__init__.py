@@ -5,6 +5,15 @@ from .api import (Backend, DirectLightingIntegrator, Film, FountainError, PathIn
                   load_ply_ascii, make_rays, read_exr, write_exr)
 from .filters import Filter, render_filtered
 
-__all__ = ["Backend", "DirectLightingIntegrator", "Film", "Filter", "render_filtered", "FountainError", "PathIntegrator", "PbrtScene", "PerspectiveCamera",
+__all__ = ["Backend", "DirectLightingIntegrator", "Film", "Filter", "render_filtered", "DisplayParams", "write_png", "FountainError", "PathIntegrator", "PbrtScene", "PerspectiveCamera",
            "RandomSampler", "SamplerIntegrator", "Scene", "SceneBuilder", "Transform", "WhittedIntegrator", "default_backend",
            "film_resolve_device", "load_ply", "load_ply_ascii", "make_rays", "read_exr", "write_exr", "_abi"]
+
+
+def __getattr__(name):
+    # DisplayParams and write_png of fountain_amd.display, imported on first use: the module is also a program
+    # (python -m fountain_amd.display), which must not find itself imported already
+    if name in ("DisplayParams", "write_png"):
+        from . import display
+        return getattr(display, name)
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))

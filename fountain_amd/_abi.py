@@ -219,6 +219,31 @@ FTN_FILTER_TABLE_WIDTH = 16
 FTN_FILTER_MAX_RADIUS = 8.0
 FTN_FILTER_ABI_VERSION = 1  # include/fountain_hip_filter.h (an extension with a version of its own)
 
+
+
+class ftn_display_params(C.Structure):
+    """include/fountain_hip_display.h: parameters of the display stage (ftn_display_params_default fills the defaults)."""
+    _fields_ = [("tonemap", c_u32), ("transfer", c_u32), ("flags", c_u32), ("reserved", c_u32), ("ev", c_f), ("key", c_f), ("white", c_f),
+                ("gamma", c_f), ("p_lo", c_f), ("p_hi", c_f), ("min_ev", c_f), ("max_ev", c_f)]
+
+
+class ftn_display_info(C.Structure):
+    """include/fountain_hip_display.h: what ftn_display_exposure found (the scale, the window's mean log2 luminance, the four counts)."""
+    _fields_ = [("scale", c_f), ("flags", c_u32), ("avg_log2", C.c_double), ("count_bins", c_u32), ("count_invalid", c_u32),
+                ("count_below", c_u32), ("count_above", c_u32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+FTN_DISPLAY_TONEMAP_LINEAR, FTN_DISPLAY_TONEMAP_REINHARD, FTN_DISPLAY_TONEMAP_ACES, FTN_DISPLAY_TONEMAP_HABLE = range(4)
+FTN_DISPLAY_TRANSFER_SRGB, FTN_DISPLAY_TRANSFER_GAMMA, FTN_DISPLAY_TRANSFER_LINEAR = range(3)
+FTN_DISPLAY_DITHER, FTN_DISPLAY_AUTO_EXPOSURE = 1, 2
+FTN_DISPLAY_INFO_EMPTY = 1
+FTN_DISPLAY_HIST_BINS, FTN_DISPLAY_HIST_INVALID, FTN_DISPLAY_HIST_BELOW, FTN_DISPLAY_HIST_ABOVE, FTN_DISPLAY_HIST_WORDS = 384, 384, 385, 386, 388
+FTN_PNG_GAMA = 1
+FTN_DISPLAY_ABI_VERSION = 1  # include/fountain_hip_display.h (an extension with a version of its own)
+
 FTN_ABI_VERSION = 3          # include/fountain_hip.h; Backend() refuses a product library that reports another one
 
 # Expected sizes (bytes) -- asserted against the header by the C side's static_asserts and tests/test_abi.py
@@ -228,7 +253,7 @@ SIZES = {
     "ftn_film_desc": 32, "ftn_sampler_desc": 24, "ftn_integrator_desc": 16, "ftn_tile_range": 16,
     "ftn_render_options": 16, "ftn_stats": 152, "ftn_scene_memory": 96, "ftn_texture": 48, "ftn_image": 24, "ftn_material_textures": 32,
     "ftn_gbuffer_pixel": 48, "ftn_denoise_params": 32, "ftn_denoise_guided_params": 32, "ftn_moment_pixel": 16, "ftn_adaptive_params": 16, "ftn_adaptive_info": 24,
-    "ftn_temporal_pixel": 32, "ftn_temporal_params": 32, "ftn_filter_desc": 32,
+    "ftn_temporal_pixel": 32, "ftn_temporal_params": 32, "ftn_filter_desc": 32, "ftn_display_params": 48, "ftn_display_info": 32,
 }
 
 # Every function the header declares (name -> None); used by the symbol-export test.
@@ -307,3 +332,21 @@ FILTER_PROTOTYPES = {
     "ftn_filter_abi_version": [],
 }
 FILTER_FUNCTIONS = sorted(FILTER_PROTOTYPES)
+
+# Every function the extension header include/fountain_hip_display.h declares (kept apart from the lists above: the reference writes
+# linear OpenEXR files only, so these have no orc_* twin either), with its prototype: name -> (argument types, result type).
+_IMG = [C.c_void_p, c_i32, c_i32]
+DISPLAY_PROTOTYPES = {
+    "ftn_display_params_default": ([C.c_void_p], None),
+    "ftn_display_histogram": (_IMG + [C.c_void_p, c_i32], C.c_int),
+    "ftn_display_histogram_device": (_IMG + [C.c_void_p, C.c_void_p], C.c_int),
+    "ftn_display_histogram_cpu": (_IMG + [C.c_void_p], C.c_int),
+    "ftn_display_exposure": ([C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
+    "ftn_display_encode": (_IMG + [C.c_void_p, c_f, C.c_void_p, C.c_void_p, c_i32], C.c_int),
+    "ftn_display_encode_device": (_IMG + [C.c_void_p, c_f, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
+    "ftn_display_encode_cpu": (_IMG + [C.c_void_p, c_f, C.c_void_p, C.c_void_p], C.c_int),
+    "ftn_display": (_IMG + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, c_i32], C.c_int),
+    "ftn_png_write": ([C.c_char_p, C.c_void_p, c_u32, c_u32, c_u32], C.c_int),
+    "ftn_display_abi_version": ([], C.c_int),
+}
+DISPLAY_FUNCTIONS = sorted(DISPLAY_PROTOTYPES)

@@ -25,6 +25,11 @@ the same moments); --gbuffer, --denoise, --exact-stream and more than one GPU do
 sets the radius.  A wide filter mixes the samples of neighbouring pixels, so --gbuffer, --denoise, --denoise-guided, --variance and
 --adaptive, which assume that a pixel's samples are its own, are refused with it, as are --exact-stream and more than one GPU.
 Without the option the image is the reference's: a box of radius 0.5, whatever the file says.
+--png also writes <name>.png beside <name>.exr through the display stage (fountain_amd/display.py): --exposure EV (default 0) or
+--auto-exposure (from the image's luminance histogram), --tonemap {linear,reinhard,aces,hable} (default aces), --transfer
+{srgb,gamma,linear} (default srgb) with --gamma G, and --dither.  <name>_denoised.exr and <name>_denoised_guided.exr get a .png beside
+them too, encoded with the exposure of the main image so that they compare fairly; the G-buffer, variance and spp files get none.  The
+display options need --png, and --png renders on one GPU.  The OpenEXR files are the same bytes with and without it.
 """
 import argparse
 import sys
@@ -56,7 +61,19 @@ def main(argv=None):
     ap.add_argument("--pixel-filter", default=None, choices=["scene", "box", "triangle", "gaussian", "mitchell", "sinc"],
                     help="render through this reconstruction filter (scene: the file's PixelFilter statement)")
     ap.add_argument("--filter-width", type=float, nargs="+", default=None, metavar="X", help="with --pixel-filter: the filter's radius, X [Y]")
+    ap.add_argument("--png", action="store_true", help="also write <name>.png (and a .png beside each denoised image) through the display stage")
+    from .display import add_arguments as add_display_arguments, display_options_given
+    add_display_arguments(ap)
     opts = ap.parse_args(argv)
+    if not opts.png and display_options_given(opts):
+        print("error: %s belongs to --png" % ", ".join(display_options_given(opts)), file=sys.stderr)
+        return 2
+    if opts.gamma is not None and opts.transfer != "gamma":
+        print("error: --gamma belongs to --transfer gamma", file=sys.stderr)
+        return 2
+    if opts.png and opts.gpus is not None and opts.gpus > 1:
+        print("error: --png encodes on one GPU: leave out --gpus", file=sys.stderr)
+        return 2
     if opts.filter_width is not None and (opts.pixel_filter is None or len(opts.filter_width) > 2):
         print("error: --filter-width X [Y] belongs to --pixel-filter", file=sys.stderr)
         return 2
@@ -95,8 +112,8 @@ def main(argv=None):
         # started plainly: start the N ranks as a child process (before anything here has touched HIP) and hand back its exit code
         return spawn_ranks(opts.gpus, sys.argv[1:] if argv is None else list(argv), module="fountain_amd.render")
     world, rank = (env_world[0], env_world[1]) if env_world is not None else (1, 0)
-    if (opts.gbuffer or opts.denoise or opts.variance or opts.denoise_guided or opts.adaptive is not None or opts.pixel_filter is not None) and world > 1:
-        flag = "--gbuffer" if opts.gbuffer else "--denoise" if opts.denoise else "--variance" if opts.variance else \
+    if (opts.gbuffer or opts.denoise or opts.variance or opts.denoise_guided or opts.adaptive is not None or opts.pixel_filter is not None or opts.png) and world > 1:
+        flag = "--png" if opts.png else "--gbuffer" if opts.gbuffer else "--denoise" if opts.denoise else "--variance" if opts.variance else \
             "--denoise-guided" if opts.denoise_guided else "--adaptive" if opts.adaptive is not None else "--pixel-filter"
         print("error: %s renders on one GPU, not under a launcher of %d ranks" % (flag, world), file=sys.stderr)
         return 2
@@ -188,12 +205,19 @@ def main(argv=None):
     print("Completed rendering in %.3f s (%.1f Mrays/s%s)" % (dt, rays / dt / 1e6, " on rank 0 of %d" % world if world > 1 else ""), file=sys.stderr)
     img, (w, h) = film.into_spectrum_buffer()
     write_exr(filename, img, be)
+    png = PngWriter(be, opts, img) if opts.png else None
+    if png:
+        png.write(img, filename)
     if opts.gbuffer or opts.denoise or opts.denoise_guided:
         gb = write_gbuffer(be, scene, parsed.camera, film, sampler, filename, opts.gpu, write=opts.gbuffer)
         if opts.denoise:
-            write_denoised(be, img, gb, filename, opts.gpu)
+            out = write_denoised(be, img, gb, filename, opts.gpu)
+            if png:
+                png.write(out, denoised_path(filename))
         if opts.denoise_guided:
-            write_denoised_guided(be, img, gb, variance, filename, opts.gpu)
+            out = write_denoised_guided(be, img, gb, variance, filename, opts.gpu)
+            if png:
+                png.write(out, denoised_guided_path(filename))
     if opts.adaptive is not None:
         import numpy as np
         path = spp_path(filename)
@@ -259,6 +283,7 @@ def write_denoised(be, img, gb12, filename, device):
     path = denoised_path(filename)
     write_exr(path, out, be)
     print("denoised: %s (%.1f ms)" % (path, (time.time() - t0) * 1e3), file=sys.stderr)
+    return out
 
 
 def write_denoised_guided(be, img, gb12, var4, filename, device):
@@ -270,6 +295,31 @@ def write_denoised_guided(be, img, gb12, var4, filename, device):
     path = denoised_guided_path(filename)
     write_exr(path, out, be)
     print("denoised (variance-guided): %s (%.1f ms)" % (path, (time.time() - t0) * 1e3), file=sys.stderr)
+    return out
+
+
+def png_path(exr_name):
+    """out.exr -> out.png"""
+    return (exr_name[:-4] if exr_name.endswith(".exr") else exr_name) + ".png"
+
+
+class PngWriter:
+    """--png: the display parameters of the command line and the exposure of the main image, which every image written beside it shares."""
+
+    def __init__(self, be, opts, main_img):
+        from . import display as D
+        self.be, self.device = be, opts.gpu
+        self.params = D.params_from_arguments(be, opts)
+        hist = D.histogram(be, main_img, device=opts.gpu) if opts.auto_exposure else None
+        self.info = D.exposure(be, hist, self.params)
+        print("display: scale %.6g%s" % (self.info["scale"], " (automatic, mean log2 luminance %.4f)" % self.info["avg_log2"] if opts.auto_exposure else ""),
+              file=sys.stderr)
+
+    def write(self, img, exr_name):
+        from . import display as D
+        path = png_path(exr_name)
+        D.write_png(path, D.encode(self.be, img, self.info["scale"], self.params, device=self.device), self.be, self.params.png_gamma)
+        print("png: %s" % path, file=sys.stderr)
 
 
 if __name__ == "__main__":
