@@ -5,7 +5,7 @@ from .api import (Backend, DirectLightingIntegrator, Film, FountainError, PathIn
                   load_ply_ascii, make_rays, read_exr, write_exr)
 from .filters import Filter, render_filtered
 
-__all__ = ["Backend", "DirectLightingIntegrator", "Film", "Filter", "render_filtered", "DisplayParams", "write_png", "FountainError", "PathIntegrator", "PbrtScene", "PerspectiveCamera",
+__all__ = ["Backend", "DirectLightingIntegrator", "Film", "Filter", "render_filtered", "DisplayParams", "write_png", "BloomParams", "FountainError", "PathIntegrator", "PbrtScene", "PerspectiveCamera",
            "RandomSampler", "SamplerIntegrator", "Scene", "SceneBuilder", "Transform", "WhittedIntegrator", "default_backend",
            "film_resolve_device", "load_ply", "load_ply_ascii", "make_rays", "read_exr", "write_exr", "_abi"]
 
@@ -16,4 +16,7 @@ def __getattr__(name):
     if name in ("DisplayParams", "write_png"):
         from . import display
         return getattr(display, name)
+    if name == "BloomParams":                    # likewise (python -m fountain_amd.bloom)
+        from . import bloom
+        return bloom.BloomParams
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -244,6 +244,17 @@ FTN_DISPLAY_HIST_BINS, FTN_DISPLAY_HIST_INVALID, FTN_DISPLAY_HIST_BELOW, FTN_DIS
 FTN_PNG_GAMA = 1
 FTN_DISPLAY_ABI_VERSION = 1  # include/fountain_hip_display.h (an extension with a version of its own)
 
+
+class ftn_bloom_params(C.Structure):
+    """include/fountain_hip_bloom.h: parameters of the bloom stage (ftn_bloom_params_default fills the defaults)."""
+    _fields_ = [("levels", c_i32), ("flags", c_u32), ("strength", c_f), ("scatter", c_f), ("threshold", c_f), ("knee", c_f), ("clamp_max", c_f),
+                ("reserved", c_u32)]
+
+
+FTN_BLOOM_KARIS = 1
+FTN_BLOOM_MAX_LEVELS = 12
+FTN_BLOOM_ABI_VERSION = 1    # include/fountain_hip_bloom.h (an extension with a version of its own)
+
 FTN_ABI_VERSION = 3          # include/fountain_hip.h; Backend() refuses a product library that reports another one
 
 # Expected sizes (bytes) -- asserted against the header by the C side's static_asserts and tests/test_abi.py
@@ -254,6 +265,7 @@ SIZES = {
     "ftn_render_options": 16, "ftn_stats": 152, "ftn_scene_memory": 96, "ftn_texture": 48, "ftn_image": 24, "ftn_material_textures": 32,
     "ftn_gbuffer_pixel": 48, "ftn_denoise_params": 32, "ftn_denoise_guided_params": 32, "ftn_moment_pixel": 16, "ftn_adaptive_params": 16, "ftn_adaptive_info": 24,
     "ftn_temporal_pixel": 32, "ftn_temporal_params": 32, "ftn_filter_desc": 32, "ftn_display_params": 48, "ftn_display_info": 32,
+    "ftn_bloom_params": 32,
 }
 
 # Every function the header declares (name -> None); used by the symbol-export test.
@@ -350,3 +362,15 @@ DISPLAY_PROTOTYPES = {
     "ftn_display_abi_version": ([], C.c_int),
 }
 DISPLAY_FUNCTIONS = sorted(DISPLAY_PROTOTYPES)
+
+# Every function the extension header include/fountain_hip_bloom.h declares (kept apart from the lists above: the reference writes
+# linear OpenEXR files only, so these have no orc_* twin either), with its prototype: name -> (argument types, result type).
+BLOOM_PROTOTYPES = {
+    "ftn_bloom_params_default": ([C.c_void_p], None),
+    "ftn_bloom": (_IMG + [C.c_void_p, C.c_void_p, c_i32], C.c_int),
+    "ftn_bloom_workspace_size": ([c_i32, c_i32, c_i32, C.c_void_p], C.c_int),
+    "ftn_bloom_device": (_IMG + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
+    "ftn_bloom_cpu": (_IMG + [C.c_void_p, C.c_void_p], C.c_int),
+    "ftn_bloom_abi_version": ([], C.c_int),
+}
+BLOOM_FUNCTIONS = sorted(BLOOM_PROTOTYPES)

@@ -15,7 +15,8 @@ float32 (ftn_film_resolve).  The *_cpu calls are the host twins, bit-identical t
 only, so the CPU oracle has no twin of these calls.
 
   python -m fountain_amd.display in.exr -o out.png [--exposure EV | --auto-exposure] [--tonemap T] [--transfer T] [--gamma G] [--dither]
-converts an existing OpenEXR file.
+converts an existing OpenEXR file.  --bloom [STRENGTH] (with --bloom-levels, --bloom-scatter, --bloom-threshold, --bloom-knee and
+--bloom-karis) blooms the linear image first (fountain_amd/bloom.py); the histogram, and so the automatic exposure, is the bloomed image's.
 """
 import argparse
 import ctypes as C
@@ -225,7 +226,12 @@ def main(argv=None):
     ap.add_argument("-o", "--output", default=None, help="the PNG file (default: the input's name with .png)")
     ap.add_argument("--gpu", type=int, default=0)
     add_arguments(ap)
+    from . import bloom as B
+    B.add_arguments(ap)
     opts = ap.parse_args(argv)
+    if B.refusal(opts):
+        print("error: %s" % B.refusal(opts), file=sys.stderr)
+        return 2
     out = opts.output or (opts.image[:-4] if opts.image.endswith(".exr") else opts.image) + ".png"
     if not out.endswith(".png"):
         print("error: the output must be a .png file", file=sys.stderr)
@@ -235,7 +241,10 @@ def main(argv=None):
         return 2
     be = default_backend()
     p = params_from_arguments(be, opts)
-    rgba8, info = display(be, read_exr(opts.image, be), p, device=opts.gpu)
+    img = read_exr(opts.image, be)
+    if opts.bloom is not None:
+        img = B.bloom(be, img, B.params_from_arguments(be, opts), device=opts.gpu)
+    rgba8, info = display(be, img, p, device=opts.gpu)
     write_png(out, rgba8, be, p.png_gamma)
     print("display: %s (scale %.6g)" % (out, info["scale"]), file=sys.stderr)
     return 0

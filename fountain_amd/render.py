@@ -30,6 +30,11 @@ Without the option the image is the reference's: a box of radius 0.5, whatever t
 {srgb,gamma,linear} (default srgb) with --gamma G, and --dither.  <name>_denoised.exr and <name>_denoised_guided.exr get a .png beside
 them too, encoded with the exposure of the main image so that they compare fairly; the G-buffer, variance and spp files get none.  The
 display options need --png, and --png renders on one GPU.  The OpenEXR files are the same bytes with and without it.
+--bloom [STRENGTH] (default 0.04) blooms the linear image in front of the display stage (fountain_amd/bloom.py) with --bloom-levels N,
+--bloom-scatter S, --bloom-threshold T, --bloom-knee K and --bloom-karis, and writes it as <name>_bloom.exr; <name>.png is then the
+bloomed image's, its histogram and so the automatic exposure included, and the denoised images' .png files are bloomed too before they
+are encoded at that exposure.  <name>.exr and every other file stay the same bytes.  --bloom needs --png and one GPU, and its
+sub-options need --bloom.
 """
 import argparse
 import sys
@@ -64,7 +69,15 @@ def main(argv=None):
     ap.add_argument("--png", action="store_true", help="also write <name>.png (and a .png beside each denoised image) through the display stage")
     from .display import add_arguments as add_display_arguments, display_options_given
     add_display_arguments(ap)
+    from . import bloom as B
+    B.add_arguments(ap)
     opts = ap.parse_args(argv)
+    if B.refusal(opts):
+        print("error: %s" % B.refusal(opts), file=sys.stderr)
+        return 2
+    if opts.bloom is not None and not opts.png:
+        print("error: --bloom belongs to --png: it is applied in front of the display stage", file=sys.stderr)
+        return 2
     if not opts.png and display_options_given(opts):
         print("error: %s belongs to --png" % ", ".join(display_options_given(opts)), file=sys.stderr)
         return 2
@@ -205,19 +218,25 @@ def main(argv=None):
     print("Completed rendering in %.3f s (%.1f Mrays/s%s)" % (dt, rays / dt / 1e6, " on rank 0 of %d" % world if world > 1 else ""), file=sys.stderr)
     img, (w, h) = film.into_spectrum_buffer()
     write_exr(filename, img, be)
-    png = PngWriter(be, opts, img) if opts.png else None
+    bloom_params = B.params_from_arguments(be, opts) if opts.bloom is not None else None
+    bloomed = (lambda a: B.bloom(be, a, bloom_params, device=opts.gpu)) if bloom_params else (lambda a: a)
+    shown = bloomed(img)
+    if bloom_params:
+        write_exr(bloom_path(filename), shown, be)
+        print("bloom: %s (strength %.6g, %d levels)" % (bloom_path(filename), bloom_params.desc.strength, bloom_params.desc.levels), file=sys.stderr)
+    png = PngWriter(be, opts, shown) if opts.png else None
     if png:
-        png.write(img, filename)
+        png.write(shown, filename)
     if opts.gbuffer or opts.denoise or opts.denoise_guided:
         gb = write_gbuffer(be, scene, parsed.camera, film, sampler, filename, opts.gpu, write=opts.gbuffer)
         if opts.denoise:
             out = write_denoised(be, img, gb, filename, opts.gpu)
             if png:
-                png.write(out, denoised_path(filename))
+                png.write(bloomed(out), denoised_path(filename))
         if opts.denoise_guided:
             out = write_denoised_guided(be, img, gb, variance, filename, opts.gpu)
             if png:
-                png.write(out, denoised_guided_path(filename))
+                png.write(bloomed(out), denoised_guided_path(filename))
     if opts.adaptive is not None:
         import numpy as np
         path = spp_path(filename)
@@ -252,6 +271,12 @@ def variance_path(filename):
     """out.exr -> out_variance.exr"""
     base = filename[:-4] if filename.endswith(".exr") else filename
     return "%s_variance.exr" % base
+
+
+def bloom_path(filename):
+    """out.exr -> out_bloom.exr"""
+    base = filename[:-4] if filename.endswith(".exr") else filename
+    return "%s_bloom.exr" % base
 
 
 def spp_path(filename):
