@@ -765,6 +765,15 @@ class Scene:
         self.be.call("intersect_full", *args)
         return out
 
+    def test_interaction(self, rows):
+        """the surface-interaction test hook (ftn_test_interaction / orc_test_interaction): rows [n, 32] -> [n, 68], layouts in fountain_hip.h"""
+        rows = np.ascontiguousarray(rows, dtype=np.float32).reshape(-1, A.FTN_TEST_INTERACTION_IN)
+        out = np.empty((rows.shape[0], A.FTN_TEST_INTERACTION_OUT), np.float32)
+        fn = self.be.fn("test_interaction")
+        fn.argtypes = A.TEST_INTERACTION_ARGTYPES
+        self.be.check(fn(self.handle, _fptr(rows), rows.shape[0], _fptr(out)))
+        return out
+
 
 PRIM_DTYPE = np.dtype([("k", "<u4"), ("i", "<u4"), ("m", "<i4"), ("a", "<i4")])
 NODE_DTYPE = np.dtype([("bmin", "<f4", 3), ("bmax", "<f4", 3), ("idx", "<u4"), ("n_prims", "<u2"), ("axis", "u1"), ("is_leaf", "u1")])
@@ -799,6 +808,15 @@ class PerspectiveCamera:
         be.call("camera_perspective", C.byref(camera_to_world.raw), (C.c_int32 * 2)(xres, yres),
                 (C.c_float * 4)(*[float(x) for x in screen_window]), (C.c_float * 2)(*shutter),
                 lens_radius, focal_dist, fov, C.byref(self.desc))
+
+    def test_rays(self, spp, rows):
+        """the camera test hook (ftn_test_camera / orc_test_camera): rows [n, 8] = p_film, p_lens, time -> [n, 20], layouts in fountain_hip.h"""
+        rows = np.ascontiguousarray(rows, dtype=np.float32).reshape(-1, A.FTN_TEST_CAMERA_IN)
+        out = np.empty((rows.shape[0], A.FTN_TEST_CAMERA_OUT), np.float32)
+        fn = self.be.fn("test_camera")
+        fn.argtypes = A.TEST_CAMERA_ARGTYPES
+        self.be.check(fn(C.addressof(self.desc), int(spp), _fptr(rows), rows.shape[0], _fptr(out)))
+        return out
 
     @classmethod
     def look_at(cls, be, eye, look, up, full_resolution, **kw):

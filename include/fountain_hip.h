@@ -488,6 +488,25 @@ int ftn_test_bsdf(const ftn_scene* scene, int32_t material, uint32_t flags, int 
 #define FTN_TEST_LIGHT_IN 15
 #define FTN_TEST_LIGHT_OUT 24
 int ftn_test_light(const ftn_scene* scene, int32_t light, int via_env0, const float* rows_in, size_t n, float* rows_out);
+/* Surface-interaction hook: ONE primitive's intersection (Triangle::intersect / Sphere::intersect, bypassing the BVH as Shape::pdf_from_ref
+ * does), compute_tex_differentials, SurfaceHit::spawn_ray and the differentials of a specular bounce ON THE DEVICE, as the shade kernels call
+ * them.  rows_in (HOST memory), 32 floats per row: [0..2] ray origin, [3..5] direction, [6] t_max, [7] time, [8] the BITS of the BVH-ordered
+ * primitive index (an int32), [9] != 0: the ray carries a differential, [10..12] rx origin, [13..15] ry origin, [16..18] rx direction,
+ * [19..21] ry direction, [22..24] the outgoing direction wi of the bounce, [25] the BSDF's eta, [26] != 0: reflect, 0: transmit, [27..31] unused.
+ * rows_out, 68 floats per row, all 0 on a miss: [0] 1 = hit, [1] t, [2..4] barycentrics (0 for a sphere), [5..7] p, [8..10] p_err, [11..13] n,
+ * [14] time, [15..17] wo, [18..20] shading normal, [21..23] shading dpdu, [24] [25] the BITS of the material and area-light indices (-1: none),
+ * [26..27] uv, [28..30] dpdu, [31..33] dpdv, [34..36] shading dndu, [37..39] shading dndv, [40..42] dpdx, [43..45] dpdy, [46..49] dudx dvdx
+ * dudy dvdy, [50..52] origin of spawn_ray(wi), [53] its t_max, [54..65] rx origin, ry origin, rx direction, ry direction of the bounced
+ * differential (0 without one), [66..67] 0.  A primitive index outside the scene is refused before anything runs.  n == 0 does nothing. */
+#define FTN_TEST_INTERACTION_IN 32
+#define FTN_TEST_INTERACTION_OUT 68
+int ftn_test_interaction(const ftn_scene* scene, const float* rows_in, size_t n, float* rows_out);
+/* Camera hook: PerspectiveCamera::generate_ray_differential and scale_differentials(1 / sqrt(spp)) ON THE DEVICE.  rows_in, 8 floats per
+ * row: [0..1] p_film, [2..3] p_lens, [4] time in [0, 1], [5..7] unused.  rows_out, 20 floats per row: [0..2] origin, [3..5] direction,
+ * [6] t_max, [7] time, [8..10] rx origin, [11..13] ry origin, [14..16] rx direction, [17..19] ry direction.  n == 0 does nothing. */
+#define FTN_TEST_CAMERA_IN 8
+#define FTN_TEST_CAMERA_OUT 20
+int ftn_test_camera(const ftn_camera_desc* camera, uint32_t spp, const float* rows_in, size_t n, float* rows_out);
 
 /* ------------------------------------------------------------------ misc */
 const char* ftn_last_error(void);

@@ -306,6 +306,15 @@ void orc_kat_camera_ray_differential(const ftn_camera_desc* cam, const float sam
     }
     out[18] = si.tex_diffs.dudx; out[19] = si.tex_diffs.dvdx; out[20] = si.tex_diffs.dudy; out[21] = si.tex_diffs.dvdy;
 }
+// t_max and time of the same ray (Ray::transform shifts t_max, transform.rs:307-322): out = t_max, time
+void orc_kat_camera_ray_full(const ftn_camera_desc* cam, const float sample5[5], float out[2]) {
+    Camera c; c.camera_to_world = from_abi(&cam->camera_to_world); c.raster_to_camera = from_abi(&cam->raster_to_camera);
+    c.shutter_open = cam->shutter_open; c.shutter_close = cam->shutter_close; c.lens_radius = cam->lens_radius; c.focal_dist = cam->focal_dist;
+    c.dx_camera = Vec3(cam->dx_camera[0], cam->dx_camera[1], cam->dx_camera[2]); c.dy_camera = Vec3(cam->dy_camera[0], cam->dy_camera[1], cam->dy_camera[2]);
+    CameraSample cs; cs.p_film = Vec2(sample5[0], sample5[1]); cs.p_lens = Vec2(sample5[2], sample5[3]); cs.time = sample5[4];
+    Float w; RayDifferential rd = c.generate_ray_differential(cs, &w);
+    out[0] = rd.ray.t_max; out[1] = rd.ray.time;
+}
 // SurfaceHit::spawn_ray (interaction.rs:22-30) from p, p_err, n along d: out = the ray's 8 floats (o, d, t_max, time 0)
 void orc_kat_spawn_ray(const float p[3], const float p_err[3], const float n[3], const float d[3], float out8[8]) {
     SurfaceHit h; h.p = Vec3(p[0], p[1], p[2]); h.p_err = Vec3(p_err[0], p_err[1], p_err[2]); h.n = Vec3(n[0], n[1], n[2]); h.time = 0.0f;
@@ -418,6 +427,59 @@ int orc_test_light(const orc_scene* s, int32_t light, int /*via_env0*/, const fl
         o[13] = ls.p1.n.x; o[14] = ls.p1.n.y; o[15] = ls.p1.n.z; o[16] = ls.p1.time;
         o[17] = L.pdf_incident_radiance(ref, wi); o[18] = L.pdf_incident_radiance(ref, ls.wi);
         o[19] = le[0]; o[20] = le[1]; o[21] = le[2]; o[22] = 0.0f; o[23] = 0.0f;
+    }
+    return FTN_OK;
+}
+// ---- surface interactions and cameras: the twins of ftn_test_interaction / ftn_test_camera (fountain_hip.h has the row layouts)
+int orc_test_interaction(const orc_scene* s, const float* in32, size_t n, float* out68) {
+    if (!s || !in32 || !out68) return fail(FTN_ERR_INVALID_ARGUMENT, "null argument");
+    const std::vector<Primitive>& prims = s->data.bvh.prims;
+    for (size_t i = 0; i < n; i++) { uint32_t prim; memcpy(&prim, in32 + 32 * i + 8, 4); if (prim >= prims.size()) return fail(FTN_ERR_INVALID_ARGUMENT, "primitive index out of range"); }
+    for (size_t i = 0; i < n; i++) {
+        const float* r = in32 + 32 * i; float* o = out68 + 68 * i;
+        for (int k = 0; k < 68; k++) o[k] = 0.0f;
+        uint32_t prim; memcpy(&prim, r + 8, 4);
+        RayDifferential rd; rd.ray = ray_from(r); rd.has_diff = r[9] != 0.0f;
+        rd.diff.rx_origin = Vec3(r[10], r[11], r[12]); rd.diff.ry_origin = Vec3(r[13], r[14], r[15]);
+        rd.diff.rx_dir = Vec3(r[16], r[17], r[18]); rd.diff.ry_dir = Vec3(r[19], r[20], r[21]);
+        const Vec3 wi(r[22], r[23], r[24]); const Float eta = r[25]; const bool reflect = r[26] != 0.0f;
+        Float t; SurfaceInteraction si;
+        if (!prims[prim].shape->intersect(rd.ray, &t, &si)) continue;
+        si.compute_tex_differentials(rd);
+        const Ray out = si.hit.spawn_ray(wi);
+        const int32_t mat = prims[prim].material, light = prims[prim].light;
+        o[0] = 1.0f; o[1] = t; o[2] = si.bary.x; o[3] = si.bary.y; o[4] = si.bary.z;
+        const Vec3 a[] = {si.hit.p, si.hit.p_err, si.hit.n};
+        for (int k = 0; k < 3; k++) for (int c = 0; c < 3; c++) o[5 + 3 * k + c] = a[k][c];
+        o[14] = si.hit.time;
+        const Vec3 b[] = {si.wo, si.shading_n, si.shading_geom.dpdu};
+        for (int k = 0; k < 3; k++) for (int c = 0; c < 3; c++) o[15 + 3 * k + c] = b[k][c];
+        memcpy(o + 24, &mat, 4); memcpy(o + 25, &light, 4);
+        o[26] = si.uv.x; o[27] = si.uv.y;
+        const Vec3 e[] = {si.geom.dpdu, si.geom.dpdv, si.shading_geom.dndu, si.shading_geom.dndv, si.tex_diffs.dpdx, si.tex_diffs.dpdy};
+        for (int k = 0; k < 6; k++) for (int c = 0; c < 3; c++) o[28 + 3 * k + c] = e[k][c];
+        o[46] = si.tex_diffs.dudx; o[47] = si.tex_diffs.dvdx; o[48] = si.tex_diffs.dudy; o[49] = si.tex_diffs.dvdy;
+        o[50] = out.origin.x; o[51] = out.origin.y; o[52] = out.origin.z; o[53] = out.t_max;
+        if (rd.has_diff) {
+            const Differential d = specular_differential(reflect, rd.diff, si, wi, eta);
+            const Vec3 v[] = {d.rx_origin, d.ry_origin, d.rx_dir, d.ry_dir};
+            for (int k = 0; k < 4; k++) for (int c = 0; c < 3; c++) o[54 + 3 * k + c] = v[k][c];
+        }
+    }
+    return FTN_OK;
+}
+int orc_test_camera(const ftn_camera_desc* cam, uint32_t spp, const float* in8, size_t n, float* out20) {
+    if (!cam || !in8 || !out20) return fail(FTN_ERR_INVALID_ARGUMENT, "null argument");
+    if (spp == 0) return fail(FTN_ERR_INVALID_ARGUMENT, "samples per pixel must be positive");
+    for (size_t i = 0; i < n; i++) {
+        float o22[22], t8[2];
+        orc_kat_camera_ray_differential(cam, in8 + 8 * i, spp, nullptr, o22);
+        orc_kat_camera_ray_full(cam, in8 + 8 * i, t8);
+        float* o = out20 + 20 * i;
+        for (int k = 0; k < 6; k++) o[k] = o22[k];
+        o[6] = t8[0]; o[7] = t8[1];
+        // rx_origin rx_dir ry_origin ry_dir -> rx_origin ry_origin rx_dir ry_dir
+        for (int c = 0; c < 3; c++) { o[8 + c] = o22[6 + c]; o[11 + c] = o22[12 + c]; o[14 + c] = o22[9 + c]; o[17 + c] = o22[15 + c]; }
     }
     return FTN_OK;
 }

@@ -322,6 +322,32 @@ inline Spectrum path_li(const Integrator& it, RayDifferential& ray, const SceneD
     return path_radiance;
 }
 
+// the differentials of a specular bounce, ray.diff.map(..): mod.rs:58-84 (reflect) / :119-163 (transmit)
+inline Differential specular_differential(bool reflect, const Differential& diff, const SurfaceInteraction& isect, Vec3 wi, Float bsdf_eta) {
+    const TextureDifferentials& td = isect.tex_diffs; const DiffGeom& sh = isect.shading_geom;
+    Vec3 wo = isect.wo;
+    Differential o;
+    o.rx_origin = isect.hit.p + td.dpdx; o.ry_origin = isect.hit.p + td.dpdy;
+    Vec3 dndx = sh.dndu * td.dudx + sh.dndv * td.dvdx, dndy = sh.dndu * td.dudy + sh.dndv * td.dvdy;
+    Vec3 ns = isect.shading_n;
+    if (reflect) {
+        Vec3 dwo_dx = -diff.rx_dir - wo, dwo_dy = -diff.ry_dir - wo;
+        Float dDN_dx = dot(dwo_dx, ns) + dot(wo, dndx), dDN_dy = dot(dwo_dy, ns) + dot(wo, dndy);
+        o.rx_dir = (wi - dwo_dx) + (2.0f * dot(wo, ns)) * dndx + dDN_dx * ns;
+        o.ry_dir = (wi - dwo_dy) + (2.0f * dot(wo, ns)) * dndy + dDN_dy * ns;
+    } else {
+        Vec3 sn = ns; Float eta = 1.0f / bsdf_eta;
+        if (dot(wo, ns) < 0.0f) { eta = bsdf_eta; sn = -sn; dndx = -dndx; dndy = -dndy; }
+        Vec3 dwo_dx = -diff.rx_dir - wo, dwo_dy = -diff.ry_dir - wo;
+        Float dDN_dx = dot(dwo_dx, ns) + dot(wo, dndx), dDN_dy = dot(dwo_dy, ns) + dot(wo, dndy);   // unflipped normal, flipped dndx (:142-143)
+        Float mu = eta * dot(wo, sn) - abs_dot(wi, sn);
+        Float dmu_dx = (eta - (eta * eta * dot(wo, sn)) / dot(wi, sn)) * dDN_dx;
+        Float dmu_dy = (eta - (eta * eta * dot(wo, sn)) / dot(wi, sn)) * dDN_dy;
+        o.rx_dir = wi - (eta * dwo_dx) + (mu * dndx + dmu_dx * sn);
+        o.ry_dir = wi - (eta * dwo_dy) + (mu * dndy + dmu_dy * sn);
+    }
+    return o;
+}
 // DirectLightingIntegrator (UniformSampleOne): src/integrator/direct_lighting.rs:50-110 + specular_reflect/transmit mod.rs:39-178
 inline Spectrum direct_li(const Integrator& it, RayDifferential& ray, const SceneData& scene, Sampler& sampler, uint32_t depth);
 inline Spectrum specular_bounce_li(const Integrator& it, const RayDifferential& ray, const SurfaceInteraction& isect, const Bsdf& bsdf,
@@ -332,30 +358,7 @@ inline Spectrum specular_bounce_li(const Integrator& it, const RayDifferential& 
     if (!bsdf.sample_f(wo, u, flags, &sc)) return Spectrum(0.0f);
     if (abs_dot(sc.wi, isect.shading_n) == 0.0f) return Spectrum(0.0f);
     RayDifferential child; child.ray = isect.hit.spawn_ray(sc.wi); child.has_diff = ray.has_diff;
-    if (ray.has_diff) {                                                     // ray.diff.map(..): mod.rs:58-84 (reflect) / :119-163 (transmit)
-        const TextureDifferentials& td = isect.tex_diffs; const DiffGeom& sh = isect.shading_geom; const Differential& diff = ray.diff;
-        Differential o;
-        o.rx_origin = isect.hit.p + td.dpdx; o.ry_origin = isect.hit.p + td.dpdy;
-        Vec3 dndx = sh.dndu * td.dudx + sh.dndv * td.dvdx, dndy = sh.dndu * td.dudy + sh.dndv * td.dvdy;
-        Vec3 ns = isect.shading_n;
-        if (flags & BSDF_REFLECTION) {
-            Vec3 dwo_dx = -diff.rx_dir - wo, dwo_dy = -diff.ry_dir - wo;
-            Float dDN_dx = dot(dwo_dx, ns) + dot(wo, dndx), dDN_dy = dot(dwo_dy, ns) + dot(wo, dndy);
-            o.rx_dir = (sc.wi - dwo_dx) + (2.0f * dot(wo, ns)) * dndx + dDN_dx * ns;
-            o.ry_dir = (sc.wi - dwo_dy) + (2.0f * dot(wo, ns)) * dndy + dDN_dy * ns;
-        } else {
-            Vec3 sn = ns; Float eta = 1.0f / bsdf.eta;
-            if (dot(wo, ns) < 0.0f) { eta = bsdf.eta; sn = -sn; dndx = -dndx; dndy = -dndy; }
-            Vec3 dwo_dx = -diff.rx_dir - wo, dwo_dy = -diff.ry_dir - wo;
-            Float dDN_dx = dot(dwo_dx, ns) + dot(wo, dndx), dDN_dy = dot(dwo_dy, ns) + dot(wo, dndy);   // unflipped normal, flipped dndx (:142-143)
-            Float mu = eta * dot(wo, sn) - abs_dot(sc.wi, sn);
-            Float dmu_dx = (eta - (eta * eta * dot(wo, sn)) / dot(sc.wi, sn)) * dDN_dx;
-            Float dmu_dy = (eta - (eta * eta * dot(wo, sn)) / dot(sc.wi, sn)) * dDN_dy;
-            o.rx_dir = sc.wi - (eta * dwo_dx) + (mu * dndx + dmu_dx * sn);
-            o.ry_dir = sc.wi - (eta * dwo_dy) + (mu * dndy + dmu_dy * sn);
-        }
-        child.diff = o;
-    }
+    if (ray.has_diff) child.diff = specular_differential((flags & BSDF_REFLECTION) != 0, ray.diff, isect, sc.wi, bsdf.eta);
     Spectrum li = direct_li(it, child, scene, sampler, depth + 1);
     return sc.f * li * fabsf(dot(sc.wi, isect.shading_n)) / sc.pdf;
 }

@@ -120,6 +120,7 @@ struct SurfaceInteraction {
     SurfaceHit hit; Vec2 uv; Vec3 wo; DiffGeom geom; Vec3 shading_n; DiffGeom shading_geom;
     TextureDifferentials tex_diffs;
     int prim = -1;   // index into the BVH-ordered primitive array (Option<&dyn Primitive>)
+    Vec3 bary;       // not in the reference: a triangle hit's barycentrics, for orc_test_interaction (0 for a sphere)
     static SurfaceInteraction make(Vec3 p, Vec3 p_err, Float time, Vec2 uv, Vec3 wo, Vec3 n, DiffGeom g) {  // :84-107
         SurfaceInteraction s; s.hit.p = p; s.hit.p_err = p_err; s.hit.time = time; s.hit.n = n;
         s.uv = uv; s.wo = wo; s.geom = g; s.shading_n = n; s.shading_geom = g; return s;
@@ -422,6 +423,7 @@ struct Triangle : Shape {
             isect.shading_n = ns;
             isect.hit.n = faceforward(isect.hit.n, isect.shading_n);
         }
+        isect.bary = Vec3(b0, b1, b2);
         *t_out = t; *si = isect;
         return true;
     }

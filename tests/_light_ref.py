@@ -282,9 +282,10 @@ class Triangle:
         p_err = gamma(6) * (np.abs(b0 * p0) + np.abs(b1 * p1) + np.abs(b2 * p2))
         return dict(p=p, p_err=p_err, n=np.array(sn), bary=np.concatenate([b0, b1, b2], axis=1), fragile=fragile)
 
-    def intersect(self, o, d):
-        """:176-393 for a ray with t_max = infinity -> hit, p, n, fragile, whether an edge function is NaN (sign_differs, :428-434, then goes by the
-        NaN's sign bit, which IEEE 754 leaves to the implementation: hit or miss is not defined by the reference's text)"""
+    def hit_test(self, o, d, t_max=np.inf):
+        """the hit test of :176-268 and the late `None` of :277-288 -> dict(miss, bary, t, fragile, nan_edges): fragile = binary32 may decide
+        otherwise; nan_edges = an edge function is NaN (sign_differs, :428-434, then goes by the NaN's sign bit, which IEEE 754 leaves to the
+        implementation: hit or miss is not defined by the reference's text)"""
         p0, p1, p2 = self.p
         with np.errstate(all="ignore"):
             pt = np.stack([p0 - o, p1 - o, p2 - o], axis=1)                           # [row][vertex][xyz]
@@ -306,7 +307,7 @@ class Triangle:
             det = e0 + e1 + e2
             z = pt[:, :, 2] * sz[:, None]
             t_scaled = e0 * z[:, 0] + e1 * z[:, 1] + e2 * z[:, 2]
-            miss = differs | (det == 0.0) | ((det < 0.0) & (t_scaled >= 0.0)) | ((det > 0.0) & (t_scaled <= 0.0))
+            miss = differs | (det == 0.0) | ((det < 0.0) & ((t_scaled >= 0.0) | (t_scaled < t_max * det))) | ((det > 0.0) & ((t_scaled <= 0.0) | (t_scaled > t_max * det)))
             inv = 1.0 / det
             bary = e * inv[:, None]
             t = t_scaled * inv
@@ -321,28 +322,37 @@ class Triangle:
             duv02, duv12 = self.uv[0] - self.uv[2], self.uv[1] - self.uv[2]
             if abs(duv02[0] * duv12[1] - duv02[1] * duv12[0]) < 1.0e-8 and dot(cross(p2 - p0, p1 - p0), cross(p2 - p0, p1 - p0)) == 0.0:
                 miss |= True
-            p = bary[:, 0:1] * p0 + bary[:, 1:2] * p1 + bary[:, 2:3] * p2
-            n = normalize(cross(p0 - p2, p1 - p2))
-            if self.flip:
-                n = -n
-            n = np.broadcast_to(n, p.shape)
             # grazing an edge: an edge function within binary32's reach of 0 (each is a difference of two products of the sheared coordinates)
             # and the origin itself is a rounded sum: half an ulp of its largest coordinate in every translated vertex
             scale = max_x * max_y
             ulp_o = 2.0 * EPS * np.abs(o).max(axis=1)
             fragile = (np.abs(e).min(axis=1) <= 64 * EPS * scale + 4.0 * ulp_o * (max_x + max_y)) | (np.abs(t - delta_t) <= 1.0e-3 * np.abs(delta_t) + 64 * EPS * np.abs(t)) | ~np.isfinite(det)
-            fragile |= np.abs(t_scaled) <= 64 * EPS * max_e * max_z
-            if self.n is not None:                                                     # :332-391: hit.n = faceforward(hit.n, ns)
-                ns = normalize(bary[:, 0:1] * self.n[0] + bary[:, 1:2] * self.n[1] + bary[:, 2:3] * self.n[2])
-                dd = dot(n, ns)
-                fragile |= np.abs(dd) <= 1.0e-5
-                n = np.where((dd < 0.0)[:, None], -n, n)
+            fragile |= (np.abs(t_scaled) <= 64 * EPS * max_e * max_z) & ~(np.abs(t) < 0.5 * delta_t)     # (a t well inside delta_t is a miss whatever its sign)
+            fragile |= np.isfinite(t_max) & (np.abs(t - t_max) <= 64 * EPS * (np.abs(t_max) + max_e * max_z * np.abs(inv)))      # t_scaled against t_max * det
             # the same edge functions in binary32, where 3e20 squared is already infinite and inf - inf is NaN
             f = np.float32
             x32 = pt[:, :, 0].astype(f) + (-dp[:, 0].astype(f) / dp[:, 2].astype(f))[:, None] * pt[:, :, 2].astype(f)
             y32 = pt[:, :, 1].astype(f) + (-dp[:, 1].astype(f) / dp[:, 2].astype(f))[:, None] * pt[:, :, 2].astype(f)
             e32 = np.stack([x32[:, 1] * y32[:, 2] - y32[:, 1] * x32[:, 2], x32[:, 2] * y32[:, 0] - y32[:, 2] * x32[:, 0], x32[:, 0] * y32[:, 1] - y32[:, 0] * x32[:, 1]], axis=1)
-        return ~miss, p, np.array(n), fragile, np.isnan(e).any(axis=1) | np.isnan(e32).any(axis=1)
+        return dict(miss=miss, bary=bary, t=t, inv_det=inv, fragile=fragile, nan_edges=np.isnan(e).any(axis=1) | np.isnan(e32).any(axis=1))
+
+    def intersect(self, o, d):
+        """:176-393 for a ray with t_max = infinity -> hit, p, n, fragile, whether an edge function is NaN"""
+        p0, p1, p2 = self.p
+        h = self.hit_test(o, d)
+        bary, fragile = h["bary"], h["fragile"]
+        with np.errstate(all="ignore"):
+            p = bary[:, 0:1] * p0 + bary[:, 1:2] * p1 + bary[:, 2:3] * p2
+            n = normalize(cross(p0 - p2, p1 - p2))
+            if self.flip:
+                n = -n
+            n = np.broadcast_to(n, p.shape)
+            if self.n is not None:                                                     # :332-391: hit.n = faceforward(hit.n, ns)
+                ns = normalize(bary[:, 0:1] * self.n[0] + bary[:, 1:2] * self.n[1] + bary[:, 2:3] * self.n[2])
+                dd = dot(n, ns)
+                fragile = fragile | (np.abs(dd) <= 1.0e-5)
+                n = np.where((dd < 0.0)[:, None], -n, n)
+        return ~h["miss"], p, np.array(n), fragile, h["nan_edges"]
 
 
 # ---------------------------------------------------------------- shapes/sphere.rs
@@ -395,9 +405,9 @@ class Sphere:
             phi = np.arctan2(p[:, 1], p[:, 0])
             return p, np.where(phi < 0.0, phi + 2.0 * PI, phi)
 
-    def intersect(self, o_w, d_w):
-        """:83-200 for a ray with t_max = infinity -> hit, p, n, fragile, which root (0 near, 1 far).  The EFloat intervals of the reference are
-        not restated: a root within their reach of 0, or a discriminant within reach of 0, flags the row instead."""
+    def intersect(self, o_w, d_w, t_max=np.inf):
+        """:83-200 -> hit, p, n, fragile, which root (0 near, 1 far), the object-space point, t, the object-space ray (o, d).  The EFloat intervals of
+        the reference are not restated: a root within their reach of 0 or of t_max, or a discriminant within reach of 0, flags the row instead."""
         with np.errstate(all="ignore"):
             m = self.w2o
             o, d = tf_point(m, o_w), tf_vector(m, d_w)
@@ -405,6 +415,7 @@ class Sphere:
             len_sq = dot(d, d)
             dt = np.where(len_sq > 0.0, dot(np.abs(d), o_err) / len_sq, 0.0)
             o = o + d * dt[:, None]
+            t_max = t_max - dt                        # transform.rs:307-322
             a, b, c = len_sq, 2.0 * dot(d, o), dot(o, o) - self.r * self.r
             disc = b * b - 4.0 * a * c                # math.rs:36-53
             miss = disc < 0.0
@@ -416,11 +427,14 @@ class Sphere:
             size = (norm(o) + self.r) / np.sqrt(len_sq)
             reach = 1.0e-4 * size
             fragile = (np.abs(disc) <= 3.0e-6 * (b * b + np.abs(4.0 * a * c))) | ~np.isfinite(disc) | ~(len_sq > 0.0)
-            miss |= t1 <= 0.0                         # :99-101
+            miss |= (t1 <= 0.0) | (t0 > t_max)        # :99-101
+            fragile |= np.abs(t0 - t_max) <= reach
             fragile |= np.abs(t1) <= reach
             far = t0 <= 0.0                           # :104-110
             fragile |= np.abs(t0) <= reach
             t = np.where(far, t1, t0)
+            miss |= far & (t1 > t_max)                # :104-110
+            fragile |= np.abs(t1 - t_max) <= reach
             p, phi = self.at(o, d, t)
             clip = self.clipped(p, phi)
             fragile |= self.near_a_clip(p, phi) & ~miss
@@ -429,8 +443,9 @@ class Sphere:
             second = clip & ~far
             clip2 = self.clipped(p2, phi2)
             fragile |= second & self.near_a_clip(p2, phi2) & ~miss
-            miss |= second & clip2
+            miss |= second & (clip2 | (t1 > t_max))
             p = np.where(second[:, None], p2, p)
+            t = np.where(second, t1, t)
             which = (far | second).astype(int)
             # the normal: dpdu x dpdv of :155-168, reversed at :183-185, then SurfaceHit::transform (transform.rs:340-346)
             theta = np.arccos(np.clip(p[:, 2] / self.r, -1.0, 1.0))
@@ -443,7 +458,7 @@ class Sphere:
                 n = -n
             n = normalize(tf_normal(self.o2w_inv, n))
             fragile |= zr <= 1.0e-4 * self.r          # at the poles dpdu vanishes
-        return ~miss, tf_point(self.o2w, p), n, fragile, which, p
+        return ~miss, tf_point(self.o2w, p), n, fragile, which, p, t, (o, d)
 
 
 # ---------------------------------------------------------------- light/*.rs

@@ -73,7 +73,7 @@ def test_rounded_cube_watertight_and_bit_exact(gpu, orc_det):
     assert sa["nodes_visited"] == sao["nodes_visited"] and sa["prims_tested"] == sao["prims_tested"]
     assert np.allclose(bary.sum(1), 1.0, atol=1e-5)
     fg, fo = sg.intersect_full(rays[:20000]), so.intersect_full(rays[:20000])
-    for sl in (slice(0, 9), slice(11, 14), slice(20, 24)):          # p, p_err, n | wo | shading_n, t
+    for sl in (slice(0, 9), slice(11, 17), slice(20, 24)):          # p, p_err, n | wo, shading dpdu | shading_n, t  (9-10 uv and 17-19 dpdv: oracle only)
         assert np.array_equal(bits(fg[:, sl]), bits(fo[:, sl]))
 
 
@@ -107,7 +107,9 @@ def test_sphere_bvh_vs_oracle(gpu, orc_det):
     to, po, _, _ = so.intersect(rays)
     assert np.array_equal(occ, prim >= 0)
     assert np.array_equal(bits(t), bits(to)) and np.array_equal(prim, po)
-    assert np.array_equal(bits(sg.intersect_full(rays)[:, :9]), bits(so.intersect_full(rays)[:, :9]))
+    fg, fo = sg.intersect_full(rays), so.intersect_full(rays)
+    assert np.array_equal(bits(fg[:, :9]), bits(fo[:, :9]))
+    assert np.array_equal(bits(fg[:, 11:17]), bits(fo[:, 11:17])) and np.array_equal(bits(fg[:, 20:24]), bits(fo[:, 20:24]))      # wo, shading dpdu | shading_n, t
 
 
 def test_empty_scene(gpu):
@@ -651,6 +653,7 @@ def test_four_box_kernels_equal_the_oracle_on_ray_batches(gpu, orc_det, scene):
     assert np.array_equal(occ, occ_o) and 0 < occ.sum() < len(occ)
     full_g, full_o = sg.intersect_full(rays[:8000]), so.intersect_full(rays[:8000])
     assert np.array_equal(bits(full_g[:, :9]), bits(full_o[:, :9])) and np.array_equal(bits(full_g[:, 20:24]), bits(full_o[:, 20:24]))
+    assert np.array_equal(bits(full_g[:, 11:17]), bits(full_o[:, 11:17]))          # wo, shading dpdu
 
 
 def test_occlusion_records_edge_cases(gpu, orc_det, monkeypatch):
