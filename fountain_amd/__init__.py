@@ -4,8 +4,9 @@ from .api import (Backend, DirectLightingIntegrator, Film, FountainError, PathIn
                   RandomSampler, SamplerIntegrator, Scene, SceneBuilder, Transform, WhittedIntegrator, default_backend, film_resolve_device, load_ply,
                   load_ply_ascii, make_rays, read_exr, write_exr)
 from .filters import Filter, render_filtered
+from .subdiv import loop_subdivide, loop_subdivide_cpu
 
-__all__ = ["Backend", "DirectLightingIntegrator", "Film", "Filter", "render_filtered", "DisplayParams", "write_png", "BloomParams", "FountainError", "PathIntegrator", "PbrtScene", "PerspectiveCamera",
+__all__ = ["Backend", "DirectLightingIntegrator", "Film", "Filter", "render_filtered", "DisplayParams", "write_png", "BloomParams", "loop_subdivide", "loop_subdivide_cpu", "FountainError", "PathIntegrator", "PbrtScene", "PerspectiveCamera",
            "RandomSampler", "SamplerIntegrator", "Scene", "SceneBuilder", "Transform", "WhittedIntegrator", "default_backend",
            "film_resolve_device", "load_ply", "load_ply_ascii", "make_rays", "read_exr", "write_exr", "_abi"]
 

@@ -255,6 +255,17 @@ FTN_BLOOM_KARIS = 1
 FTN_BLOOM_MAX_LEVELS = 12
 FTN_BLOOM_ABI_VERSION = 1    # include/fountain_hip_bloom.h (an extension with a version of its own)
 
+FTN_SUBDIV_MAX_LEVELS = 10
+FTN_SUBDIV_MAX_FACES = 1 << 26
+FTN_SUBDIV_ABI_VERSION = 1   # include/fountain_hip_subdiv.h (an extension with a version of its own)
+
+
+class ftn_subdiv_info(C.Structure):
+    """include/fountain_hip_subdiv.h: the counts of every level of a Loop subdivision (ftn_loop_subdivide_info fills them)."""
+    _fields_ = [("levels", c_i32), ("max_valence", c_i32), ("n_vertices", c_u32 * (FTN_SUBDIV_MAX_LEVELS + 1)), ("n_faces", c_u32 * (FTN_SUBDIV_MAX_LEVELS + 1)),
+                ("n_edges", c_u32 * (FTN_SUBDIV_MAX_LEVELS + 1)), ("n_boundary", c_u32 * (FTN_SUBDIV_MAX_LEVELS + 1))]
+
+
 FTN_ABI_VERSION = 3          # include/fountain_hip.h; Backend() refuses a product library that reports another one
 
 # Expected sizes (bytes) -- asserted against the header by the C side's static_asserts and tests/test_abi.py
@@ -265,7 +276,7 @@ SIZES = {
     "ftn_render_options": 16, "ftn_stats": 152, "ftn_scene_memory": 96, "ftn_texture": 48, "ftn_image": 24, "ftn_material_textures": 32,
     "ftn_gbuffer_pixel": 48, "ftn_denoise_params": 32, "ftn_denoise_guided_params": 32, "ftn_moment_pixel": 16, "ftn_adaptive_params": 16, "ftn_adaptive_info": 24,
     "ftn_temporal_pixel": 32, "ftn_temporal_params": 32, "ftn_filter_desc": 32, "ftn_display_params": 48, "ftn_display_info": 32,
-    "ftn_bloom_params": 32,
+    "ftn_bloom_params": 32, "ftn_subdiv_info": 184,
 }
 
 # Every function the header declares (name -> None); used by the symbol-export test.
@@ -379,3 +390,14 @@ BLOOM_PROTOTYPES = {
     "ftn_bloom_abi_version": ([], C.c_int),
 }
 BLOOM_FUNCTIONS = sorted(BLOOM_PROTOTYPES)
+
+# Every function the extension header include/fountain_hip_subdiv.h declares (kept apart from the lists above: the reference's
+# loop_subdiv.rs ends in unimplemented!(), so these have no orc_* twin either), with its prototype: name -> (argument types, result type).
+_CAGE = [C.c_void_p, c_i32, C.c_void_p, c_i32, c_i32]      # P, n_vertices, indices, n_faces, levels
+SUBDIV_PROTOTYPES = {
+    "ftn_loop_subdivide_info": ([C.c_void_p, c_i32, c_i32, c_i32, C.c_void_p], C.c_int),
+    "ftn_loop_subdivide": (_CAGE + [C.c_void_p, C.c_void_p, C.c_void_p, c_i32], C.c_int),
+    "ftn_loop_subdivide_cpu": (_CAGE + [C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
+    "ftn_subdiv_abi_version": ([], C.c_int),
+}
+SUBDIV_FUNCTIONS = sorted(SUBDIV_PROTOTYPES)

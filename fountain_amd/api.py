@@ -455,6 +455,18 @@ class SceneBuilder:
                 idx = np.asarray(kw["indices"], dtype=np.uint32).reshape(-1, 3)
             S = np.asarray(kw["S"], dtype=np.float32).reshape(-1, 3) if kw.get("S") is not None else None      # constructors.rs:63
             self.add_mesh(P, N, UV, idx, tf, st["rev"], st["material"], st["area"], S=S)
+        elif name == "loopsubdiv":
+            # include/fountain_hip_subdiv.h: refined on the GPU where the product library has one, by its host twin otherwise and always
+            # over the oracle backend, which has no twin of it -- the same bits either way
+            from . import subdiv
+            if kw.get("P") is None or kw.get("indices") is None:
+                raise ValueError("loopsubdiv needs indices and P")
+            P = np.asarray(kw["P"], dtype=np.float32).reshape(-1, 3)
+            idx = np.asarray(kw["indices"], dtype=np.uint32).reshape(-1, 3)
+            levels = kw.get("levels", kw.get("nlevels", 3))
+            on_gpu = not self.be.is_oracle and self.be.fn("device_count")() > 0
+            P, N, idx = subdiv.loop_subdivide(self.be, P, idx, levels) if on_gpu else subdiv.loop_subdivide_cpu(self.be, P, idx, levels)
+            self.add_mesh(P, N, None, idx, tf, st["rev"], st["material"], st["area"])
         else:
             raise ValueError("unknown shape " + name)
 

@@ -7,9 +7,11 @@
  * plastic reads "ks" in lower case (constructors.rs:232); point/distant lights ignore the CTM; Integrator / PixelFilter /
  * Accelerator statements are ignored (pbrt.rs:528-530; PixelFilter is remembered for ftn_pbrt_filter alone); ObjectBegin/End are unimplemented in the reference -> FTN_ERR_UNSUPPORTED.
  * Texture statements: checkerboard (spectrum / float), uv and imagemap (OpenEXR files) as in pbrt.rs:362-385.
+ * `Shape "loopsubdiv"` (the shape src/shapes/loop_subdiv.rs began) is refined through include/fountain_hip_subdiv.h into a mesh with normals.
  */
 #include "../../include/fountain_hip.h"
 #include "../../include/fountain_hip_filter.h"
+#include "../../include/fountain_hip_subdiv.h"
 
 #include <cmath>
 #include <cstdio>
@@ -450,6 +452,22 @@ int parse(ftn_pbrt* S, const std::string& path) {
             } else if (type == "plymesh") {
                 auto it = ps.find("filename"); if (it == ps.end() || it->second.s.empty()) return fail(S, FTN_ERR_INVALID_ARGUMENT, "plymesh needs a filename");
                 Mesh m; if ((rc = load_ply(S, S->base_dir + "/" + it->second.s[0], &m))) return rc;
+                if ((rc = add_mesh(S, m))) return rc;
+            } else if (type == "loopsubdiv") {                      /* the shape loop_subdiv.rs began: fountain_hip_subdiv.h */
+                auto it = ps.find("indices"); auto ip = ps.find("P");
+                if (it == ps.end() || ip == ps.end()) return fail(S, FTN_ERR_INVALID_ARGUMENT, "loopsubdiv needs indices and P");
+                if (it->second.i.size() % 3) return fail(S, FTN_ERR_INVALID_ARGUMENT, "indices is not a multiple of 3");
+                if (ip->second.f.size() % 3) return fail(S, FTN_ERR_INVALID_ARGUMENT, "P is not a multiple of 3");
+                const int levels = geti(ps, "levels", geti(ps, "nlevels", 3));
+                std::vector<uint32_t> cage; for (int v : it->second.i) cage.push_back((uint32_t)v);
+                const int32_t nv = (int32_t)(ip->second.f.size() / 3), nf = (int32_t)(cage.size() / 3);
+                ftn_subdiv_info info;
+                if ((rc = ftn_loop_subdivide_info(cage.data(), nv, nf, levels, &info))) return fail(S, rc, ftn_last_error());
+                Mesh m; m.P.resize(3 * (size_t)info.n_vertices[levels]); m.N.resize(m.P.size()); m.idx.resize(3 * (size_t)info.n_faces[levels]);
+                /* the GPU where there is one, the host twin otherwise: the same bits, so the descriptors do not depend on which ran */
+                rc = ftn_device_count() > 0 ? ftn_loop_subdivide(ip->second.f.data(), nv, cage.data(), nf, levels, m.P.data(), m.N.data(), m.idx.data(), -1)
+                                            : ftn_loop_subdivide_cpu(ip->second.f.data(), nv, cage.data(), nf, levels, m.P.data(), m.N.data(), m.idx.data());
+                if (rc) return fail(S, rc, ftn_last_error());
                 if ((rc = add_mesh(S, m))) return rc;
             } else return fail(S, FTN_ERR_INVALID_ARGUMENT, "UnknownName(" + type + ")");
         } else return fail(S, FTN_ERR_INVALID_ARGUMENT, "unknown directive " + w);
