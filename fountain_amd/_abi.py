@@ -292,7 +292,7 @@ DECLARED_FUNCTIONS = [
     "ftn_last_error", "ftn_device_count", "ftn_version", "ftn_abi_version", "ftn_scene_memory_info", "ftn_test_math",
     "ftn_pbrt_load", "ftn_pbrt_destroy", "ftn_pbrt_scene", "ftn_pbrt_camera", "ftn_pbrt_film",
     "ftn_pbrt_samples_per_pixel", "ftn_pbrt_film_name", "ftn_pbrt_last_error", "ftn_ply_load",
-    "ftn_test_mipmap_level", "ftn_test_texture_eval", "ftn_test_bsdf", "ftn_test_light", "ftn_test_interaction", "ftn_test_camera", "ftn_film_resolve_device", "ftn_exr_write", "ftn_exr_read", "ftn_imageio_last_error", "ftn_image_inverse_gamma",
+    "ftn_test_mipmap_level", "ftn_test_texture_eval", "ftn_test_bsdf", "ftn_test_light", "ftn_test_interaction", "ftn_test_camera", "ftn_test_material", "ftn_film_resolve_device", "ftn_exr_write", "ftn_exr_read", "ftn_imageio_last_error", "ftn_image_inverse_gamma",
 ]
 
 # ftn_test_bsdf (the BSDF test hook): floats per input / output row, the BxDFType bits of `flags`, the argument types
@@ -307,6 +307,9 @@ FTN_TEST_INTERACTION_IN, FTN_TEST_INTERACTION_OUT = 32, 68
 TEST_INTERACTION_ARGTYPES = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
 FTN_TEST_CAMERA_IN, FTN_TEST_CAMERA_OUT = 8, 20
 TEST_CAMERA_ARGTYPES = [C.c_void_p, c_u32, C.c_void_p, C.c_size_t, C.c_void_p]
+# ftn_test_material (the textured-material test hook): floats per input / output row, the argument types
+FTN_TEST_MATERIAL_IN, FTN_TEST_MATERIAL_OUT = 6, 16
+TEST_MATERIAL_ARGTYPES = [C.c_void_p, c_i32, C.c_void_p, C.c_size_t, C.c_void_p]
 
 # Every function the extension header include/fountain_hip_gbuffer.h declares (kept apart from DECLARED_FUNCTIONS, which mirrors
 # fountain_hip.h alone: the reference has no G-buffer, so these have no orc_* twin).

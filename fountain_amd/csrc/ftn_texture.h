@@ -48,8 +48,11 @@ __device__ inline Rgb mip_triangle(const DScene& S, const DImage& im, int level,
     const float s = st.x * (float)im.lw[level] - 0.5f, t = st.y * (float)im.lh[level] - 0.5f;
     const int s0 = f2i_sat(floorf(s)), t0 = f2i_sat(floorf(t));
     const float ds = s - (float)s0, dt = t - (float)t0;
-    return mip_texel(S, im, (uint32_t)level, s0, t0) * (1.0f - ds) * (1.0f - dt) + mip_texel(S, im, (uint32_t)level, s0, t0 + 1) * (1.0f - ds) * dt +
-           mip_texel(S, im, (uint32_t)level, s0 + 1, t0) * ds * (1.0f - dt) + mip_texel(S, im, (uint32_t)level, s0 + 1, t0 + 1) * ds * dt;
+    /* s0 + 1 as Rust's release build adds i32: wrapping.  s0 is INT_MAX once st * w reaches 2^31 (uv of 1e10 or +inf); a signed add there is
+     * undefined, and the compiler used that to turn the `black` test t0 + 1 >= 0 into t0 > -2, which let the wrapped INT_MIN through as a row */
+    const int s1 = (int)((uint32_t)s0 + 1u), t1 = (int)((uint32_t)t0 + 1u);
+    return mip_texel(S, im, (uint32_t)level, s0, t0) * (1.0f - ds) * (1.0f - dt) + mip_texel(S, im, (uint32_t)level, s0, t1) * (1.0f - ds) * dt +
+           mip_texel(S, im, (uint32_t)level, s1, t0) * ds * (1.0f - dt) + mip_texel(S, im, (uint32_t)level, s1, t1) * ds * dt;
 }
 __device__ inline Rgb mip_lookup_trilinear_width(const DScene& S, const DImage& im, V2 st, float width) {  /* :273-286 */
     const float level = (float)im.n_levels - 1.0f + ftn_det::log2f_det(fmax_(width, 1.0e-8f));

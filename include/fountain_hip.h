@@ -507,6 +507,16 @@ int ftn_test_interaction(const ftn_scene* scene, const float* rows_in, size_t n,
 #define FTN_TEST_CAMERA_IN 8
 #define FTN_TEST_CAMERA_OUT 20
 int ftn_test_camera(const ftn_camera_desc* camera, uint32_t spp, const float* rows_in, size_t n, float* rows_out);
+/* Textured-material hook: what the shade kernels do with a hit's material ON THE DEVICE -- a material with a textured parameter has every
+ * such parameter evaluated at the row (Texture::evaluate) and the constant-per-material part of compute_scattering_functions applied to the
+ * result; any other material comes back as ftn_scene_create stored it (that part applied once, at upload).  rows_in (HOST memory), 6 floats
+ * per row, as ftn_test_texture_eval takes them: u, v, dudx, dvdx, dudy, dvdy.  rows_out, 16 floats per row: [0] 1 = the material has a
+ * textured parameter, else 0; [1] the BITS of its type; [2] the BITS of remap_roughness afterwards; [3..5] a; [6..8] b; [9..11] s0, s1, s2
+ * (matte: the clamped sigma and the Oren-Nayar A, B; plastic, metal, glass: s1, s2 the alphas); [12..15] 0.  A null argument or a material
+ * index outside the scene is refused before anything runs.  n == 0 does nothing.                                                       */
+#define FTN_TEST_MATERIAL_IN 6
+#define FTN_TEST_MATERIAL_OUT 16
+int ftn_test_material(const ftn_scene* scene, int32_t material, const float* rows_in, size_t n, float* rows_out);
 
 /* ------------------------------------------------------------------ misc */
 const char* ftn_last_error(void);

@@ -383,6 +383,37 @@ int orc_test_texture_eval(const orc_scene* s, int32_t texture, const float* in6,
     }
     return FTN_OK;
 }
+// the constant-per-material part of compute_scattering_functions (orc_reflection.hpp: matte.rs:39-50 + OrenNayar::new, the remap of
+// metal.rs:40-44, plastic.rs:35-38, glass.rs:57-61), written back into the record the way the device keeps it
+static void finalize_material(ftn_material& m) {
+    if (m.type == FTN_MAT_MATTE) {
+        m.s0 = clampf(m.s0, 0.0f, 90.0f);
+        if (m.s0 != 0.0f) { Float sg = deg_to_rad_cgmath(m.s0); Float sigma2 = sg * sg; m.s1 = 1.0f - (sigma2 / (2.0f * (sigma2 + 0.33f))); m.s2 = 0.45f * sigma2 / (sigma2 + 0.09f); }
+    } else if (m.type == FTN_MAT_METAL || m.type == FTN_MAT_GLASS) {
+        if (m.remap_roughness) { m.s1 = roughness_to_alpha(m.s1); m.s2 = roughness_to_alpha(m.s2); m.remap_roughness = 0; }
+    } else if (m.type == FTN_MAT_PLASTIC) {
+        if (m.remap_roughness) { m.s1 = roughness_to_alpha(m.s1); m.remap_roughness = 0; }
+    }
+}
+// ---- textured materials: the twin of ftn_test_material (fountain_hip.h has the row layouts): TextureSet::resolve, then the step above
+int orc_test_material(const orc_scene* s, int32_t material, const float* in6, size_t n, float* out16) {
+    if (!s || !in6 || !out16) return fail(FTN_ERR_INVALID_ARGUMENT, "null argument");
+    if (material < 0 || (size_t)material >= s->data.materials.size()) return fail(FTN_ERR_INVALID_ARGUMENT, "material index out of range");
+    const ftn_material_textures* mt = s->data.mtex.empty() ? nullptr : &s->data.mtex[material];
+    const bool textured = mt && (mt->a & mt->b & mt->s0 & mt->s1 & mt->s2) >= 0;
+    for (size_t i = 0; i < n; i++) {
+        const float* r = in6 + 6 * i; float* o = out16 + 16 * i;
+        SurfaceInteraction si; si.uv = Vec2(r[0], r[1]);
+        si.tex_diffs.dudx = r[2]; si.tex_diffs.dvdx = r[3]; si.tex_diffs.dudy = r[4]; si.tex_diffs.dvdy = r[5];
+        ftn_material m = s->data.tex.resolve(s->data.materials[material], textured ? mt : nullptr, si);
+        finalize_material(m);
+        const uint32_t type = m.type, remap = m.remap_roughness;
+        o[0] = textured ? 1.0f : 0.0f; memcpy(o + 1, &type, 4); memcpy(o + 2, &remap, 4);
+        for (int k = 0; k < 3; k++) { o[3 + k] = m.a[k]; o[6 + k] = m.b[k]; }
+        o[9] = m.s0; o[10] = m.s1; o[11] = m.s2; o[12] = o[13] = o[14] = o[15] = 0.0f;
+    }
+    return FTN_OK;
+}
 // ---- BSDFs (orc_reflection.hpp): the twin of ftn_test_bsdf (fountain_hip.h has the row layouts); `specialised` has no meaning here
 int orc_test_bsdf(const orc_scene* s, int32_t material, uint32_t flags, int allow_multiple_lobes, int /*specialised*/, const float* in17, size_t n, float* out16) {
     if (!s || !in17 || !out16) return fail(FTN_ERR_INVALID_ARGUMENT, "null argument");

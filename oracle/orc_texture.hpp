@@ -168,8 +168,9 @@ struct MIPMap {
         Float s = st.x * (Float)L.w - 0.5f, t = st.y * (Float)L.h - 0.5f;
         int s0 = f2i32(floorf(s)), t0 = f2i32(floorf(t));
         Float ds = s - (Float)s0, dt = t - (Float)t0;
-        return texel_of(L, s0, t0, wrap) * (1.0f - ds) * (1.0f - dt) + texel_of(L, s0, t0 + 1, wrap) * (1.0f - ds) * dt +
-               texel_of(L, s0 + 1, t0, wrap) * ds * (1.0f - dt) + texel_of(L, s0 + 1, t0 + 1, wrap) * ds * dt;
+        int s1 = (int)((uint32_t)s0 + 1u), t1 = (int)((uint32_t)t0 + 1u);   // i32 add (wrapping in release): s0 is INT_MAX once st * w reaches 2^31
+        return texel_of(L, s0, t0, wrap) * (1.0f - ds) * (1.0f - dt) + texel_of(L, s0, t1, wrap) * (1.0f - ds) * dt +
+               texel_of(L, s1, t0, wrap) * ds * (1.0f - dt) + texel_of(L, s1, t1, wrap) * ds * dt;
     }
     Spectrum lookup_trilinear_width(Vec2 st, Float width) const {           // :273-286
         Float level = (Float)levels() - 1.0f + m_log2(fmaxf(width, 1.0e-8f));

@@ -141,7 +141,11 @@ def test_texture_evaluate_closed_forms(orc):
     # a footprint as wide as the whole image returns the coarsest level's single texel (mipmap.rs:277-279)
     wide = rows.copy(); wide[:, 2] = 1.0
     got = tex_eval(sc, ids["img_clamp"], wide)
-    assert np.all(got == got[0]) and np.allclose(got[0], lvl0.mean(axis=(0, 1)), rtol=0.2)
+    stored = b.images[b.textures[ids["img_clamp"]].image][0]
+    top = mip_level(orc, stored, 3)                          # 6 x 10: 1 + floor(log2 10) = 4 levels
+    assert top.shape == (1, 1, 3) and mip_level(orc, stored, 4) is None
+    assert np.array_equal(got.view(np.uint32), np.broadcast_to(top[0, 0].view(np.uint32), got.shape))
+    assert np.allclose(top[0, 0], lvl0.mean(axis=(0, 1)), rtol=0.2)      # ... which is a weighted mean of the image
 
 
 def _textured_quad(be, integ_light="distant"):
