@@ -1,5 +1,8 @@
-"""Helpers shared by the bindings of the calls the CPU oracle has no twin of (gbuffer.py, denoise.py, moments.py, adaptive.py)."""
+"""Helpers shared by the bindings of the calls the CPU oracle has no twin of: the render passes (gbuffer.py, moments.py, adaptive.py) and
+the image-space stages (denoise.py, temporal.py, display.py, bloom.py)."""
 import ctypes as C
+
+import numpy as np
 
 from . import _abi as A
 from .api import FountainError
@@ -30,3 +33,50 @@ def check_tensor(t, shape):
     import torch
     if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() or tuple(t.shape) != tuple(shape):
         raise ValueError("expected a contiguous float32 CUDA tensor of shape %r" % (tuple(shape),))
+
+
+def check_workspace(t, need, device):
+    import torch
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or not t.is_contiguous() or t.device != device or t.numel() * t.element_size() < need:
+        raise ValueError("workspace must be a contiguous CUDA tensor of at least %d bytes on the device of rgb" % need)
+
+
+def set_fields(p, fields, hidden=()):
+    """The given fields of the params struct p (`hidden`: fields a caller does not set); returns p."""
+    for k, v in fields.items():
+        if k not in dict(p._fields_) or k in hidden:
+            raise TypeError("%s has no field %r" % (type(p).__name__, k))
+        setattr(p, k, v)
+    return p
+
+
+def params_of(be, params, struct, default_fn_name, lib_fn, wrapper=None, hidden=()):
+    """A `struct` from what a call takes as `params`: None (the defaults of lib_fn(be)'s default_fn_name), a dict (the defaults, then its
+    fields -- the arguments of `wrapper`, where the stage has one: a class whose instances carry the struct as .desc), a wrapper, or a
+    struct, which is returned as it is."""
+    if params is None or isinstance(params, dict):
+        if wrapper is not None:
+            return wrapper(be, **(params or {})).desc
+        p = struct()
+        getattr(lib_fn(be), default_fn_name)(C.byref(p))
+        return set_fields(p, params or {}, hidden)
+    if wrapper is not None and isinstance(params, wrapper):
+        return params.desc
+    if not isinstance(params, struct):
+        raise TypeError("params must be None, a dict%s or an %s" % (", a %s" % wrapper.__name__ if wrapper else "", struct.__name__))
+    return params
+
+
+_IMAGES = {3: "rgb", 4: "var4", 8: "history", 12: "gb12"}
+
+
+def host_image(a, channels, hw=None):
+    """`a` as a contiguous float32 [H, W, channels] array (with H, W = hw when given); ValueError otherwise."""
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    if a.ndim != 3 or a.shape[-1] != channels or (hw is not None and a.shape[:2] != tuple(hw)):
+        raise ValueError("expected %s [H, W, %d], got %r" % (_IMAGES[channels], channels, a.shape))
+    return a
+
+
+def ptr(a):
+    return None if a is None else a.ctypes.data_as(C.c_void_p)

@@ -22,7 +22,7 @@ import sys
 import numpy as np
 
 from . import _abi as A
-from ._nontwin import checked_lib
+from ._nontwin import checked_lib, host_image, params_of, ptr, set_fields
 from .api import default_backend
 
 
@@ -44,51 +44,28 @@ class BloomParams:
         _lib(self.be).ftn_bloom_params_default(C.byref(self.desc))
         if karis is not None:
             self.desc.flags = (self.desc.flags | A.FTN_BLOOM_KARIS) if karis else (self.desc.flags & ~A.FTN_BLOOM_KARIS)
-        known = dict(A.ftn_bloom_params._fields_)
-        for k, v in fields.items():
-            if k not in known:
-                raise TypeError("ftn_bloom_params has no field %r" % k)
-            setattr(self.desc, k, v)
+        set_fields(self.desc, fields)
 
 
 def _params(be, params):
-    if params is None:
-        return BloomParams(be).desc
-    if isinstance(params, dict):
-        return BloomParams(be, **params).desc
-    if isinstance(params, BloomParams):
-        return params.desc
-    if not isinstance(params, A.ftn_bloom_params):
-        raise TypeError("params must be None, a dict, a BloomParams or an ftn_bloom_params")
-    return params
-
-
-def _rgb(rgb):
-    rgb = np.ascontiguousarray(rgb, dtype=np.float32)
-    if rgb.ndim != 3 or rgb.shape[-1] != 3:
-        raise ValueError("expected rgb [H, W, 3], got %r" % (rgb.shape,))
-    return rgb
-
-
-def _ptr(a):
-    return a.ctypes.data_as(C.c_void_p)
+    return params_of(be, params, A.ftn_bloom_params, "ftn_bloom_params_default", _lib, BloomParams)
 
 
 def bloom(be, rgb, params=None, device=-1):
     """ftn_bloom: the bloomed image of a host image, computed on GPU `device`."""
     p = _params(be, params)
-    rgb = _rgb(rgb)
+    rgb = host_image(rgb, 3)
     out = np.empty_like(rgb)
-    be.check(_lib(be).ftn_bloom(_ptr(rgb), rgb.shape[1], rgb.shape[0], C.byref(p), _ptr(out), device))
+    be.check(_lib(be).ftn_bloom(ptr(rgb), rgb.shape[1], rgb.shape[0], C.byref(p), ptr(out), device))
     return out
 
 
 def bloom_cpu(be, rgb, params=None):
     """ftn_bloom_cpu: the host twin (the same bits)."""
     p = _params(be, params)
-    rgb = _rgb(rgb)
+    rgb = host_image(rgb, 3)
     out = np.empty_like(rgb)
-    be.check(_lib(be).ftn_bloom_cpu(_ptr(rgb), rgb.shape[1], rgb.shape[0], C.byref(p), _ptr(out)))
+    be.check(_lib(be).ftn_bloom_cpu(ptr(rgb), rgb.shape[1], rgb.shape[0], C.byref(p), ptr(out)))
     return out
 
 

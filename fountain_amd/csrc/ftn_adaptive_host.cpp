@@ -7,7 +7,7 @@
  * grow in sample order however the range is cut, and indexed_key makes each sample's stream independent of its neighbours' counts.  The
  * scene's cached tile list (ftn_scene::sel, tiles, tile_key) is not used.
  */
-#include "ftn_host_internal.h"
+#include "ftn_stage_host.h"
 #include "../../include/fountain_hip_adaptive.h"
 #include "ftn_adaptive.h"
 
@@ -70,7 +70,7 @@ int ftn_render_adaptive_device(const ftn_scene* cs, const ftn_camera_desc* cam, 
                                void* device_pixels, void* device_moments, void* device_samples, void* stream_v, ftn_adaptive_info* info, ftn_stats* st) {
     if (!cs || !cam || !film || !sd || !id || !ap || !device_pixels || !device_moments || !device_samples) return fail(FTN_ERR_INVALID_ARGUMENT, "null argument");
     int rc = adaptive_refusals(cs, sd, id, opt, ap); if (rc) return rc;
-    if (ftn_device_count() <= 0) return fail(FTN_ERR_NO_DEVICE, "no HIP device available: the fountain HIP path needs an AMD GPU (there is no CPU fallback)");
+    if (int no = need_device()) return no;
     ftn_scene* s = const_cast<ftn_scene*>(cs);
     if ((rc = bind_scene_device(s, opt))) return rc;
     hipStream_t stream = (hipStream_t)stream_v;
@@ -152,7 +152,7 @@ int ftn_render_adaptive(const ftn_scene* cs, const ftn_camera_desc* cam, const f
                         ftn_pixel* out_pixels, ftn_moment_pixel* out_moments, uint32_t* out_samples, ftn_adaptive_info* info, ftn_stats* st) {
     if (!cs || !cam || !film || !sd || !id || !ap || !out_pixels || !out_moments || !out_samples) return fail(FTN_ERR_INVALID_ARGUMENT, "null argument");
     int rc = adaptive_refusals(cs, sd, id, opt, ap); if (rc) return rc;
-    if (ftn_device_count() <= 0) return fail(FTN_ERR_NO_DEVICE, "no HIP device available: the fountain HIP path needs an AMD GPU (there is no CPU fallback)");
+    if (int no = need_device()) return no;
     if ((rc = bind_scene_device(cs, opt))) return rc;
     const size_t npix = (size_t)std::max(0, film->crop[2] - film->crop[0]) * (size_t)std::max(0, film->crop[3] - film->crop[1]);
     /* as ftn_render_moments: the call's sums from zero device buffers, added once into the caller's; the counts only for the tile range's

@@ -2,10 +2,10 @@
  * ftn_bloom_host.cpp -- C entry points of include/fountain_hip_bloom.h: the refusals, the workspace size, the host twin of the kernels
  * and the host-buffer entry.
  *
- * The per-pixel code is ftn_bloom.h's, shared with the kernels; error reporting, device selection and the host thread budget are the
- * host library's (ftn_host_internal.h).
+ * The per-pixel code is ftn_bloom.h's, shared with the kernels; the refusals' shared parts and the device buffers of the host-buffer
+ * entry are the stages' scaffold's (ftn_stage_host.h).
  */
-#include "ftn_host_internal.h"
+#include "ftn_stage_host.h"
 #include "ftn_bloom.h"
 
 #include <cstring>
@@ -14,20 +14,11 @@ using namespace ftn;
 
 namespace {
 
-const char* const kNoDevice = "no HIP device available: the fountain HIP path needs an AMD GPU (there is no CPU fallback)";
-
-int size_check(int32_t w, int32_t h) {
-    if (w <= 0 || h <= 0) return fail(FTN_ERR_INVALID_ARGUMENT, "image width and height must be positive");
-    if ((int64_t)w * (int64_t)h >= ((int64_t)1 << 31)) return fail(FTN_ERR_INVALID_ARGUMENT, "w * h must be below 2^31 pixels");
-    return FTN_OK;
-}
-
 int levels_check(int32_t levels) {
     if (levels < 0 || levels > FTN_BLOOM_MAX_LEVELS) return fail(FTN_ERR_INVALID_ARGUMENT, "bloom levels must be 0..12");
     return FTN_OK;
 }
 
-bool finite(float v) { return (f2u(v) & 0x7f800000u) != 0x7f800000u; }
 bool unit(float v) { return v >= 0.0f && v <= 1.0f; }
 
 /* refusals (3) to (7) of the header */
@@ -35,16 +26,11 @@ int params_check(const ftn_bloom_params* p) {
     int rc = levels_check(p->levels); if (rc) return rc;
     if (p->flags & ~FTN_BLOOM_KARIS) return fail(FTN_ERR_INVALID_ARGUMENT, "unknown ftn_bloom_params.flags bits");
     if (p->reserved != 0) return fail(FTN_ERR_INVALID_ARGUMENT, "ftn_bloom_params.reserved must be 0");
-    if (!finite(p->strength) || !finite(p->scatter) || !finite(p->threshold) || !finite(p->knee) || !finite(p->clamp_max))
+    if (!is_finite(p->strength) || !is_finite(p->scatter) || !is_finite(p->threshold) || !is_finite(p->knee) || !is_finite(p->clamp_max))
         return fail(FTN_ERR_INVALID_ARGUMENT, "strength, scatter, threshold, knee and clamp_max of ftn_bloom_params must be finite");
     if (!unit(p->strength) || !unit(p->scatter) || !unit(p->knee) || !(p->threshold >= 0.0f) || !(p->clamp_max > 0.0f && p->clamp_max <= 1e30f))
         return fail(FTN_ERR_INVALID_ARGUMENT, "ftn_bloom_params out of range: strength, scatter and knee in [0, 1], threshold >= 0, clamp_max in (0, 1e30]");
     return FTN_OK;
-}
-
-bool overlaps(const void* a, size_t na, const void* b, size_t nb) {
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return na && nb && a0 < b0 + nb && b0 < a0 + na;
 }
 
 bool is_copy(const BloomPlan& plan, const ftn_bloom_params* p) { return plan.L == 0 || p->strength == 0.0f; }
@@ -71,7 +57,7 @@ void ftn_bloom_params_default(ftn_bloom_params* p) {
 int ftn_bloom_workspace_size(int32_t w, int32_t h, int32_t levels, size_t* bytes) {
     if (!bytes) return fail(FTN_ERR_INVALID_ARGUMENT, "null argument");
     int rc;
-    if ((rc = size_check(w, h)) || (rc = levels_check(levels))) return rc;
+    if ((rc = image_check(w, h)) || (rc = levels_check(levels))) return rc;
     *bytes = bloom_plan(w, h, levels).floats * sizeof(float);
     return FTN_OK;
 }
@@ -79,41 +65,34 @@ int ftn_bloom_workspace_size(int32_t w, int32_t h, int32_t levels, size_t* bytes
 int ftn_bloom_device(const void* rgb, int32_t w, int32_t h, const ftn_bloom_params* p, void* out_rgb, void* workspace, void* stream) {
     if (!rgb || !p || !out_rgb) return fail(FTN_ERR_INVALID_ARGUMENT, "null argument");
     int rc;
-    if ((rc = size_check(w, h)) || (rc = params_check(p))) return rc;
+    if ((rc = image_check(w, h)) || (rc = params_check(p))) return rc;
     const BloomPlan plan = bloom_plan(w, h, p->levels);
-    const size_t n_rgb = 3 * (size_t)w * (size_t)h * sizeof(float), n_ws = plan.floats * sizeof(float);
-    if (n_ws && !workspace) return fail(FTN_ERR_INVALID_ARGUMENT, "null workspace");
-    if (overlaps(out_rgb, n_rgb, rgb, n_rgb) || overlaps(out_rgb, n_rgb, workspace, n_ws) || overlaps(workspace, n_ws, rgb, n_rgb))
-        return fail(FTN_ERR_INVALID_ARGUMENT, "out_rgb overlaps the input or the workspace, or the workspace overlaps the input");
-    if ((uintptr_t)rgb % 16 || (uintptr_t)out_rgb % 16 || (uintptr_t)workspace % 16)
-        return fail(FTN_ERR_INVALID_ARGUMENT, "misaligned buffer: rgb, out_rgb and the workspace need 16 bytes");
-    if (ftn_device_count() <= 0) return fail(FTN_ERR_NO_DEVICE, kNoDevice);
-    const hipError_t e = launch_bloom((const float*)rgb, plan, bloom_make(*p), is_copy(plan, p), (float*)out_rgb, (float*)workspace, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(FTN_ERR_INTERNAL, std::string("bloom launch: ") + hipGetErrorString(e));
-    return FTN_OK;
+    const size_t n_rgb = 3 * (size_t)w * (size_t)h * sizeof(float);
+    const Range r_rgb = {rgb, n_rgb, 16}, r_out = {out_rgb, n_rgb, 16}, r_ws = {workspace, plan.floats * sizeof(float), 16};
+    if (r_ws.bytes && !workspace) return fail(FTN_ERR_INVALID_ARGUMENT, "null workspace");
+    if ((rc = overlap_check({r_out, r_ws}, {r_rgb}, "out_rgb overlaps the input or the workspace, or the workspace overlaps the input"))) return rc;
+    if ((rc = align_check({r_rgb, r_out, r_ws}, "misaligned buffer: rgb, out_rgb and the workspace need 16 bytes"))) return rc;
+    if ((rc = need_device())) return rc;
+    return launched(launch_bloom((const float*)rgb, plan, bloom_make(*p), is_copy(plan, p), (float*)out_rgb, (float*)workspace, (hipStream_t)stream), "bloom");
 }
 
 int ftn_bloom(const float* rgb, int32_t w, int32_t h, const ftn_bloom_params* p, float* out_rgb, int32_t device) {
     if (!rgb || !p || !out_rgb) return fail(FTN_ERR_INVALID_ARGUMENT, "null argument");
     int rc;
-    if ((rc = size_check(w, h)) || (rc = params_check(p))) return rc;
-    if (ftn_device_count() <= 0) return fail(FTN_ERR_NO_DEVICE, kNoDevice);
-    if ((rc = set_device(device))) return rc;
-    const size_t n3 = 3 * (size_t)w * (size_t)h, ws = bloom_plan(w, h, p->levels).floats;
-    DevBuf<float> d_rgb, d_out, d_ws;
-    struct Release { DevBuf<float>* a; DevBuf<float>* b; DevBuf<float>* c; ~Release() { a->release(); b->release(); c->release(); } } keep{&d_rgb, &d_out, &d_ws};
-    if ((rc = d_rgb.upload(rgb, n3))) return rc;
-    HIP_TRY(hipMalloc((void**)&d_out.p, n3 * sizeof(float)));
-    if (ws) HIP_TRY(hipMalloc((void**)&d_ws.p, ws * sizeof(float)));
-    if ((rc = ftn_bloom_device(d_rgb.p, w, h, p, d_out.p, d_ws.p, nullptr))) return rc;
-    HIP_TRY(hipMemcpy(out_rgb, d_out.p, n3 * sizeof(float), hipMemcpyDeviceToHost));
-    return FTN_OK;
+    if ((rc = image_check(w, h)) || (rc = params_check(p))) return rc;
+    if ((rc = need_device()) || (rc = set_device(device))) return rc;
+    const size_t n3 = 3 * (size_t)w * (size_t)h;
+    StageBufs bufs;
+    float *d_rgb, *d_out, *d_ws;                                   /* (d_ws is null where the plan needs no workspace) */
+    if ((rc = bufs.upload(rgb, n3, &d_rgb)) || (rc = bufs.alloc(n3, &d_out)) || (rc = bufs.alloc(bloom_plan(w, h, p->levels).floats, &d_ws))) return rc;
+    if ((rc = ftn_bloom_device(d_rgb, w, h, p, d_out, d_ws, nullptr))) return rc;
+    return bufs.copy_back(out_rgb, d_out, n3);
 }
 
 int ftn_bloom_cpu(const float* rgb, int32_t w, int32_t h, const ftn_bloom_params* p, float* out_rgb) {
     if (!rgb || !p || !out_rgb) return fail(FTN_ERR_INVALID_ARGUMENT, "null argument");
     int rc;
-    if ((rc = size_check(w, h)) || (rc = params_check(p))) return rc;
+    if ((rc = image_check(w, h)) || (rc = params_check(p))) return rc;
     const BloomPlan plan = bloom_plan(w, h, p->levels);
     const size_t n = (size_t)w * (size_t)h;
     if (is_copy(plan, p)) { memmove(out_rgb, rgb, 3 * n * sizeof(float)); return FTN_OK; }

@@ -2,10 +2,10 @@
  * ftn_display_host.cpp -- C entry points of include/fountain_hip_display.h: the refusals, the exposure (host only, binary64), the host
  * twins of both kernels, the host-buffer entries and the PNG writer.
  *
- * The per-pixel code is ftn_display.h's, shared with the kernels; error reporting, device selection and the host thread budget are the
- * host library's (ftn_host_internal.h).
+ * The per-pixel code is ftn_display.h's, shared with the kernels; the refusals' shared parts and the device buffers of the host-buffer
+ * entries are the stages' scaffold's (ftn_stage_host.h).
  */
-#include "ftn_host_internal.h"
+#include "ftn_stage_host.h"
 #include "ftn_display.h"
 
 #include <cmath>
@@ -18,23 +18,13 @@ using namespace ftn;
 
 namespace {
 
-const char* const kNoDevice = "no HIP device available: the fountain HIP path needs an AMD GPU (there is no CPU fallback)";
-
-int size_check(int32_t w, int32_t h) {
-    if (w <= 0 || h <= 0) return fail(FTN_ERR_INVALID_ARGUMENT, "image width and height must be positive");
-    if ((int64_t)w * (int64_t)h >= ((int64_t)1 << 31)) return fail(FTN_ERR_INVALID_ARGUMENT, "w * h must be below 2^31 pixels");
-    return FTN_OK;
-}
-
-bool finite(float v) { return (f2u(v) & 0x7f800000u) != 0x7f800000u; }
-
 /* refusals (3) to (8) of the header */
 int params_check(const ftn_display_params* p) {
     if (p->tonemap > FTN_DISPLAY_TONEMAP_HABLE) return fail(FTN_ERR_INVALID_ARGUMENT, "unknown ftn_display_params.tonemap");
     if (p->transfer > FTN_DISPLAY_TRANSFER_LINEAR) return fail(FTN_ERR_INVALID_ARGUMENT, "unknown ftn_display_params.transfer");
     if (p->flags & ~(FTN_DISPLAY_DITHER | FTN_DISPLAY_AUTO_EXPOSURE)) return fail(FTN_ERR_INVALID_ARGUMENT, "unknown ftn_display_params.flags bits");
     if (p->reserved != 0) return fail(FTN_ERR_INVALID_ARGUMENT, "ftn_display_params.reserved must be 0");
-    if (!finite(p->ev) || !finite(p->key) || !finite(p->white) || !finite(p->gamma))
+    if (!is_finite(p->ev) || !is_finite(p->key) || !is_finite(p->white) || !is_finite(p->gamma))
         return fail(FTN_ERR_INVALID_ARGUMENT, "ev, key, white and gamma of ftn_display_params must be finite");
     if (!(p->key > 0.0f) || !(p->white > 0.0f) || !(p->gamma > 0.0f)) return fail(FTN_ERR_INVALID_ARGUMENT, "key, white and gamma of ftn_display_params must be above 0");
     if (!(p->p_lo >= 0.0f && p->p_lo < p->p_hi && p->p_hi <= 1.0f)) return fail(FTN_ERR_INVALID_ARGUMENT, "the percentiles of ftn_display_params need 0 <= p_lo < p_hi <= 1");
@@ -43,13 +33,8 @@ int params_check(const ftn_display_params* p) {
 }
 
 int scale_check(float scale) {
-    if (!finite(scale) || !(scale >= 0.0f)) return fail(FTN_ERR_INVALID_ARGUMENT, "the scale must be finite and not negative");
+    if (!is_finite(scale) || !(scale >= 0.0f)) return fail(FTN_ERR_INVALID_ARGUMENT, "the scale must be finite and not negative");
     return FTN_OK;
-}
-
-bool overlaps(const void* a, size_t na, const void* b, size_t nb) {
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return a0 < b0 + nb && b0 < a0 + na;
 }
 
 void put_be32(std::vector<unsigned char>& v, uint32_t x) { for (int s = 24; s >= 0; s -= 8) v.push_back((unsigned char)(x >> s)); }
@@ -89,33 +74,29 @@ void ftn_display_params_default(ftn_display_params* p) {
 
 int ftn_display_histogram_device(const void* rgb, int32_t w, int32_t h, void* hist, void* stream) {
     if (!rgb || !hist) return fail(FTN_ERR_INVALID_ARGUMENT, "null argument");
-    int rc = size_check(w, h); if (rc) return rc;
+    int rc = image_check(w, h); if (rc) return rc;
     const size_t n = (size_t)w * (size_t)h;
-    if (overlaps(hist, FTN_DISPLAY_HIST_WORDS * sizeof(uint32_t), rgb, 3 * n * sizeof(float))) return fail(FTN_ERR_INVALID_ARGUMENT, "the histogram overlaps the input");
-    if ((uintptr_t)rgb % 16 || (uintptr_t)hist % 16) return fail(FTN_ERR_INVALID_ARGUMENT, "misaligned buffer: rgb and the histogram need 16 bytes");
-    if (ftn_device_count() <= 0) return fail(FTN_ERR_NO_DEVICE, kNoDevice);
-    const hipError_t e = launch_display_histogram((const float*)rgb, (uint32_t)n, (uint32_t*)hist, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(FTN_ERR_INTERNAL, std::string("display histogram launch: ") + hipGetErrorString(e));
-    return FTN_OK;
+    const Range r_rgb = {rgb, 12 * n, 16}, r_hist = {hist, FTN_DISPLAY_HIST_WORDS * sizeof(uint32_t), 16};
+    if ((rc = overlap_check({r_hist}, {r_rgb}, "the histogram overlaps the input"))) return rc;
+    if ((rc = align_check({r_rgb, r_hist}, "misaligned buffer: rgb and the histogram need 16 bytes"))) return rc;
+    if ((rc = need_device())) return rc;
+    return launched(launch_display_histogram((const float*)rgb, (uint32_t)n, (uint32_t*)hist, (hipStream_t)stream), "display histogram");
 }
 
 int ftn_display_histogram(const float* rgb, int32_t w, int32_t h, uint32_t* hist, int32_t device) {
     if (!rgb || !hist) return fail(FTN_ERR_INVALID_ARGUMENT, "null argument");
-    int rc = size_check(w, h); if (rc) return rc;
-    if (ftn_device_count() <= 0) return fail(FTN_ERR_NO_DEVICE, kNoDevice);
-    if ((rc = set_device(device))) return rc;
-    const size_t n = (size_t)w * (size_t)h;
-    DevBuf<float> d_rgb; DevBuf<uint32_t> d_hist;
-    struct Release { DevBuf<float>* a; DevBuf<uint32_t>* b; ~Release() { a->release(); b->release(); } } keep{&d_rgb, &d_hist};
-    if ((rc = d_rgb.upload(rgb, 3 * n)) || (rc = d_hist.alloc_zero(FTN_DISPLAY_HIST_WORDS))) return rc;
-    if ((rc = ftn_display_histogram_device(d_rgb.p, w, h, d_hist.p, nullptr))) return rc;
-    HIP_TRY(hipMemcpy(hist, d_hist.p, FTN_DISPLAY_HIST_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    return FTN_OK;
+    int rc = image_check(w, h); if (rc) return rc;
+    if ((rc = need_device()) || (rc = set_device(device))) return rc;
+    StageBufs bufs;
+    float* d_rgb; uint32_t* d_hist;
+    if ((rc = bufs.upload(rgb, 3 * (size_t)w * (size_t)h, &d_rgb)) || (rc = bufs.alloc_zero(FTN_DISPLAY_HIST_WORDS, &d_hist))) return rc;
+    if ((rc = ftn_display_histogram_device(d_rgb, w, h, d_hist, nullptr))) return rc;
+    return bufs.copy_back(hist, d_hist, FTN_DISPLAY_HIST_WORDS);
 }
 
 int ftn_display_histogram_cpu(const float* rgb, int32_t w, int32_t h, uint32_t* hist) {
     if (!rgb || !hist) return fail(FTN_ERR_INVALID_ARGUMENT, "null argument");
-    int rc = size_check(w, h); if (rc) return rc;
+    int rc = image_check(w, h); if (rc) return rc;
     const size_t n = (size_t)w * (size_t)h;
     memset(hist, 0, FTN_DISPLAY_HIST_WORDS * sizeof(uint32_t));
     std::mutex m;
@@ -164,22 +145,20 @@ int ftn_display_exposure(const uint32_t* hist, const ftn_display_params* p, ftn_
 int ftn_display_encode_device(const void* rgb, int32_t w, int32_t h, const ftn_display_params* p, float scale, void* out_rgb, void* out_rgba8, void* stream) {
     if (!rgb || !p || !out_rgba8) return fail(FTN_ERR_INVALID_ARGUMENT, "null argument");
     int rc;
-    if ((rc = size_check(w, h)) || (rc = params_check(p)) || (rc = scale_check(scale))) return rc;
-    const size_t n = (size_t)w * (size_t)h, n_rgb = 3 * n * sizeof(float), n_8 = n * sizeof(uint32_t);
-    if (overlaps(out_rgba8, n_8, rgb, n_rgb) || (out_rgb && (overlaps(out_rgb, n_rgb, rgb, n_rgb) || overlaps(out_rgb, n_rgb, out_rgba8, n_8))))
-        return fail(FTN_ERR_INVALID_ARGUMENT, "an output overlaps the input or the other output");
-    if ((uintptr_t)rgb % 16 || (uintptr_t)out_rgb % 16 || (uintptr_t)out_rgba8 % 16)
-        return fail(FTN_ERR_INVALID_ARGUMENT, "misaligned buffer: rgb, out_rgb and out_rgba8 need 16 bytes");
-    if (ftn_device_count() <= 0) return fail(FTN_ERR_NO_DEVICE, kNoDevice);
-    const hipError_t e = launch_display_encode((const float*)rgb, (uint32_t)w, (uint32_t)n, disp_make(*p, scale), (float*)out_rgb, (uint32_t*)out_rgba8, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(FTN_ERR_INTERNAL, std::string("display encode launch: ") + hipGetErrorString(e));
-    return FTN_OK;
+    if ((rc = image_check(w, h)) || (rc = params_check(p)) || (rc = scale_check(scale))) return rc;
+    const size_t n = (size_t)w * (size_t)h;
+    const Range r_rgb = {rgb, 12 * n, 16}, r_out = {out_rgb, 12 * n, 16}, r_8 = {out_rgba8, 4 * n, 16};     /* (out_rgb may be null) */
+    if ((rc = overlap_check({r_8, r_out}, {r_rgb}, "an output overlaps the input or the other output"))) return rc;
+    if ((rc = align_check({r_rgb, r_out, r_8}, "misaligned buffer: rgb, out_rgb and out_rgba8 need 16 bytes"))) return rc;
+    if ((rc = need_device())) return rc;
+    return launched(launch_display_encode((const float*)rgb, (uint32_t)w, (uint32_t)n, disp_make(*p, scale), (float*)out_rgb, (uint32_t*)out_rgba8,
+                                          (hipStream_t)stream), "display encode");
 }
 
 int ftn_display_encode_cpu(const float* rgb, int32_t w, int32_t h, const ftn_display_params* p, float scale, float* out_rgb, uint32_t* out_rgba8) {
     if (!rgb || !p || !out_rgba8) return fail(FTN_ERR_INVALID_ARGUMENT, "null argument");
     int rc;
-    if ((rc = size_check(w, h)) || (rc = params_check(p)) || (rc = scale_check(scale))) return rc;
+    if ((rc = image_check(w, h)) || (rc = params_check(p)) || (rc = scale_check(scale))) return rc;
     const DispEncode e = disp_make(*p, scale);
     parallel_for((size_t)w * (size_t)h, [&](size_t i0, size_t i1) {
         for (size_t i = i0; i < i1; i++) {
@@ -195,13 +174,11 @@ int ftn_display_encode_cpu(const float* rgb, int32_t w, int32_t h, const ftn_dis
 static int display_host(const float* rgb, int32_t w, int32_t h, const ftn_display_params* p, const float* scale_in, float* out_rgb, uint32_t* out_rgba8,
                         ftn_display_info* info_out, int32_t device) {
     int rc;
-    if (ftn_device_count() <= 0) return fail(FTN_ERR_NO_DEVICE, kNoDevice);
-    if ((rc = set_device(device))) return rc;
+    if ((rc = need_device()) || (rc = set_device(device))) return rc;
     const size_t n = (size_t)w * (size_t)h;
-    DevBuf<float> d_rgb, d_out; DevBuf<uint32_t> d_8, d_hist;
-    struct Release { DevBuf<float>* a; DevBuf<float>* b; DevBuf<uint32_t>* c; DevBuf<uint32_t>* d;
-                     ~Release() { a->release(); b->release(); c->release(); d->release(); } } keep{&d_rgb, &d_out, &d_8, &d_hist};
-    if ((rc = d_rgb.upload(rgb, 3 * n))) return rc;
+    StageBufs bufs;
+    float *d_rgb, *d_out; uint32_t *d_8, *d_hist;
+    if ((rc = bufs.upload(rgb, 3 * n, &d_rgb))) return rc;
     float scale;
     if (scale_in) scale = *scale_in;
     else {
@@ -209,33 +186,31 @@ static int display_host(const float* rgb, int32_t w, int32_t h, const ftn_displa
         std::vector<uint32_t> hist;
         if (p->flags & FTN_DISPLAY_AUTO_EXPOSURE) {
             hist.resize(FTN_DISPLAY_HIST_WORDS);
-            if ((rc = d_hist.alloc_zero(FTN_DISPLAY_HIST_WORDS)) || (rc = ftn_display_histogram_device(d_rgb.p, w, h, d_hist.p, nullptr))) return rc;
-            HIP_TRY(hipMemcpy(hist.data(), d_hist.p, FTN_DISPLAY_HIST_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost));
+            if ((rc = bufs.alloc_zero(FTN_DISPLAY_HIST_WORDS, &d_hist)) || (rc = ftn_display_histogram_device(d_rgb, w, h, d_hist, nullptr)) ||
+                (rc = bufs.copy_back(hist.data(), d_hist, FTN_DISPLAY_HIST_WORDS))) return rc;
         }
         if ((rc = ftn_display_exposure(hist.empty() ? nullptr : hist.data(), p, &info))) return rc;
         if (info_out) *info_out = info;
         scale = info.scale;
         if ((rc = scale_check(scale))) return rc;
     }
-    if (out_rgb) HIP_TRY(hipMalloc((void**)&d_out.p, 3 * n * sizeof(float)));
-    HIP_TRY(hipMalloc((void**)&d_8.p, n * sizeof(uint32_t)));
-    if ((rc = ftn_display_encode_device(d_rgb.p, w, h, p, scale, d_out.p, d_8.p, nullptr))) return rc;
-    if (out_rgb) HIP_TRY(hipMemcpy(out_rgb, d_out.p, 3 * n * sizeof(float), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(out_rgba8, d_8.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    return FTN_OK;
+    if ((rc = bufs.alloc(out_rgb ? 3 * n : 0, &d_out)) || (rc = bufs.alloc(n, &d_8))) return rc;
+    if ((rc = ftn_display_encode_device(d_rgb, w, h, p, scale, d_out, d_8, nullptr))) return rc;
+    if ((rc = bufs.copy_back(out_rgb, d_out, 3 * n))) return rc;
+    return bufs.copy_back(out_rgba8, d_8, n);
 }
 
 int ftn_display_encode(const float* rgb, int32_t w, int32_t h, const ftn_display_params* p, float scale, float* out_rgb, uint32_t* out_rgba8, int32_t device) {
     if (!rgb || !p || !out_rgba8) return fail(FTN_ERR_INVALID_ARGUMENT, "null argument");
     int rc;
-    if ((rc = size_check(w, h)) || (rc = params_check(p)) || (rc = scale_check(scale))) return rc;
+    if ((rc = image_check(w, h)) || (rc = params_check(p)) || (rc = scale_check(scale))) return rc;
     return display_host(rgb, w, h, p, &scale, out_rgb, out_rgba8, nullptr, device);
 }
 
 int ftn_display(const float* rgb, int32_t w, int32_t h, const ftn_display_params* p, float* out_rgb, uint32_t* out_rgba8, ftn_display_info* info, int32_t device) {
     if (!rgb || !p || !out_rgba8) return fail(FTN_ERR_INVALID_ARGUMENT, "null argument");
     int rc;
-    if ((rc = size_check(w, h)) || (rc = params_check(p))) return rc;
+    if ((rc = image_check(w, h)) || (rc = params_check(p))) return rc;
     return display_host(rgb, w, h, p, nullptr, out_rgb, out_rgba8, info, device);
 }
 

@@ -7,7 +7,7 @@
  * renders no moments: `own` holds the gather's running sums, `in_tile` the call's grid map followed by its output-tile list.  They are
  * left marked dirty, so the next moments call clears them as after any call that spilled.
  */
-#include "ftn_host_internal.h"
+#include "ftn_stage_host.h"
 #include "../../include/fountain_hip_filter.h"
 #include "ftn_filter.h"
 
@@ -113,7 +113,7 @@ int ftn_render_filtered_device(const ftn_scene* cs, const ftn_camera_desc* cam, 
     int32_t sb[4]; ftn_film_sample_bounds(film, sb);
     G.mx = filter_margin(filter->radius[0], sb[0], sb[2]); G.my = filter_margin(filter->radius[1], sb[1], sb[3]);
     if (G.mx > 16 || G.my > 16) return fail(FTN_ERR_UNSUPPORTED, "film coordinates too large for the filter's footprint to stay within one tile of its pixel");
-    if (ftn_device_count() <= 0) return fail(FTN_ERR_NO_DEVICE, "no HIP device available: the fountain HIP path needs an AMD GPU (there is no CPU fallback)");
+    if (int no = need_device()) return no;
     ftn_scene* s = const_cast<ftn_scene*>(cs);
     if ((rc = bind_scene_device(s, opt))) return rc;
     hipStream_t stream = (hipStream_t)stream_v;
@@ -175,7 +175,7 @@ int ftn_render_filtered(const ftn_scene* cs, const ftn_camera_desc* cam, const f
     { int32_t sb[4]; ftn_film_sample_bounds(film, sb);
       if (filter_margin(filter->radius[0], sb[0], sb[2]) > 16 || filter_margin(filter->radius[1], sb[1], sb[3]) > 16)
           return fail(FTN_ERR_UNSUPPORTED, "film coordinates too large for the filter's footprint to stay within one tile of its pixel"); }
-    if (ftn_device_count() <= 0) return fail(FTN_ERR_NO_DEVICE, "no HIP device available: the fountain HIP path needs an AMD GPU (there is no CPU fallback)");
+    if (int no = need_device()) return no;
     if ((rc = bind_scene_device(cs, opt))) return rc;
     /* as ftn_render: the call's film from a zero device buffer, added once into the caller's */
     return render_to_host(crop_pixels(film), {{out_pixels, sizeof(ftn_pixel), true}},

@@ -4,7 +4,7 @@
  * The pass takes the steps of every render call (ftn_host_internal.h): the scene's tile-list cache and film accumulators (the samples whose
  * footprint leaves their own pixel are summed there), with PathIntegrator of max_depth 0 in the parameters.
  */
-#include "ftn_host_internal.h"
+#include "ftn_stage_host.h"
 #include "../../include/fountain_hip_gbuffer.h"
 #include "ftn_gbuffer.h"
 
@@ -26,7 +26,7 @@ int ftn_render_gbuffer_device(const ftn_scene* cs, const ftn_camera_desc* cam, c
     const uint32_t pipeline = opt ? opt->pipeline : FTN_PIPELINE_AUTO;
     if (pipeline == FTN_PIPELINE_MEGAKERNEL) return fail(FTN_ERR_UNSUPPORTED, "the G-buffer pass runs on the wavefront pipeline (FTN_PIPELINE_AUTO or FTN_PIPELINE_WAVEFRONT)");
     if (pipeline != FTN_PIPELINE_AUTO && pipeline != FTN_PIPELINE_WAVEFRONT) return fail(FTN_ERR_INVALID_ARGUMENT, "unknown pipeline");
-    if (ftn_device_count() <= 0) return fail(FTN_ERR_NO_DEVICE, "no HIP device available: the fountain HIP path needs an AMD GPU (there is no CPU fallback)");
+    if (int no = need_device()) return no;
     ftn_scene* s = const_cast<ftn_scene*>(cs);
     int rc = bind_scene_device(s, opt); if (rc) return rc;
     hipStream_t stream = (hipStream_t)stream_v;
@@ -54,7 +54,7 @@ int ftn_render_gbuffer(const ftn_scene* cs, const ftn_camera_desc* cam, const ft
     if (!cs || !cam || !film || !sd || !out_pixels) return fail(FTN_ERR_INVALID_ARGUMENT, "null argument");
     if (sd->kind == FTN_SAMPLER_TILE_SERIAL || (opt && opt->pipeline == FTN_PIPELINE_MEGAKERNEL))          /* (the refusals come before any device work) */
         return ftn_render_gbuffer_device(cs, cam, film, sd, tr, opt, out_pixels, nullptr, st);
-    if (ftn_device_count() <= 0) return fail(FTN_ERR_NO_DEVICE, "no HIP device available: the fountain HIP path needs an AMD GPU (there is no CPU fallback)");
+    if (int no = need_device()) return no;
     int rc = bind_scene_device(cs, opt); if (rc) return rc;
     const size_t npix = (size_t)std::max(0, film->crop[2] - film->crop[0]) * (size_t)std::max(0, film->crop[3] - film->crop[1]);
     /* the caller's sums go to the device and come back: every pixel's own samples are added to them one at a time (not summed apart and

@@ -4,7 +4,7 @@
  * The pass takes the steps of every render call (ftn_host_internal.h), with the scene's moments accumulators beside the film's: they are
  * grown on the first moments or adaptive call of a scene (ftn_render never allocates or clears them) and cleared under the same rule.
  */
-#include "ftn_host_internal.h"
+#include "ftn_stage_host.h"
 #include "../../include/fountain_hip_moments.h"
 #include "ftn_moments.h"
 
@@ -38,7 +38,7 @@ int ftn_render_moments_device(const ftn_scene* cs, const ftn_camera_desc* cam, c
                               const ftn_tile_range* tr, const ftn_render_options* opt, void* device_pixels, void* device_moments, void* stream_v, ftn_stats* st) {
     if (!cs || !cam || !film || !sd || !id || !device_pixels || !device_moments) return fail(FTN_ERR_INVALID_ARGUMENT, "null argument");
     int rc = moments_refusals(cs, sd, id, opt); if (rc) return rc;
-    if (ftn_device_count() <= 0) return fail(FTN_ERR_NO_DEVICE, "no HIP device available: the fountain HIP path needs an AMD GPU (there is no CPU fallback)");
+    if (int no = need_device()) return no;
     ftn_scene* s = const_cast<ftn_scene*>(cs);
     if ((rc = bind_scene_device(s, opt))) return rc;
     hipStream_t stream = (hipStream_t)stream_v;
@@ -62,7 +62,7 @@ int ftn_render_moments(const ftn_scene* cs, const ftn_camera_desc* cam, const ft
                        const ftn_tile_range* tr, const ftn_render_options* opt, ftn_pixel* out_pixels, ftn_moment_pixel* out_moments, ftn_stats* st) {
     if (!cs || !cam || !film || !sd || !id || !out_pixels || !out_moments) return fail(FTN_ERR_INVALID_ARGUMENT, "null argument");
     int rc = moments_refusals(cs, sd, id, opt); if (rc) return rc;
-    if (ftn_device_count() <= 0) return fail(FTN_ERR_NO_DEVICE, "no HIP device available: the fountain HIP path needs an AMD GPU (there is no CPU fallback)");
+    if (int no = need_device()) return no;
     if ((rc = bind_scene_device(cs, opt))) return rc;
     const size_t npix = (size_t)std::max(0, film->crop[2] - film->crop[0]) * (size_t)std::max(0, film->crop[3] - film->crop[1]);
     /* as ftn_render: the call's sums from zero device buffers, added once into the caller's */

@@ -5,7 +5,7 @@
  * The per-element code is ftn_subdiv.h's, shared with the kernels; error reporting, device selection and the host thread budget are the
  * host library's (ftn_host_internal.h).
  */
-#include "ftn_host_internal.h"
+#include "ftn_stage_host.h"
 #include "ftn_subdiv.h"
 
 #include <atomic>
@@ -14,8 +14,6 @@
 using namespace ftn;
 
 namespace {
-
-const char* const kNoDevice = "no HIP device available: the fountain HIP path needs an AMD GPU (there is no CPU fallback)";
 
 /* level 0: what the header's "Level 0" paragraph builds, and the counts that follow from it */
 struct Cage {
@@ -202,7 +200,7 @@ int ftn_loop_subdivide(const float* P, int32_t n_vertices, const uint32_t* indic
     if (!P || !indices || !out_P || !out_N || !out_indices) return fail(FTN_ERR_INVALID_ARGUMENT, "null argument");
     Cage c;
     int rc = build_cage(indices, n_vertices, n_faces, levels, &c); if (rc) return rc;
-    if (ftn_device_count() <= 0) return fail(FTN_ERR_NO_DEVICE, kNoDevice);
+    if (int no = need_device()) return no;
     if ((rc = set_device(device))) return rc;
     const ftn_subdiv_info& in = c.info;
     /* set s holds the levels of parity s; the limit positions go to the P set the last level does not use */

@@ -1,10 +1,10 @@
 /*
  * ftn_temporal_host.cpp -- C entry points of include/fountain_hip_temporal.h.
  *
- * The per-pixel code is ftn_temporal.h's, shared with the kernel; error reporting, device selection and the host thread budget are the host
- * library's (ftn_host_internal.h).
+ * The per-pixel code is ftn_temporal.h's, shared with the kernel; the refusals' shared parts and the device buffers of the host-buffer entry are
+ * the stages' scaffold's (ftn_stage_host.h).
  */
-#include "ftn_host_internal.h"
+#include "ftn_stage_host.h"
 #include "ftn_temporal.h"
 
 #include <cstring>
@@ -20,16 +20,15 @@ static int temporal_check(const ftn_camera_desc* cur, const ftn_film_desc* film,
     const int n_prev = (prev != nullptr) + (prev_gb12 != nullptr) + (prev_history != nullptr);
     if (n_prev != 0 && n_prev != 3)
         return fail(FTN_ERR_INVALID_ARGUMENT, "prev_camera, prev_gb12 and prev_history must be all null (the first frame) or all given");
-    if (w <= 0 || h <= 0) return fail(FTN_ERR_INVALID_ARGUMENT, "image width and height must be positive");
-    if ((int64_t)w * (int64_t)h >= ((int64_t)1 << 31)) return fail(FTN_ERR_INVALID_ARGUMENT, "w * h must be below 2^31 pixels");
+    if (int rc = image_check(w, h)) return rc;
     if ((int64_t)film->crop[2] - (int64_t)film->crop[0] != w || (int64_t)film->crop[3] - (int64_t)film->crop[1] != h)
         return fail(FTN_ERR_INVALID_ARGUMENT, "the film's crop is not w x h pixels");
     if (p->flags & ~(uint32_t)FTN_DENOISE_DEMODULATE) return fail(FTN_ERR_INVALID_ARGUMENT, "unknown ftn_temporal_params.flags bits");
     if (p->reserved[0] != 0 || p->reserved[1] != 0) return fail(FTN_ERR_INVALID_ARGUMENT, "ftn_temporal_params.reserved must be 0");
     if (!(p->alpha_min >= 0.0f && p->alpha_min <= 1.0f)) return fail(FTN_ERR_INVALID_ARGUMENT, "ftn_temporal_params.alpha_min must be in 0..1");
     for (float t : {p->normal_tol, p->plane_tol, p->albedo_tol})
-        if (!(t >= 0.0f) || !dn_finite(t)) return fail(FTN_ERR_INVALID_ARGUMENT, "a tolerance of ftn_temporal_params is negative or not finite");
-    if (!(p->albedo_eps >= 0.0f) || !dn_finite(p->albedo_eps)) return fail(FTN_ERR_INVALID_ARGUMENT, "ftn_temporal_params.albedo_eps is negative or not finite");
+        if (!(t >= 0.0f) || !is_finite(t)) return fail(FTN_ERR_INVALID_ARGUMENT, "a tolerance of ftn_temporal_params is negative or not finite");
+    if (!(p->albedo_eps >= 0.0f) || !is_finite(p->albedo_eps)) return fail(FTN_ERR_INVALID_ARGUMENT, "ftn_temporal_params.albedo_eps is negative or not finite");
     F->cur = tp_camera(*cur);
     F->prev = tp_camera(prev ? *prev : *cur);
     F->same_view = prev && tp_same_view(F->cur, F->prev);
@@ -37,11 +36,6 @@ static int temporal_check(const ftn_camera_desc* cur, const ftn_film_desc* film,
     F->flags = p->flags;
     F->alpha_min = p->alpha_min; F->normal_tol = p->normal_tol; F->plane_tol = p->plane_tol; F->albedo_eps = p->albedo_eps; F->albedo_tol = p->albedo_tol;
     return FTN_OK;
-}
-
-static bool overlaps(const void* a, size_t na, const void* b, size_t nb) {
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return a0 < b0 + nb && b0 < a0 + na;
 }
 
 }  // namespace
@@ -69,23 +63,13 @@ int ftn_temporal_accumulate_device(const void* rgb, const void* gb12, const void
     TpFrame F;
     int rc = temporal_check(cur_camera, film, w, h, prev_camera, prev_gb12, prev_history, p, &F); if (rc) return rc;
     const size_t n = (size_t)w * (size_t)h;
-    struct Range { const void* p; size_t bytes; };
-    const Range in[5] = {{rgb, 12 * n}, {gb12, 48 * n}, {var4, 16 * n}, {prev_gb12, 48 * n}, {prev_history, 32 * n}};
-    const Range out[3] = {{out_history, 32 * n}, {out_rgb, 12 * n}, {out_var4, 16 * n}};
-    for (int o = 0; o < 3; o++) {
-        for (const Range& i : in)
-            if (i.p && overlaps(out[o].p, out[o].bytes, i.p, i.bytes)) return fail(FTN_ERR_INVALID_ARGUMENT, "an output overlaps an input");
-        for (int o2 = o + 1; o2 < 3; o2++)
-            if (overlaps(out[o].p, out[o].bytes, out[o2].p, out[o2].bytes)) return fail(FTN_ERR_INVALID_ARGUMENT, "two outputs overlap");
-    }
-    if ((uintptr_t)out_history % 16 || (uintptr_t)prev_history % 16 || (uintptr_t)rgb % 4 || (uintptr_t)gb12 % 4 || (uintptr_t)var4 % 4 ||
-        (uintptr_t)prev_gb12 % 4 || (uintptr_t)out_rgb % 4 || (uintptr_t)out_var4 % 4)
-        return fail(FTN_ERR_INVALID_ARGUMENT, "misaligned buffer: the histories need 16 bytes, the images 4");
-    if (ftn_device_count() <= 0) return fail(FTN_ERR_NO_DEVICE, "no HIP device available: the fountain HIP path needs an AMD GPU (there is no CPU fallback)");
-    const hipError_t e = launch_temporal((const float*)rgb, (const float*)gb12, (const float*)var4, (const float*)prev_gb12, (const float4*)prev_history,
-                                         F, (float4*)out_history, (float*)out_rgb, (float*)out_var4, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(FTN_ERR_INTERNAL, std::string("temporal accumulation launch: ") + hipGetErrorString(e));
-    return FTN_OK;
+    const Range r_rgb = {rgb, 12 * n, 4}, r_gb = {gb12, 48 * n, 4}, r_var = {var4, 16 * n, 4}, r_pgb = {prev_gb12, 48 * n, 4}, r_ph = {prev_history, 32 * n, 16},
+                r_oh = {out_history, 32 * n, 16}, r_out = {out_rgb, 12 * n, 4}, r_ovar = {out_var4, 16 * n, 4};
+    if ((rc = overlap_check({r_oh, r_out, r_ovar}, {r_rgb, r_gb, r_var, r_pgb, r_ph}, "an output overlaps an input", "two outputs overlap"))) return rc;
+    if ((rc = align_check({r_oh, r_ph, r_rgb, r_gb, r_var, r_pgb, r_out, r_ovar}, "misaligned buffer: the histories need 16 bytes, the images 4"))) return rc;
+    if ((rc = need_device())) return rc;
+    return launched(launch_temporal((const float*)rgb, (const float*)gb12, (const float*)var4, (const float*)prev_gb12, (const float4*)prev_history, F,
+                                    (float4*)out_history, (float*)out_rgb, (float*)out_var4, (hipStream_t)stream), "temporal accumulation");
 }
 
 int ftn_temporal_accumulate(const float* rgb, const float* gb12, const float* var4, const ftn_camera_desc* cur_camera, const ftn_film_desc* film,
@@ -94,24 +78,17 @@ int ftn_temporal_accumulate(const float* rgb, const float* gb12, const float* va
     if (!rgb || !gb12 || !var4 || !out_history || !out_rgb || !out_var4) return fail(FTN_ERR_INVALID_ARGUMENT, "null argument");
     TpFrame F;
     int rc = temporal_check(cur_camera, film, w, h, prev_camera, prev_gb12, prev_history, p, &F); if (rc) return rc;
-    if (ftn_device_count() <= 0) return fail(FTN_ERR_NO_DEVICE, "no HIP device available: the fountain HIP path needs an AMD GPU (there is no CPU fallback)");
-    if ((rc = set_device(device))) return rc;
+    if ((rc = need_device()) || (rc = set_device(device))) return rc;
     const size_t n = (size_t)w * (size_t)h;
-    DevBuf<float> d_rgb, d_gb, d_var, d_pgb, d_out, d_ovar;
-    DevBuf<ftn_temporal_pixel> d_ph, d_oh;
-    struct Release { DevBuf<float>* f[6]; DevBuf<ftn_temporal_pixel>* t[2];
-                     ~Release() { for (auto* b : f) b->release(); for (auto* b : t) b->release(); } } keep{{&d_rgb, &d_gb, &d_var, &d_pgb, &d_out, &d_ovar}, {&d_ph, &d_oh}};
-    if ((rc = d_rgb.upload(rgb, 3 * n)) || (rc = d_gb.upload(gb12, 12 * n)) || (rc = d_var.upload(var4, 4 * n))) return rc;
-    if (prev_history && ((rc = d_pgb.upload(prev_gb12, 12 * n)) || (rc = d_ph.upload(prev_history, n)))) return rc;
-    HIP_TRY(hipMalloc((void**)&d_oh.p, n * sizeof(ftn_temporal_pixel)));
-    HIP_TRY(hipMalloc((void**)&d_out.p, 3 * n * sizeof(float)));
-    HIP_TRY(hipMalloc((void**)&d_ovar.p, 4 * n * sizeof(float)));
-    if ((rc = ftn_temporal_accumulate_device(d_rgb.p, d_gb.p, d_var.p, cur_camera, film, w, h, prev_camera, d_pgb.p, d_ph.p, p, d_oh.p, d_out.p,
-                                             d_ovar.p, nullptr))) return rc;
-    HIP_TRY(hipMemcpy(out_history, d_oh.p, n * sizeof(ftn_temporal_pixel), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(out_rgb, d_out.p, 3 * n * sizeof(float), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(out_var4, d_ovar.p, 4 * n * sizeof(float), hipMemcpyDeviceToHost));
-    return FTN_OK;
+    StageBufs bufs;
+    float *d_rgb, *d_gb, *d_var, *d_pgb, *d_out, *d_ovar;
+    ftn_temporal_pixel *d_ph, *d_oh;
+    if ((rc = bufs.upload(rgb, 3 * n, &d_rgb)) || (rc = bufs.upload(gb12, 12 * n, &d_gb)) || (rc = bufs.upload(var4, 4 * n, &d_var)) ||
+        (rc = bufs.upload(prev_gb12, 12 * n, &d_pgb)) || (rc = bufs.upload(prev_history, n, &d_ph)) ||      /* (null on the first frame) */
+        (rc = bufs.alloc(n, &d_oh)) || (rc = bufs.alloc(3 * n, &d_out)) || (rc = bufs.alloc(4 * n, &d_ovar))) return rc;
+    if ((rc = ftn_temporal_accumulate_device(d_rgb, d_gb, d_var, cur_camera, film, w, h, prev_camera, d_pgb, d_ph, p, d_oh, d_out, d_ovar, nullptr))) return rc;
+    if ((rc = bufs.copy_back(out_history, d_oh, n)) || (rc = bufs.copy_back(out_rgb, d_out, 3 * n))) return rc;
+    return bufs.copy_back(out_var4, d_ovar, 4 * n);
 }
 
 int ftn_temporal_accumulate_cpu(const float* rgb, const float* gb12, const float* var4, const ftn_camera_desc* cur_camera, const ftn_film_desc* film,

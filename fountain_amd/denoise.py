@@ -21,7 +21,7 @@ import ctypes as C
 import numpy as np
 
 from . import _abi as A
-from ._nontwin import checked_lib
+from ._nontwin import check_tensor, check_workspace, checked_lib, host_image, params_of, ptr
 
 
 def _lib(be):
@@ -33,172 +33,116 @@ def _guided_lib(be):
                        A.FTN_DENOISE_GUIDED_ABI_VERSION)
 
 
+# the two filters: the params struct, the prefix of the C names, the library check.  The calls below are written once for both; the guided
+# filter's take var4 between gb12 and the sizes
+_PLAIN = (A.ftn_denoise_params, "ftn_denoise", _lib)
+_GUIDED = (A.ftn_denoise_guided_params, "ftn_denoise_guided", _guided_lib)
+
+
+def _params(be, kind, params):
+    return params_of(be, params, kind[0], kind[1] + "_params_default", kind[2])
+
+
 def default_params(be, **fields):
     """ftn_denoise_params_default, then the given fields."""
-    p = A.ftn_denoise_params()
-    _lib(be).ftn_denoise_params_default(C.byref(p))
-    for k, v in fields.items():
-        if k not in dict(A.ftn_denoise_params._fields_):
-            raise TypeError("ftn_denoise_params has no field %r" % k)
-        setattr(p, k, v)
-    return p
+    return _params(be, _PLAIN, fields)
 
 
-def _params(be, params):
-    if params is None:
-        return default_params(be)
-    if isinstance(params, dict):
-        return default_params(be, **params)
-    if not isinstance(params, A.ftn_denoise_params):
-        raise TypeError("params must be None, a dict or an ftn_denoise_params")
-    return params
+def guided_params(be, **fields):
+    """ftn_denoise_guided_params_default, then the given fields."""
+    return _params(be, _GUIDED, fields)
 
 
-def _host_args(rgb, gb12):
-    rgb = np.ascontiguousarray(rgb, dtype=np.float32)
-    gb12 = np.ascontiguousarray(gb12, dtype=np.float32)
-    if rgb.ndim != 3 or rgb.shape[-1] != 3 or gb12.shape != rgb.shape[:2] + (12,):
-        raise ValueError("expected rgb [H, W, 3] and gb12 [H, W, 12], got %r and %r" % (rgb.shape, gb12.shape))
-    return rgb, gb12
+def _host_call(be, kind, suffix, rgb, gb12, var4, params, tail):
+    lib = kind[2](be)
+    p = _params(be, kind, params)
+    try:
+        rgb = host_image(rgb, 3)
+        gb12 = host_image(gb12, 12, rgb.shape[:2])
+    except ValueError:
+        raise ValueError("expected rgb [H, W, 3] and gb12 [H, W, 12], got %r and %r" % (np.shape(rgb), np.shape(gb12))) from None
+    images = [rgb, gb12]
+    if kind is _GUIDED:
+        try:
+            images.append(host_image(var4, 4, rgb.shape[:2]))
+        except ValueError:
+            raise ValueError("expected var4 [H, W, 4] with the H and W of rgb %r, got %r" % (rgb.shape, np.shape(var4))) from None
+    h, w = rgb.shape[:2]
+    out = np.empty_like(rgb)
+    be.check(getattr(lib, kind[1] + suffix)(*map(ptr, images), C.c_int32(w), C.c_int32(h), C.byref(p), ptr(out), *tail))
+    return out
 
 
 def denoise(be, rgb, gb12, params=None, device=-1):
     """ftn_denoise: host arrays, filtered on GPU `device` (-1 = the current one); returns a new [H, W, 3] float32 array."""
-    lib = _lib(be)
-    p = _params(be, params)
-    rgb, gb12 = _host_args(rgb, gb12)
-    h, w = rgb.shape[:2]
-    out = np.empty_like(rgb)
-    be.check(lib.ftn_denoise(rgb.ctypes.data_as(C.c_void_p), gb12.ctypes.data_as(C.c_void_p), C.c_int32(w), C.c_int32(h), C.byref(p),
-                             out.ctypes.data_as(C.c_void_p), C.c_int32(device)))
-    return out
+    return _host_call(be, _PLAIN, "", rgb, gb12, None, params, (C.c_int32(device),))
 
 
 def denoise_cpu(be, rgb, gb12, params=None):
     """ftn_denoise_cpu: the host twin of the filter (same bits as the GPU); returns a new [H, W, 3] float32 array."""
-    lib = _lib(be)
-    p = _params(be, params)
-    rgb, gb12 = _host_args(rgb, gb12)
-    h, w = rgb.shape[:2]
-    out = np.empty_like(rgb)
-    be.check(lib.ftn_denoise_cpu(rgb.ctypes.data_as(C.c_void_p), gb12.ctypes.data_as(C.c_void_p), C.c_int32(w), C.c_int32(h), C.byref(p),
-                                 out.ctypes.data_as(C.c_void_p)))
-    return out
+    return _host_call(be, _PLAIN, "_cpu", rgb, gb12, None, params, ())
+
+
+def denoise_guided(be, rgb, gb12, var4, params=None, device=-1):
+    """ftn_denoise_guided: host arrays, filtered on GPU `device` (-1 = the current one); returns a new [H, W, 3] float32 array."""
+    return _host_call(be, _GUIDED, "", rgb, gb12, var4, params, (C.c_int32(device),))
+
+
+def denoise_guided_cpu(be, rgb, gb12, var4, params=None):
+    """ftn_denoise_guided_cpu: the host twin of the guided filter (same bits as the GPU); returns a new [H, W, 3] float32 array."""
+    return _host_call(be, _GUIDED, "_cpu", rgb, gb12, var4, params, ())
+
+
+def _workspace_bytes(be, kind, w, h):
+    n = C.c_size_t()
+    be.check(getattr(kind[2](be), kind[1] + "_workspace_size")(C.c_int32(w), C.c_int32(h), C.byref(n)))
+    return n.value
 
 
 def workspace_bytes(be, w, h):
     """ftn_denoise_workspace_size: device bytes ftn_denoise_device needs for a w x h image (64 per pixel)."""
-    n = C.c_size_t()
-    be.check(_lib(be).ftn_denoise_workspace_size(C.c_int32(w), C.c_int32(h), C.byref(n)))
-    return n.value
+    return _workspace_bytes(be, _PLAIN, w, h)
+
+
+def guided_workspace_bytes(be, w, h):
+    """ftn_denoise_guided_workspace_size: device bytes ftn_denoise_guided_device needs for a w x h image (64 per pixel)."""
+    return _workspace_bytes(be, _GUIDED, w, h)
+
+
+def _torch_call(be, kind, rgb, gb12, var4, out, workspace, params):
+    import torch
+    lib = kind[2](be)
+    p = _params(be, kind, params)
+    inputs = [("rgb", rgb, 3), ("gb12", gb12, 12)] + ([("var4", var4, 4)] if kind is _GUIDED else [])
+    for _, t, k in inputs + [("out", out, 3)]:
+        try:
+            check_tensor(t, tuple(np.shape(t)[:2]) + (k,))
+        except ValueError:
+            raise ValueError("expected contiguous float32 CUDA tensors %s and out [H, W, 3]"
+                             % ", ".join("%s [H, W, %d]" % (n, k) for n, _, k in inputs)) from None
+    h, w = rgb.shape[:2]
+    if any(tuple(t.shape[:2]) != (h, w) or t.device != rgb.device for _, t, _ in inputs[1:] + [("out", out, 3)]):
+        raise ValueError("%s and out must have the same H and W and live on the same device" % ", ".join(n for n, _, _ in inputs))
+    need = _workspace_bytes(be, kind, w, h)
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=rgb.device)
+    else:
+        check_workspace(workspace, need, rgb.device)
+    stream = torch.cuda.current_stream(rgb.device).cuda_stream
+    be.check(getattr(lib, kind[1] + "_device")(*[C.c_void_p(t.data_ptr()) for _, t, _ in inputs], C.c_int32(w), C.c_int32(h), C.byref(p),
+                                               C.c_void_p(out.data_ptr()), C.c_void_p(workspace.data_ptr()), C.c_void_p(stream)))
+    return out
 
 
 def denoise_torch(be, rgb, gb12, out, workspace=None, params=None):
     """ftn_denoise_device: rgb [H, W, 3] and gb12 [H, W, 12] -> out [H, W, 3], contiguous float32 CUDA tensors on one device, on its
     current stream.  `workspace` is a CUDA tensor of at least workspace_bytes(be, W, H) bytes, 16-byte aligned; one is allocated when
     None (the call itself allocates nothing, so with a workspace given it can be captured in a graph).  Returns out."""
-    import torch
-    lib = _lib(be)
-    p = _params(be, params)
-    for t, k in ((rgb, 3), (gb12, 12), (out, 3)):
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() or t.dim() != 3 or t.shape[-1] != k:
-            raise ValueError("expected contiguous float32 CUDA tensors rgb [H, W, 3], gb12 [H, W, 12] and out [H, W, 3]")
-    h, w = rgb.shape[:2]
-    if tuple(gb12.shape[:2]) != (h, w) or tuple(out.shape[:2]) != (h, w) or gb12.device != rgb.device or out.device != rgb.device:
-        raise ValueError("rgb, gb12 and out must have the same H and W and live on the same device")
-    need = workspace_bytes(be, w, h)
-    if workspace is None:
-        workspace = torch.empty(need, dtype=torch.uint8, device=rgb.device)
-    elif not isinstance(workspace, torch.Tensor) or not workspace.is_cuda or not workspace.is_contiguous() or workspace.device != rgb.device \
-            or workspace.numel() * workspace.element_size() < need:
-        raise ValueError("workspace must be a contiguous CUDA tensor of at least %d bytes on the device of rgb" % need)
-    stream = torch.cuda.current_stream(rgb.device).cuda_stream
-    be.check(lib.ftn_denoise_device(C.c_void_p(rgb.data_ptr()), C.c_void_p(gb12.data_ptr()), C.c_int32(w), C.c_int32(h), C.byref(p),
-                                    C.c_void_p(out.data_ptr()), C.c_void_p(workspace.data_ptr()), C.c_void_p(stream)))
-    return out
-
-
-# ------------------------------------------------------------------ the variance-guided filter
-def guided_params(be, **fields):
-    """ftn_denoise_guided_params_default, then the given fields."""
-    p = A.ftn_denoise_guided_params()
-    _guided_lib(be).ftn_denoise_guided_params_default(C.byref(p))
-    for k, v in fields.items():
-        if k not in dict(A.ftn_denoise_guided_params._fields_):
-            raise TypeError("ftn_denoise_guided_params has no field %r" % k)
-        setattr(p, k, v)
-    return p
-
-
-def _guided_params(be, params):
-    if params is None:
-        return guided_params(be)
-    if isinstance(params, dict):
-        return guided_params(be, **params)
-    if not isinstance(params, A.ftn_denoise_guided_params):
-        raise TypeError("params must be None, a dict or an ftn_denoise_guided_params")
-    return params
-
-
-def _guided_host_args(rgb, gb12, var4):
-    rgb, gb12 = _host_args(rgb, gb12)
-    var4 = np.ascontiguousarray(var4, dtype=np.float32)
-    if var4.shape != rgb.shape[:2] + (4,):
-        raise ValueError("expected var4 [H, W, 4] with the H and W of rgb %r, got %r" % (rgb.shape, var4.shape))
-    return rgb, gb12, var4
-
-
-def denoise_guided(be, rgb, gb12, var4, params=None, device=-1):
-    """ftn_denoise_guided: host arrays, filtered on GPU `device` (-1 = the current one); returns a new [H, W, 3] float32 array."""
-    lib = _guided_lib(be)
-    p = _guided_params(be, params)
-    rgb, gb12, var4 = _guided_host_args(rgb, gb12, var4)
-    h, w = rgb.shape[:2]
-    out = np.empty_like(rgb)
-    be.check(lib.ftn_denoise_guided(rgb.ctypes.data_as(C.c_void_p), gb12.ctypes.data_as(C.c_void_p), var4.ctypes.data_as(C.c_void_p),
-                                    C.c_int32(w), C.c_int32(h), C.byref(p), out.ctypes.data_as(C.c_void_p), C.c_int32(device)))
-    return out
-
-
-def denoise_guided_cpu(be, rgb, gb12, var4, params=None):
-    """ftn_denoise_guided_cpu: the host twin of the guided filter (same bits as the GPU); returns a new [H, W, 3] float32 array."""
-    lib = _guided_lib(be)
-    p = _guided_params(be, params)
-    rgb, gb12, var4 = _guided_host_args(rgb, gb12, var4)
-    h, w = rgb.shape[:2]
-    out = np.empty_like(rgb)
-    be.check(lib.ftn_denoise_guided_cpu(rgb.ctypes.data_as(C.c_void_p), gb12.ctypes.data_as(C.c_void_p), var4.ctypes.data_as(C.c_void_p),
-                                        C.c_int32(w), C.c_int32(h), C.byref(p), out.ctypes.data_as(C.c_void_p)))
-    return out
-
-
-def guided_workspace_bytes(be, w, h):
-    """ftn_denoise_guided_workspace_size: device bytes ftn_denoise_guided_device needs for a w x h image (64 per pixel)."""
-    n = C.c_size_t()
-    be.check(_guided_lib(be).ftn_denoise_guided_workspace_size(C.c_int32(w), C.c_int32(h), C.byref(n)))
-    return n.value
+    return _torch_call(be, _PLAIN, rgb, gb12, None, out, workspace, params)
 
 
 def denoise_guided_torch(be, rgb, gb12, var4, out, workspace=None, params=None):
     """ftn_denoise_guided_device: rgb [H, W, 3], gb12 [H, W, 12] and var4 [H, W, 4] -> out [H, W, 3], contiguous float32 CUDA tensors on
     one device, on its current stream.  `workspace` as for denoise_torch, of at least guided_workspace_bytes(be, W, H) bytes.  Returns
     out."""
-    import torch
-    lib = _guided_lib(be)
-    p = _guided_params(be, params)
-    for t, k in ((rgb, 3), (gb12, 12), (var4, 4), (out, 3)):
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() or t.dim() != 3 or t.shape[-1] != k:
-            raise ValueError("expected contiguous float32 CUDA tensors rgb [H, W, 3], gb12 [H, W, 12], var4 [H, W, 4] and out [H, W, 3]")
-    h, w = rgb.shape[:2]
-    if any(tuple(t.shape[:2]) != (h, w) or t.device != rgb.device for t in (gb12, var4, out)):
-        raise ValueError("rgb, gb12, var4 and out must have the same H and W and live on the same device")
-    need = guided_workspace_bytes(be, w, h)
-    if workspace is None:
-        workspace = torch.empty(need, dtype=torch.uint8, device=rgb.device)
-    elif not isinstance(workspace, torch.Tensor) or not workspace.is_cuda or not workspace.is_contiguous() or workspace.device != rgb.device \
-            or workspace.numel() * workspace.element_size() < need:
-        raise ValueError("workspace must be a contiguous CUDA tensor of at least %d bytes on the device of rgb" % need)
-    stream = torch.cuda.current_stream(rgb.device).cuda_stream
-    be.check(lib.ftn_denoise_guided_device(C.c_void_p(rgb.data_ptr()), C.c_void_p(gb12.data_ptr()), C.c_void_p(var4.data_ptr()), C.c_int32(w),
-                                           C.c_int32(h), C.byref(p), C.c_void_p(out.data_ptr()), C.c_void_p(workspace.data_ptr()), C.c_void_p(stream)))
-    return out
+    return _torch_call(be, _GUIDED, rgb, gb12, var4, out, workspace, params)

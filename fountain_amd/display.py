@@ -26,7 +26,7 @@ import sys
 import numpy as np
 
 from . import _abi as A
-from ._nontwin import checked_lib
+from ._nontwin import checked_lib, host_image, params_of, ptr, set_fields
 from .api import default_backend
 
 TONEMAPS = {"linear": A.FTN_DISPLAY_TONEMAP_LINEAR, "reinhard": A.FTN_DISPLAY_TONEMAP_REINHARD, "aces": A.FTN_DISPLAY_TONEMAP_ACES,
@@ -61,11 +61,7 @@ class DisplayParams:
         for bit, on in ((A.FTN_DISPLAY_DITHER, dither), (A.FTN_DISPLAY_AUTO_EXPOSURE, auto_exposure)):
             if on is not None:
                 self.desc.flags = (self.desc.flags | bit) if on else (self.desc.flags & ~bit)
-        known = dict(A.ftn_display_params._fields_)
-        for k, v in fields.items():
-            if k not in known:
-                raise TypeError("ftn_display_params has no field %r" % k)
-            setattr(self.desc, k, v)
+        set_fields(self.desc, fields)
 
     @property
     def png_gamma(self):
@@ -74,41 +70,22 @@ class DisplayParams:
 
 
 def _params(be, params):
-    if params is None:
-        return DisplayParams(be).desc
-    if isinstance(params, dict):
-        return DisplayParams(be, **params).desc
-    if isinstance(params, DisplayParams):
-        return params.desc
-    if not isinstance(params, A.ftn_display_params):
-        raise TypeError("params must be None, a dict, a DisplayParams or an ftn_display_params")
-    return params
-
-
-def _rgb(rgb):
-    rgb = np.ascontiguousarray(rgb, dtype=np.float32)
-    if rgb.ndim != 3 or rgb.shape[-1] != 3:
-        raise ValueError("expected rgb [H, W, 3], got %r" % (rgb.shape,))
-    return rgb
-
-
-def _ptr(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
+    return params_of(be, params, A.ftn_display_params, "ftn_display_params_default", _lib, DisplayParams)
 
 
 def histogram(be, rgb, device=-1):
     """ftn_display_histogram: the luminance histogram of a host image, counted on GPU `device`; uint32 [FTN_DISPLAY_HIST_WORDS]."""
-    rgb = _rgb(rgb)
+    rgb = host_image(rgb, 3)
     hist = np.empty(A.FTN_DISPLAY_HIST_WORDS, np.uint32)
-    be.check(_lib(be).ftn_display_histogram(_ptr(rgb), rgb.shape[1], rgb.shape[0], _ptr(hist), device))
+    be.check(_lib(be).ftn_display_histogram(ptr(rgb), rgb.shape[1], rgb.shape[0], ptr(hist), device))
     return hist
 
 
 def histogram_cpu(be, rgb):
     """ftn_display_histogram_cpu: the host twin (the same words)."""
-    rgb = _rgb(rgb)
+    rgb = host_image(rgb, 3)
     hist = np.empty(A.FTN_DISPLAY_HIST_WORDS, np.uint32)
-    be.check(_lib(be).ftn_display_histogram_cpu(_ptr(rgb), rgb.shape[1], rgb.shape[0], _ptr(hist)))
+    be.check(_lib(be).ftn_display_histogram_cpu(ptr(rgb), rgb.shape[1], rgb.shape[0], ptr(hist)))
     return hist
 
 
@@ -127,17 +104,17 @@ def exposure(be, hist, params=None):
         if hist.shape != (A.FTN_DISPLAY_HIST_WORDS,):
             raise ValueError("expected a histogram of %d words" % A.FTN_DISPLAY_HIST_WORDS)
     info = A.ftn_display_info()
-    be.check(_lib(be).ftn_display_exposure(_ptr(hist), C.byref(p), C.byref(info)))
+    be.check(_lib(be).ftn_display_exposure(ptr(hist), C.byref(p), C.byref(info)))
     return info.as_dict()
 
 
 def _encode(be, fn, rgb, scale, params, want_float, tail):
     p = _params(be, params)
-    rgb = _rgb(rgb)
+    rgb = host_image(rgb, 3)
     h, w = rgb.shape[:2]
     out8 = np.empty((h, w), np.uint32)
     outf = np.empty_like(rgb) if want_float else None
-    be.check(fn(_ptr(rgb), w, h, C.byref(p), scale, _ptr(outf), _ptr(out8), *tail))
+    be.check(fn(ptr(rgb), w, h, C.byref(p), scale, ptr(outf), ptr(out8), *tail))
     return (out8, outf) if want_float else out8
 
 
@@ -165,12 +142,12 @@ def display(be, rgb, params=None, want_float=False, device=-1):
     (rgba8, float image, info)."""
     lib = _lib(be)
     p = _params(be, params)
-    rgb = _rgb(rgb)
+    rgb = host_image(rgb, 3)
     h, w = rgb.shape[:2]
     out8 = np.empty((h, w), np.uint32)
     outf = np.empty_like(rgb) if want_float else None
     info = A.ftn_display_info()
-    be.check(lib.ftn_display(_ptr(rgb), w, h, C.byref(p), _ptr(outf), _ptr(out8), C.byref(info), device))
+    be.check(lib.ftn_display(ptr(rgb), w, h, C.byref(p), ptr(outf), ptr(out8), C.byref(info), device))
     return (out8, outf, info.as_dict()) if want_float else (out8, info.as_dict())
 
 
@@ -190,7 +167,7 @@ def write_png(path, rgba8, be=None, gamma=None):
     if rgba8.ndim != 2:
         raise ValueError("expected rgba8 [H, W], got %r" % (rgba8.shape,))
     flags = 0 if gamma is None else ((int(100000.0 / gamma + 0.5) << 8) | A.FTN_PNG_GAMA)
-    be.check(_lib(be).ftn_png_write(os.fsencode(path), _ptr(rgba8), rgba8.shape[1], rgba8.shape[0], flags))
+    be.check(_lib(be).ftn_png_write(os.fsencode(path), ptr(rgba8), rgba8.shape[1], rgba8.shape[0], flags))
 
 
 def add_arguments(ap):

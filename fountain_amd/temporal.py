@@ -26,7 +26,7 @@ import sys
 import numpy as np
 
 from . import _abi as A
-from ._nontwin import check_tensor as _check_tensor, checked_lib
+from ._nontwin import check_tensor, checked_lib, host_image, params_of, ptr
 
 
 def _lib(be):
@@ -34,25 +34,13 @@ def _lib(be):
                        A.FTN_TEMPORAL_ABI_VERSION)
 
 
+def _params(be, params):
+    return params_of(be, params, A.ftn_temporal_params, "ftn_temporal_params_default", _lib, hidden=("reserved",))
+
+
 def temporal_params(be, **fields):
     """ftn_temporal_params_default, then the given fields."""
-    p = A.ftn_temporal_params()
-    _lib(be).ftn_temporal_params_default(C.byref(p))
-    for k, v in fields.items():
-        if k not in dict(A.ftn_temporal_params._fields_) or k == "reserved":
-            raise TypeError("ftn_temporal_params has no field %r" % k)
-        setattr(p, k, v)
-    return p
-
-
-def _params(be, params):
-    if params is None:
-        return temporal_params(be)
-    if isinstance(params, dict):
-        return temporal_params(be, **params)
-    if not isinstance(params, A.ftn_temporal_params):
-        raise TypeError("params must be None, a dict or an ftn_temporal_params")
-    return params
+    return _params(be, fields)
 
 
 def _desc(obj, typ, what):
@@ -71,18 +59,19 @@ def _prev(prev):
 
 
 def _host_frame(rgb, gb12, var4, prev):
-    rgb = np.ascontiguousarray(rgb, dtype=np.float32)
-    gb12 = np.ascontiguousarray(gb12, dtype=np.float32)
-    var4 = np.ascontiguousarray(var4, dtype=np.float32)
-    if rgb.ndim != 3 or rgb.shape[-1] != 3 or gb12.shape != rgb.shape[:2] + (12,) or var4.shape != rgb.shape[:2] + (4,):
-        raise ValueError("expected rgb [H, W, 3], gb12 [H, W, 12] and var4 [H, W, 4], got %r, %r and %r" % (rgb.shape, gb12.shape, var4.shape))
+    try:
+        rgb = host_image(rgb, 3)
+        gb12, var4 = host_image(gb12, 12, rgb.shape[:2]), host_image(var4, 4, rgb.shape[:2])
+    except ValueError:
+        raise ValueError("expected rgb [H, W, 3], gb12 [H, W, 12] and var4 [H, W, 4], got %r, %r and %r"
+                         % (np.shape(rgb), np.shape(gb12), np.shape(var4))) from None
     prev = _prev(prev)
     if prev is not None:
-        pgb = np.ascontiguousarray(prev[1], dtype=np.float32)
-        ph = np.ascontiguousarray(prev[2], dtype=np.float32)
-        if pgb.shape != gb12.shape or ph.shape != rgb.shape[:2] + (8,):
+        try:
+            pgb, ph = host_image(prev[1], 12, rgb.shape[:2]), host_image(prev[2], 8, rgb.shape[:2])
+        except ValueError:
             raise ValueError("expected a previous gb12 %r and a previous history %r, got %r and %r"
-                             % (gb12.shape, rgb.shape[:2] + (8,), pgb.shape, ph.shape))
+                             % (gb12.shape, rgb.shape[:2] + (8,), np.shape(prev[1]), np.shape(prev[2]))) from None
         prev = (_desc(prev[0], A.ftn_camera_desc, "the previous camera"), pgb, ph)
     return rgb, gb12, var4, prev
 
@@ -93,7 +82,6 @@ def _host_call(be, fn, rgb, gb12, var4, camera, film, prev, params, tail):
     rgb, gb12, var4, prev = _host_frame(rgb, gb12, var4, prev)
     h, w = rgb.shape[:2]
     hist, out, ovar = np.empty((h, w, 8), np.float32), np.empty_like(rgb), np.empty_like(var4)
-    ptr = lambda a: a.ctypes.data_as(C.c_void_p)
     pc, pg, ph = (C.byref(prev[0]), ptr(prev[1]), ptr(prev[2])) if prev is not None else (None, None, None)
     be.check(fn(ptr(rgb), ptr(gb12), ptr(var4), C.byref(cam), C.byref(fd), C.c_int32(w), C.c_int32(h), pc, pg, ph, C.byref(p),
                 ptr(hist), ptr(out), ptr(ovar), *tail))
@@ -125,7 +113,7 @@ def temporal_accumulate_torch(be, rgb, gb12, var4, camera, film, out_history, ou
     prev = _prev(prev)
     tensors = [(rgb, 3), (gb12, 12), (var4, 4), (out_history, 8), (out_rgb, 3), (out_var4, 4)] + ([(prev[1], 12), (prev[2], 8)] if prev is not None else [])
     for t, k in tensors:
-        _check_tensor(t, (h, w, k))
+        check_tensor(t, (h, w, k))
         if t.device != rgb.device:
             raise ValueError("every tensor must live on the device of rgb")
     pc, pg, ph = (C.byref(_desc(prev[0], A.ftn_camera_desc, "the previous camera")), C.c_void_p(prev[1].data_ptr()), C.c_void_p(prev[2].data_ptr())) \

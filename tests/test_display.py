@@ -161,6 +161,19 @@ def test_whole_chain_on_a_rendered_cornell_box(gpu, cornell):
     assert 20 < codes.mean() < 235                                      # an exposed picture, neither black nor burnt out
 
 
+@pytest.mark.parametrize("name", ["random 1x1", "random 37x53"])
+def test_whole_chain_with_and_without_its_optional_buffers(gpu, imgs, name):
+    """ftn_display on images of one pixel and of no whole tile: with the automatic exposure (a histogram on the device) and without
+    (none), with the float image and without, each against the chain of the twins"""
+    img = imgs[name]
+    for p in (dict(auto_exposure=True), dict(ev=-0.5, dither=True)):
+        want8, wantf, winfo = D.display_cpu(gpu, img, p, want_float=True)
+        got8, gotf, info = D.display(gpu, img, p, want_float=True)
+        assert np.array_equal(got8, want8) and np.array_equal(bits(gotf), bits(wantf)) and info == winfo, (name, p)
+        got8, info = D.display(gpu, img, p)
+        assert np.array_equal(got8, want8) and info == winfo, (name, p)
+
+
 def test_cli(gpu, tmp_path):
     """--png --auto-exposure --denoise writes out.png and out_denoised.png, both encoded at the main image's exposure and readable by
     the independent reader; the OpenEXR files beside them are byte for byte those written without --png; fountain_amd.display converts

@@ -89,6 +89,27 @@ def test_edge_inputs_device_equals_twin(gpu):
     assert np.isinf(out[1][2]).all() and (out[1][0][..., 3] == 2).all()
 
 
+@pytest.mark.parametrize("h,w", [(1, 1), (53, 37)])
+def test_host_history_need_not_be_aligned(gpu, h, w):
+    """the host-buffer entry takes a previous history at any 4-byte address (only device pointers need 16): a first frame, then a second
+    one whose previous history starts 4, 8 and 12 bytes past a 16-byte boundary, device against twin and against the aligned call"""
+    cams, frames = TC.sequence(h, w, 0.3, seed=1000 * h + w)
+    film = R.film_desc(A, (w, h))
+    d = [R.camera_desc(A, c) for c in cams]
+    first = T.temporal_accumulate(gpu, *frames[0], d[0], film, None, None)
+    assert same_bits(first, T.temporal_accumulate_cpu(gpu, *frames[0], d[0], film, None, None))
+    aligned = T.temporal_accumulate(gpu, *frames[1], d[1], film, (d[0], frames[0][1], first[0]), None)
+    raw = np.zeros(first[0].size + 8, np.float32)
+    at = (-raw.ctypes.data // 4) % 4                                     # floats up to the next 16-byte boundary
+    for off in (1, 2, 3):
+        hist = raw[at + off:at + off + first[0].size].reshape(first[0].shape)
+        hist[...] = first[0]
+        assert hist.ctypes.data % 16 == 4 * off and hist.flags["C_CONTIGUOUS"]
+        prev = (d[0], frames[0][1], hist)
+        got = T.temporal_accumulate(gpu, *frames[1], d[1], film, prev, None)
+        assert same_bits(got, T.temporal_accumulate_cpu(gpu, *frames[1], d[1], film, prev, None)) and same_bits(got, aligned)
+
+
 def arc_camera(be, k, n=8, res=128, step=0.01):
     """camera k of n on a short arc around the Cornell box that ends at scenes.cornell's own camera: `step` radians a frame, about 1.8
     pixels at the box's centre at 128^2"""
