@@ -101,15 +101,15 @@ struct DScene {
      * {n2, uv1.x} {uv1.y, uv2.x, uv2.y, shape index} {unused}.  The traversal kernels keep reading the dense `geom`. */
     const float4* srec;
     /* third view of the same BVH, what the production traversal kernels (ftn_trace4.hip) walk: one 128-byte record per two levels of
-     * the tree = the node records of an interior node's four grandchildren side by side (built by build_quads, ftn_host.cpp; NULL: not
+     * the tree = the node records of an interior node's four grandchildren side by side (built by build_quads, ftn_bvh_host.cpp; NULL: not
      * built).  quad_stack_bound: upper bound of the entries a walk can have pending. */
     const float4* quad;
     uint32_t n_quads, quad_stack_bound;
-    /* a second tree over the same leaves for Scene::intersect_test only (build_octs, ftn_host.cpp; ftn_trace8.hip): 128-byte records of up
+    /* a second tree over the same leaves for Scene::intersect_test only (build_octs, ftn_bvh_host.cpp; ftn_trace8.hip): 128-byte records of up
      * to eight children with outward-rounded 8-bit boxes, exact leaf boxes (oct_xbox: the leaves whose box is not their one triangle's) */
     const uint4* oct; const float4* oct_xbox;
     uint32_t n_octs, oct_stack_bound;
-    /* the same records as `quad` in 64 bytes for the closest-hit walk of triangle-only scenes (build_quad64s, ftn_host.cpp; NULL: not
+    /* the same records as `quad` in 64 bytes for the closest-hit walk of triangle-only scenes (build_quad64s, ftn_bvh_host.cpp; NULL: not
      * built): outward-rounded 8-bit boxes on a per-record grid, the leaves tested exactly on their own box (quad64_xbox: the leaves whose
      * box is not their one triangle's).  Record q here is record q of `quad`; quad64_stack_bound = quad_stack_bound */
     const uint4* quad64; const float4* quad64_xbox;

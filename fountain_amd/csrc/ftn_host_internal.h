@@ -1,7 +1,8 @@
 /*
- * ftn_host_internal.h -- what the host files of libfountain_hip.so share (ftn_host.cpp, ftn_gbuffer_host.cpp, ftn_denoise_host.cpp,
- * ftn_moments_host.cpp, ftn_adaptive_host.cpp): the scene behind a ftn_scene handle, error reporting, device selection, the host thread
- * budget, and the steps every render call takes (device, tiles, parameters, accumulators, timing, statistics).
+ * ftn_host_internal.h -- what the host files of libfountain_hip.so share (ftn_host.cpp, ftn_scene_host.cpp, ftn_bvh_host.cpp,
+ * ftn_geometry_host.cpp, ftn_gbuffer_host.cpp, ftn_denoise_host.cpp, ftn_moments_host.cpp, ftn_adaptive_host.cpp, the test hooks): the scene
+ * behind a ftn_scene handle, error reporting, device selection, the host thread budget, and the steps every render call takes (device,
+ * tiles, parameters, accumulators, timing, statistics).  What scene construction asks of the BVH unit is in ftn_bvh_host.h.
  *
  * Everything declared here has hidden visibility: splitting the host library into files exports nothing beyond the C ABI.
  */
@@ -21,7 +22,8 @@
 int fail(int code, const std::string& msg);
 #define HIP_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return fail(e_ == hipErrorOutOfMemory ? FTN_ERR_OUT_OF_MEMORY : FTN_ERR_NO_DEVICE, std::string(#expr ": ") + hipGetErrorString(e_)); } while (0)
 
-/* hipSetDevice(device) unless device < 0; FTN_ERR_NO_DEVICE without a HIP device */
+/* hipSetDevice(device) unless device < 0; FTN_ERR_NO_DEVICE (kNoDevice) without a HIP device */
+inline const char* const kNoDevice = "no HIP device available: the fountain HIP path needs an AMD GPU (there is no CPU fallback)";
 int set_device(int device);
 
 /* host threads for per-element passes (this process's share of the host; FTN_BVH_THREADS overrides; at most 32).  f(begin, end) over

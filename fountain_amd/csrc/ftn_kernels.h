@@ -1,5 +1,5 @@
 /*
- * ftn_kernels.h -- launch parameter blocks shared by the host driver (ftn_host.cpp) and the gfx950 kernels
+ * ftn_kernels.h -- launch parameter blocks shared by the host units (ftn_host.cpp, ftn_scene_host.cpp) and the gfx950 kernels
  * (ftn_kernels.hip, ftn_wavefront.hip).  Plain data only.
  */
 #ifndef FTN_KERNELS_H

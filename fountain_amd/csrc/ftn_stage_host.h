@@ -11,9 +11,6 @@
 
 #pragma GCC visibility push(hidden)
 
-/* (ftn_host.cpp's set_device keeps a copy of this sentence: that file is one of the benchmark's hashed sources, profiles/r03/traffic.json,
- * and stays as it is) */
-inline const char* const kNoDevice = "no HIP device available: the fountain HIP path needs an AMD GPU (there is no CPU fallback)";
 inline int need_device() { return ftn_device_count() <= 0 ? fail(FTN_ERR_NO_DEVICE, kNoDevice) : FTN_OK; }
 
 inline int image_check(int32_t w, int32_t h) {

@@ -1,9 +1,9 @@
 /*
  * ftn_test_bsdf.hip -- the BSDF test hook (include/fountain_hip.h, ftn_test_bsdf): kernel, launch and C entry point in a unit of their
- * own, so that the sources of the render kernels and of the host driver stay as they were profiled (profiles/r03/traffic.json hashes them).
+ * own, so that the sources of the render kernels stay as they were profiled (profiles/r03/traffic.json hashes them).
  * Calls make_bsdf / bsdf_f / bsdf_pdf / bsdf_sample of ftn_device.h as the shade kernels do; a row is 17 floats in, four float4 out.
  */
-#include "ftn_host_internal.h"
+#include "ftn_test_rows.h"
 
 namespace ftn {
 
@@ -46,9 +46,7 @@ __global__ void __launch_bounds__(256) k_test_bsdf(DScene S, int material, uint3
 }
 static void launch_test_bsdf(const DScene& S, int material, uint32_t flags, int allow_multiple_lobes, int specialised, const float* rows_in, size_t n,
                              float* rows_out, hipStream_t stream) {
-    if (n == 0) return;
-    size_t blocks = (n + 255) / 256; if (blocks > 8192) blocks = 8192;
-    hipLaunchKernelGGL(k_test_bsdf, dim3((unsigned)blocks), dim3(256), 0, stream, S, material, flags, allow_multiple_lobes, specialised, rows_in, n,
+    hipLaunchKernelGGL(k_test_bsdf, dim3(blocks_for(n)), dim3(256), 0, stream, S, material, flags, allow_multiple_lobes, specialised, rows_in, n,
                        reinterpret_cast<float4*>(rows_out));
 }
 
@@ -67,11 +65,6 @@ extern "C" int ftn_test_bsdf(const ftn_scene* cs, int32_t material, uint32_t fla
         if (e != hipSuccess) return fail(FTN_ERR_NO_DEVICE, hipGetErrorString(e));
         if ((mt.a & mt.b & mt.s0 & mt.s1 & mt.s2) >= 0) return fail(FTN_ERR_UNSUPPORTED, "ftn_test_bsdf takes materials with constant parameters only");
     }
-    DevBuf<float> din, dout;
-    if ((rc = din.upload(rows_in, FTN_TEST_BSDF_IN * n)) || (rc = dout.alloc_zero(FTN_TEST_BSDF_OUT * n))) { din.release(); dout.release(); return rc; }
-    launch_test_bsdf(cs->d, material, flags, allow_multiple_lobes, specialised, din.p, n, dout.p, 0);
-    hipError_t e = hipMemcpy(rows_out, dout.p, FTN_TEST_BSDF_OUT * n * sizeof(float), hipMemcpyDeviceToHost);
-    din.release(); dout.release();
-    if (e != hipSuccess) return fail(FTN_ERR_NO_DEVICE, hipGetErrorString(e));
-    return FTN_OK;
+    return test_rows(cs->device, n, {{rows_in, FTN_TEST_BSDF_IN}}, rows_out, FTN_TEST_BSDF_OUT,
+                     [&](const float* const* in, float* dout) { launch_test_bsdf(cs->d, material, flags, allow_multiple_lobes, specialised, in[0], n, dout, 0); });
 }

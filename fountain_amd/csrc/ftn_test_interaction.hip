@@ -1,7 +1,7 @@
 /*
  * ftn_test_interaction.hip -- the surface-interaction and camera test hooks (include/fountain_hip.h, ftn_test_interaction, ftn_test_camera):
  * kernels, launches and C entry points in a unit of their own, as ftn_test_bsdf.hip and ftn_test_light.hip, so that the sources of the render
- * kernels and of the host driver stay as they were profiled.
+ * kernels stay as they were profiled.
  * k_test_interaction intersects ONE primitive per row as shape_pdf_from_ref does (tri_hit + tri_uv_degenerate_reject, or sphere_intersect), then
  * calls make_interaction, compute_tex_diffs, spawn_ray and specular_diff of ftn_device.h / ftn_texture.h as the shade kernels do.
  * k_test_camera calls camera_ray and camera_ray_diff on a DCamera built by render_params, the host code of ftn_render.
@@ -18,7 +18,7 @@
  *                                    under GF_HAS_TANGENTS, which is set only when the scene has tangents, and then T holds n_vertices entries.
  * Rows are read and written at 32 * i and 68 * i floats of buffers of 32 * n and 68 * n floats, i < n.
  */
-#include "ftn_host_internal.h"
+#include "ftn_test_rows.h"
 #include "ftn_texture.h"
 
 #include <cstring>
@@ -78,19 +78,9 @@ __global__ void __launch_bounds__(256) k_test_camera(DCamera C, float spp_scale,
     }
 }
 
-static unsigned blocks_for(size_t n) { size_t b = (n + 255) / 256; return (unsigned)(b > 8192 ? 8192 : b); }
-
 }  // namespace ftn
 
 using namespace ftn;
-
-/* the rows go up, the output buffer starts zeroed, the rows come back: as ftn_test_light */
-static int copy_back(DevBuf<float>& din, DevBuf<float>& dout, float* rows_out, size_t n_out) {
-    hipError_t e = hipMemcpy(rows_out, dout.p, n_out * sizeof(float), hipMemcpyDeviceToHost);
-    din.release(); dout.release();
-    if (e != hipSuccess) return fail(FTN_ERR_NO_DEVICE, hipGetErrorString(e));
-    return FTN_OK;
-}
 
 extern "C" int ftn_test_interaction(const ftn_scene* cs, const float* rows_in, size_t n, float* rows_out) {
     if (!cs || !rows_in || !rows_out) return fail(FTN_ERR_INVALID_ARGUMENT, "null argument");
@@ -98,12 +88,8 @@ extern "C" int ftn_test_interaction(const ftn_scene* cs, const float* rows_in, s
         uint32_t prim; memcpy(&prim, rows_in + FTN_TEST_INTERACTION_IN * i + 8, 4);
         if (prim >= cs->d.n_prims) return fail(FTN_ERR_INVALID_ARGUMENT, "primitive index out of range");
     }
-    if (n == 0) return FTN_OK;
-    int rc = set_device(cs->device); if (rc) return rc;
-    DevBuf<float> din, dout;
-    if ((rc = din.upload(rows_in, FTN_TEST_INTERACTION_IN * n)) || (rc = dout.alloc_zero(FTN_TEST_INTERACTION_OUT * n))) { din.release(); dout.release(); return rc; }
-    hipLaunchKernelGGL(k_test_interaction, dim3(blocks_for(n)), dim3(256), 0, 0, cs->d, din.p, n, dout.p);
-    return copy_back(din, dout, rows_out, FTN_TEST_INTERACTION_OUT * n);
+    return test_rows(cs->device, n, {{rows_in, FTN_TEST_INTERACTION_IN}}, rows_out, FTN_TEST_INTERACTION_OUT,
+                     [&](const float* const* in, float* dout) { hipLaunchKernelGGL(k_test_interaction, dim3(blocks_for(n)), dim3(256), 0, 0, cs->d, in[0], n, dout); });
 }
 
 extern "C" int ftn_test_camera(const ftn_camera_desc* cam, uint32_t spp, const float* rows_in, size_t n, float* rows_out) {
@@ -116,9 +102,6 @@ extern "C" int ftn_test_camera(const ftn_camera_desc* cam, uint32_t spp, const f
     ftn_sampler_desc sd; memset(&sd, 0, sizeof(sd)); sd.samples_per_pixel = spp;
     ftn_integrator_desc id; memset(&id, 0, sizeof(id));
     const RenderParams P = render_params(&none, cam, &film, &sd, &id);
-    int rc = set_device(-1); if (rc) return rc;
-    DevBuf<float> din, dout;
-    if ((rc = din.upload(rows_in, FTN_TEST_CAMERA_IN * n)) || (rc = dout.alloc_zero(FTN_TEST_CAMERA_OUT * n))) { din.release(); dout.release(); return rc; }
-    hipLaunchKernelGGL(k_test_camera, dim3(blocks_for(n)), dim3(256), 0, 0, P.C, 1.0f / sqrtf((float)P.spp), din.p, n, dout.p);
-    return copy_back(din, dout, rows_out, FTN_TEST_CAMERA_OUT * n);
+    return test_rows(-1, n, {{rows_in, FTN_TEST_CAMERA_IN}}, rows_out, FTN_TEST_CAMERA_OUT,
+                     [&](const float* const* in, float* dout) { hipLaunchKernelGGL(k_test_camera, dim3(blocks_for(n)), dim3(256), 0, 0, P.C, 1.0f / sqrtf((float)P.spp), in[0], n, dout); });
 }

@@ -1,11 +1,11 @@
 /*
  * ftn_test_light.hip -- the light test hook (include/fountain_hip.h, ftn_test_light): kernel, launch and C entry point in a unit of their
- * own, as ftn_test_bsdf.hip, so that the sources of the render kernels and of the host driver stay as they were profiled.
+ * own, as ftn_test_bsdf.hip, so that the sources of the render kernels stay as they were profiled.
  * Calls light_sample / light_pdf / light_Le_env / area_Le of ftn_device.h as the shade kernels do -- through S.lights[light], or through
  * the copy of the one infinite light in the kernel arguments (S.env0, light_sample_env / light_pdf_env) as k_wf_shade<.., ENV> does.
  * A row is 15 floats in, six float4 out.
  */
-#include "ftn_host_internal.h"
+#include "ftn_test_rows.h"
 
 namespace ftn {
 
@@ -37,9 +37,7 @@ __global__ void __launch_bounds__(256) k_test_light(DScene S, int light, int via
     }
 }
 static void launch_test_light(const DScene& S, int light, int via_env0, const float* rows_in, size_t n, float* rows_out, hipStream_t stream) {
-    if (n == 0) return;
-    size_t blocks = (n + 255) / 256; if (blocks > 8192) blocks = 8192;
-    hipLaunchKernelGGL(k_test_light, dim3((unsigned)blocks), dim3(256), 0, stream, S, light, via_env0, rows_in, n, reinterpret_cast<float4*>(rows_out));
+    hipLaunchKernelGGL(k_test_light, dim3(blocks_for(n)), dim3(256), 0, stream, S, light, via_env0, rows_in, n, reinterpret_cast<float4*>(rows_out));
 }
 
 }  // namespace ftn
@@ -50,13 +48,6 @@ extern "C" int ftn_test_light(const ftn_scene* cs, int32_t light, int via_env0, 
     if (!cs || !rows_in || !rows_out) return fail(FTN_ERR_INVALID_ARGUMENT, "null argument");
     if (light < 0 || (uint32_t)light >= cs->d.n_lights) return fail(FTN_ERR_INVALID_ARGUMENT, "light index out of range");
     if (via_env0 && !cs->d.env_only) return fail(FTN_ERR_INVALID_ARGUMENT, "via_env0 needs a scene lit by one infinite light alone");
-    if (n == 0) return FTN_OK;
-    int rc = set_device(cs->device); if (rc) return rc;
-    DevBuf<float> din, dout;
-    if ((rc = din.upload(rows_in, FTN_TEST_LIGHT_IN * n)) || (rc = dout.alloc_zero(FTN_TEST_LIGHT_OUT * n))) { din.release(); dout.release(); return rc; }
-    launch_test_light(cs->d, light, via_env0 != 0, din.p, n, dout.p, 0);
-    hipError_t e = hipMemcpy(rows_out, dout.p, FTN_TEST_LIGHT_OUT * n * sizeof(float), hipMemcpyDeviceToHost);
-    din.release(); dout.release();
-    if (e != hipSuccess) return fail(FTN_ERR_NO_DEVICE, hipGetErrorString(e));
-    return FTN_OK;
+    return test_rows(cs->device, n, {{rows_in, FTN_TEST_LIGHT_IN}}, rows_out, FTN_TEST_LIGHT_OUT,
+                     [&](const float* const* in, float* dout) { launch_test_light(cs->d, light, via_env0 != 0, in[0], n, dout, 0); });
 }

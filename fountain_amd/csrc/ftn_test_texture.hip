@@ -1,7 +1,7 @@
 /*
  * ftn_test_texture.hip -- the textured-material test hook (include/fountain_hip.h, ftn_test_material): kernel, launch and C entry point in a
- * unit of their own, as ftn_test_bsdf.hip, ftn_test_light.hip and ftn_test_interaction.hip, so that the sources of the render kernels and of
- * the host driver stay as they were profiled.
+ * unit of their own, as ftn_test_bsdf.hip, ftn_test_light.hip and ftn_test_interaction.hip, so that the sources of the render kernels stay
+ * as they were profiled.
  * k_test_material does per row what the shade kernels do per hit: material_is_textured(S, mat) ? material_resolve(S, mat, uv, td) :
  * S.materials[mat] (ftn_texture.h).  A row is six floats in (u, v, dudx, dvdx, dudy, dvdy, as ftn_test_texture_eval takes them), 16 floats out.
  *
@@ -21,7 +21,7 @@
  *                            inside or rejects it); a level holds w * h texels from off[level] on, and the levels lie back to back.
  * Rows are read and written at 6 * i and 16 * i floats of buffers of 6 * n and 16 * n floats, i < n.
  */
-#include "ftn_host_internal.h"
+#include "ftn_test_rows.h"
 #include "ftn_texture.h"
 
 namespace ftn {
@@ -41,9 +41,7 @@ __global__ void __launch_bounds__(256) k_test_material(DScene S, int mat, const 
     }
 }
 static void launch_test_material(const DScene& S, int mat, const float* rows_in, size_t n, float* rows_out, hipStream_t stream) {
-    if (n == 0) return;
-    size_t blocks = (n + 255) / 256; if (blocks > 8192) blocks = 8192;
-    hipLaunchKernelGGL(k_test_material, dim3((unsigned)blocks), dim3(256), 0, stream, S, mat, rows_in, n, rows_out);
+    hipLaunchKernelGGL(k_test_material, dim3(blocks_for(n)), dim3(256), 0, stream, S, mat, rows_in, n, rows_out);
 }
 
 }  // namespace ftn
@@ -53,13 +51,6 @@ using namespace ftn;
 extern "C" int ftn_test_material(const ftn_scene* cs, int32_t material, const float* rows_in, size_t n, float* rows_out) {
     if (!cs || !rows_in || !rows_out) return fail(FTN_ERR_INVALID_ARGUMENT, "null argument");
     if (material < 0 || (size_t)material >= cs->materials.n) return fail(FTN_ERR_INVALID_ARGUMENT, "material index out of range");
-    if (n == 0) return FTN_OK;
-    int rc = set_device(cs->device); if (rc) return rc;
-    DevBuf<float> din, dout;
-    if ((rc = din.upload(rows_in, FTN_TEST_MATERIAL_IN * n)) || (rc = dout.alloc_zero(FTN_TEST_MATERIAL_OUT * n))) { din.release(); dout.release(); return rc; }
-    launch_test_material(cs->d, material, din.p, n, dout.p, 0);
-    hipError_t e = hipMemcpy(rows_out, dout.p, FTN_TEST_MATERIAL_OUT * n * sizeof(float), hipMemcpyDeviceToHost);
-    din.release(); dout.release();
-    if (e != hipSuccess) return fail(FTN_ERR_NO_DEVICE, hipGetErrorString(e));
-    return FTN_OK;
+    return test_rows(cs->device, n, {{rows_in, FTN_TEST_MATERIAL_IN}}, rows_out, FTN_TEST_MATERIAL_OUT,
+                     [&](const float* const* in, float* dout) { launch_test_material(cs->d, material, in[0], n, dout, 0); });
 }

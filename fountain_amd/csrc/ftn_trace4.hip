@@ -1,6 +1,6 @@
 /*
  * ftn_trace4.hip -- the production traversal kernels: Scene::intersect / Scene::intersect_test (src/bvh.rs:160-266) over 128-byte
- * four-box records (DScene::quad, built by build_quads in ftn_host.cpp: the reference's tree, two levels per record).
+ * four-box records (DScene::quad, built by build_quads in ftn_bvh_host.cpp: the reference's tree, two levels per record).
  *
  * Why this shape on gfx950: the reference's 32-byte nodes are gathered at random places of a 640 MB array, and the memory system
  * moves 128-byte lines -- a node visit costs a line (from L2, or from HBM) and a dependent round trip for ONE box test.  A four-box
@@ -466,7 +466,7 @@ __global__ void __launch_bounds__(256) k_wf_trace4_any(DScene S, WfBuffers W, co
     if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(&stats->rays_any, (unsigned long long)count);
 }
 
-/* ------------------------------------------------------------------ any hit over eight-box occlusion records (k_wf_trace8_any; DScene::oct, build_octs in ftn_host.cpp)
+/* ------------------------------------------------------------------ any hit over eight-box occlusion records (k_wf_trace8_any; DScene::oct, build_octs in ftn_bvh_host.cpp)
  * intersect_test returns a boolean and never shrinks t_max: a ray is occluded iff some LEAF's own box passes the slab test and one of the
  * leaf's primitives passes its test -- the interior boxes on the way only have to let every such leaf be reached, so they may be larger
  * than the reference's.  The records hold up to eight children with 8-bit planes on a per-record grid, rounded outwards by the builder

@@ -355,7 +355,7 @@ int ftn_bvh_build(const ftn_scene_desc* desc, ftn_bvh_node* nodes_out, uint32_t*
  * records_out: capacity 32 * (number of interior nodes) floats, or NULL to query the counts. */
 int ftn_bvh_quads(const ftn_bvh_node* nodes, uint32_t n_nodes, float* records_out, uint32_t* n_records_out, uint32_t* stack_bound_out);
 
-/* The eight-box occlusion records the any-hit kernel walks in triangle-only scenes (fountain_amd/csrc/ftn_host.cpp build_octs: a second
+/* The eight-box occlusion records the any-hit kernel walks in triangle-only scenes (fountain_amd/csrc/ftn_bvh_host.cpp build_octs: a second
  * tree over the reference's leaves with outward-rounded 8-bit boxes; exact because intersect_test only depends on which LEAF boxes and
  * primitives a ray passes).  Host-only, for tests: 32 words per record, 8 floats {min, first primitive, max, 0} per explicit leaf box. */
 int ftn_bvh_octs(const ftn_bvh_node* nodes, uint32_t n_nodes, uint32_t* records_out, uint32_t* n_records_out, uint32_t* stack_bound_out,

@@ -1,11 +1,11 @@
 """Shared by tests/test_bsdf_cpu.py (the oracle) and tests/test_bsdf.py (the device): the material configurations, the rows fed
 to the BSDF hook, the measured tolerances and the property checks, so that both sides face the same seeds and the same bounds."""
 import ctypes as C
-from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
 import _bsdf_ref as R
+from _rows import run_rows
 from fountain_amd import SceneBuilder, _abi as A
 
 f32 = np.float32
@@ -73,22 +73,9 @@ class Hook:
         self.fn.restype = C.c_int
 
     def raw(self, name, flags, aml, rows, specialised=0):
-        rows = np.ascontiguousarray(rows, f32).reshape(-1, A.FTN_TEST_BSDF_IN)
-        n = rows.shape[0]
-        out = np.empty((n, A.FTN_TEST_BSDF_OUT), f32)
         mat = self.index[name]
-
-        def part(lo, hi):
-            return self.fn(self.scene.handle, mat, flags, int(aml), int(specialised), rows[lo:hi].ctypes.data_as(C.c_void_p), hi - lo, out[lo:hi].ctypes.data_as(C.c_void_p))
-        if self.be.is_oracle and n >= 65536:          # the oracle walks the rows on the calling thread: split them over a few
-            cuts = np.linspace(0, n, 9).astype(int)
-            with ThreadPoolExecutor(8) as ex:
-                rcs = list(ex.map(lambda k: part(cuts[k], cuts[k + 1]), range(8)))
-        else:
-            rcs = [part(0, n)]
-        for rc in rcs:
-            self.be.check(rc)
-        return out
+        return run_rows(self.be, lambda pin, n, pout: self.fn(self.scene.handle, mat, flags, int(aml), int(specialised), pin, n, pout),
+                        rows, A.FTN_TEST_BSDF_IN, A.FTN_TEST_BSDF_OUT)
 
     def __call__(self, name, flags, aml, rows, specialised=0):
         return R.unpack(self.raw(name, flags, aml, rows, specialised))

@@ -3,12 +3,12 @@ cameras, the rows fed to the interaction and camera hooks (ftn_test_interaction 
 and the property checks, so that both sides face the same seeds and the same bounds.  Every bound below follows from the
 number formats or from reasoning written next to it; none comes from what a library returned."""
 import ctypes as C
-from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
 import _light_ref as R
 from _light_common import TRI_VARIANTS, above, below, same_bits_or_both_nan, unit
+from _rows import run_rows
 from fountain_amd import PerspectiveCamera, SceneBuilder, Transform, _abi as A
 
 f32 = np.float32
@@ -216,18 +216,7 @@ class Hook:
         rows = np.array(rows, f32, order="C").reshape(-1, NIN)
         if not bvh_indices:
             rows[:, 8:9].view(np.int32)[:, 0] = self.to_bvh[rows[:, 8:9].view(np.int32)[:, 0]]
-        n = rows.shape[0]
-        out = np.empty((n, NOUT), f32)
-
-        def part(lo, hi):
-            out[lo:hi] = self.scene.test_interaction(rows[lo:hi])
-        if self.be.is_oracle and n >= 65536:          # the oracle walks the rows on the calling thread: split them over a few
-            cuts = np.linspace(0, n, 9).astype(int)
-            with ThreadPoolExecutor(8) as ex:
-                list(ex.map(lambda k: part(cuts[k], cuts[k + 1]), range(8)))
-        else:
-            part(0, n)
-        return out
+        return run_rows(self.be, lambda pin, n, pout: self.fn(self.scene.handle, pin, n, pout), rows, NIN, NOUT)
 
     def __call__(self, rows):
         return unpack(self.raw(rows))

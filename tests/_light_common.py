@@ -2,12 +2,12 @@
 light hook (ftn_test_light / orc_test_light), the measured tolerances and the property checks, so that both sides face the same seeds and
 the same bounds."""
 import ctypes as C
-from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
 import _light_ref as R
 from _bsdf_common import wilson_hilferty
+from _rows import run_rows
 from fountain_amd import SceneBuilder, _abi as A
 
 f32 = np.float32
@@ -205,21 +205,7 @@ class Hook:
         return self._desc
 
     def raw(self, rows, via_env0=0):
-        rows = np.ascontiguousarray(rows, f32).reshape(-1, NIN)
-        n = rows.shape[0]
-        out = np.empty((n, NOUT), f32)
-
-        def part(lo, hi):
-            return self.fn(self.scene.handle, self.light, int(via_env0), rows[lo:hi].ctypes.data_as(C.c_void_p), hi - lo, out[lo:hi].ctypes.data_as(C.c_void_p))
-        if self.be.is_oracle and n >= 65536:          # the oracle walks the rows on the calling thread: split them over a few
-            cuts = np.linspace(0, n, 9).astype(int)
-            with ThreadPoolExecutor(8) as ex:
-                rcs = list(ex.map(lambda k: part(cuts[k], cuts[k + 1]), range(8)))
-        else:
-            rcs = [part(0, n)]
-        for rc in rcs:
-            self.be.check(rc)
-        return out
+        return run_rows(self.be, lambda pin, n, pout: self.fn(self.scene.handle, self.light, int(via_env0), pin, n, pout), rows, NIN, NOUT)
 
     def __call__(self, rows, via_env0=0):
         return unpack(self.raw(rows, via_env0))

@@ -3,11 +3,11 @@ fed to the hooks (ftn_test_texture_eval / orc_test_texture_eval, ftn_test_materi
 orc_test_mipmap_level), the measured tolerances and the property checks, so that both sides face the same seeds and the same bounds.
 DESIGN.md 3.4."""
 import ctypes as C
-from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
 import _texture_ref as X
+from _rows import run_rows
 from fountain_amd import SceneBuilder, _abi as A
 
 f32 = np.float32
@@ -137,19 +137,7 @@ class Hook:
         return [("tex", k) for k in self.tex] + [("mat", k) for k in self.mat]
 
     def _run(self, fn, index, rows, width):
-        rows = np.ascontiguousarray(rows, f32).reshape(-1, 6)
-        n = rows.shape[0]
-        out = np.empty((n, width), f32)
-
-        def part(lo, hi):
-            assert fn(self.scene.handle, index, rows[lo:hi].ctypes.data_as(C.c_void_p), hi - lo, out[lo:hi].ctypes.data_as(C.c_void_p)) == 0
-        if self.be.is_oracle and n >= 65536:          # the oracle walks the rows on the calling thread: split them over a few
-            cuts = np.linspace(0, n, 9).astype(int)
-            with ThreadPoolExecutor(8) as ex:
-                list(ex.map(lambda k: part(cuts[k], cuts[k + 1]), range(8)))
-        else:
-            part(0, n)
-        return out
+        return run_rows(self.be, lambda pin, n, pout: fn(self.scene.handle, index, pin, n, pout), rows, 6, width)
 
     def eval(self, tex, rows):
         return self._run(self.f_tex, self.tex[tex], rows, 3)

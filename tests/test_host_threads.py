@@ -1,4 +1,4 @@
-"""ftn_scene_create's host passes run on several threads for large scenes (parallel_for / ParallelBvh, ftn_host.cpp).  Every pass
+"""ftn_scene_create's host passes run on several threads for large scenes (parallel_for / ParallelBvh, ftn_scene_host.cpp and ftn_bvh_host.cpp).  Every pass
 writes an element from that element's inputs alone, so the arrays must not depend on the thread count: the BVH (nodes, primitive
 order), the four-box records and the eight-box records of a 300 k-triangle scene with FTN_BVH_THREADS=1 and =7, byte for byte.  CPU only
 (the host-only entry points of the C ABI)."""

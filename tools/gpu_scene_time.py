@@ -1,4 +1,4 @@
-import os, sys, time
+import os, resource, sys, time
 sys.path.insert(0, os.getcwd())
 from fountain_amd import default_backend, scenes
 gpu = default_backend()
@@ -8,3 +8,4 @@ t1 = time.time()
 sc = b.create_scene()
 t2 = time.time()
 print("python scene description %.2f s, create_scene %.2f s" % (t1 - t0, t2 - t1), flush=True)
+print("Maximum resident set size (kbytes): %d" % resource.getrusage(resource.RUSAGE_SELF).ru_maxrss, flush=True)
