@@ -255,6 +255,30 @@ FTN_BLOOM_KARIS = 1
 FTN_BLOOM_MAX_LEVELS = 12
 FTN_BLOOM_ABI_VERSION = 1    # include/fountain_hip_bloom.h (an extension with a version of its own)
 
+class ftn_metrics_params(C.Structure):
+    """include/fountain_hip_metrics.h: parameters of the measuring stage (ftn_metrics_params_default fills the defaults)."""
+    _fields_ = [("flags", c_u32), ("peak", c_f), ("rel_eps", c_f), ("reserved", c_u32)]
+
+
+class ftn_metrics_totals(C.Structure):
+    """include/fountain_hip_metrics.h: what the device writes (the eight sums SE, AE, REL, SM, SE_r, SE_g, SE_b, SSIM; the largest
+    difference and its pixel; the counts)."""
+    _fields_ = [("sum", C.c_double * 8), ("max_abs", C.c_double), ("max_abs_index", C.c_uint64), ("n_pixels", C.c_uint64),
+                ("n_nonfinite", C.c_uint64), ("n_different", C.c_uint64), ("n_ssim_windows", C.c_uint64)]
+
+
+class ftn_metrics_result(C.Structure):
+    """include/fountain_hip_metrics.h: what ftn_metrics_resolve makes of the totals."""
+    _fields_ = [("mse", C.c_double), ("rmse", C.c_double), ("mae", C.c_double), ("rel_mse", C.c_double), ("smape", C.c_double),
+                ("psnr", C.c_double), ("ssim", C.c_double), ("mse_rgb", C.c_double * 3), ("max_abs", C.c_double),
+                ("max_abs_index", C.c_uint64), ("n_pixels", C.c_uint64), ("n", C.c_uint64), ("n_nonfinite", C.c_uint64),
+                ("n_different", C.c_uint64), ("n_ssim_windows", C.c_uint64)]
+
+
+FTN_METRICS_SSIM = 1
+FTN_METRICS_TILE, FTN_METRICS_SUMS, FTN_METRICS_SSIM_TAPS = 16, 8, 11
+FTN_METRICS_ABI_VERSION = 1  # include/fountain_hip_metrics.h (an extension with a version of its own)
+
 FTN_SUBDIV_MAX_LEVELS = 10
 FTN_SUBDIV_MAX_FACES = 1 << 26
 FTN_SUBDIV_ABI_VERSION = 1   # include/fountain_hip_subdiv.h (an extension with a version of its own)
@@ -277,6 +301,7 @@ SIZES = {
     "ftn_gbuffer_pixel": 48, "ftn_denoise_params": 32, "ftn_denoise_guided_params": 32, "ftn_moment_pixel": 16, "ftn_adaptive_params": 16, "ftn_adaptive_info": 24,
     "ftn_temporal_pixel": 32, "ftn_temporal_params": 32, "ftn_filter_desc": 32, "ftn_display_params": 48, "ftn_display_info": 32,
     "ftn_bloom_params": 32, "ftn_subdiv_info": 184,
+    "ftn_metrics_params": 16, "ftn_metrics_totals": 112, "ftn_metrics_result": 136,
 }
 
 # Every function the header declares (name -> None); used by the symbol-export test.
@@ -393,6 +418,21 @@ BLOOM_PROTOTYPES = {
     "ftn_bloom_abi_version": ([], C.c_int),
 }
 BLOOM_FUNCTIONS = sorted(BLOOM_PROTOTYPES)
+
+# Every function the extension header include/fountain_hip_metrics.h declares (kept apart from the lists above: the reference compares
+# no images, so these have no orc_* twin either), with its prototype: name -> (argument types, result type).
+_PAIR = [C.c_void_p, C.c_void_p, c_i32, c_i32, C.c_void_p]      # test, ref, w, h, params
+METRICS_PROTOTYPES = {
+    "ftn_metrics_params_default": ([C.c_void_p], None),
+    "ftn_metrics_workspace_size": ([c_i32, c_i32, c_u32, C.c_void_p], C.c_int),
+    "ftn_metrics_ssim_weights": ([C.c_void_p], C.c_int),
+    "ftn_metrics": (_PAIR + [C.c_void_p] * 5 + [c_i32], C.c_int),
+    "ftn_metrics_device": (_PAIR + [C.c_void_p] * 6, C.c_int),
+    "ftn_metrics_resolve": ([C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
+    "ftn_metrics_cpu": (_PAIR + [C.c_void_p] * 5, C.c_int),
+    "ftn_metrics_abi_version": ([], C.c_int),
+}
+METRICS_FUNCTIONS = sorted(METRICS_PROTOTYPES)
 
 # Every function the extension header include/fountain_hip_subdiv.h declares (kept apart from the lists above: the reference's
 # loop_subdiv.rs ends in unimplemented!(), so these have no orc_* twin either), with its prototype: name -> (argument types, result type).

@@ -1,5 +1,5 @@
 """Helpers shared by the bindings of the calls the CPU oracle has no twin of: the render passes (gbuffer.py, moments.py, adaptive.py) and
-the image-space stages (denoise.py, temporal.py, display.py, bloom.py)."""
+the image-space stages (denoise.py, temporal.py, display.py, bloom.py, metrics.py)."""
 import ctypes as C
 
 import numpy as np

@@ -35,6 +35,10 @@ display options need --png, and --png renders on one GPU.  The OpenEXR files are
 bloomed image's, its histogram and so the automatic exposure included, and the denoised images' .png files are bloomed too before they
 are encoded at that exposure.  <name>.exr and every other file stay the same bytes.  --bloom needs --png and one GPU, and its
 sub-options need --bloom.
+--compare-to REF.exr [--ssim] measures the image just written against REF.exr (fountain_amd/metrics.py) and prints the line of
+`python -m fountain_amd.metrics`: RMSE, MSE, MAE, relMSE, SMAPE, PSNR, the largest difference, with --ssim SSIM, and how many pixels
+differ.  REF.exr must exist and have the film's size, and the option renders on one GPU; all of that is checked before anything is
+rendered.  It writes no file, and without it nothing changes.
 """
 import argparse
 import sys
@@ -71,7 +75,20 @@ def main(argv=None):
     add_display_arguments(ap)
     from . import bloom as B
     B.add_arguments(ap)
+    ap.add_argument("--compare-to", default=None, metavar="REF.exr", help="measure the image against this OpenEXR file and print the error measures")
+    ap.add_argument("--ssim", action="store_true", help="with --compare-to: SSIM as well")
     opts = ap.parse_args(argv)
+    if opts.ssim and opts.compare_to is None:
+        print("error: --ssim belongs to --compare-to", file=sys.stderr)
+        return 2
+    if opts.compare_to is not None:
+        import os.path
+        if opts.gpus is not None:
+            print("error: --compare-to measures on one GPU: leave out --gpus", file=sys.stderr)
+            return 2
+        if not opts.compare_to.endswith(".exr") or not os.path.isfile(opts.compare_to):
+            print("error: --compare-to takes an existing .exr file, not %s" % opts.compare_to, file=sys.stderr)
+            return 2
     if B.refusal(opts):
         print("error: %s" % B.refusal(opts), file=sys.stderr)
         return 2
@@ -130,6 +147,9 @@ def main(argv=None):
             "--denoise-guided" if opts.denoise_guided else "--adaptive" if opts.adaptive is not None else "--pixel-filter"
         print("error: %s renders on one GPU, not under a launcher of %d ranks" % (flag, world), file=sys.stderr)
         return 2
+    if opts.compare_to is not None and world > 1:
+        print("error: --compare-to measures on one GPU, not under a launcher of %d ranks" % world, file=sys.stderr)
+        return 2
     if opts.gpus is not None and opts.gpus != world:
         print("error: --gpus %d but the launcher started WORLD_SIZE %d ranks" % (opts.gpus, world), file=sys.stderr)
         return 2
@@ -141,6 +161,13 @@ def main(argv=None):
     filename = opts.image_name or parsed.film_name
     if ".exr" not in filename:
         raise SystemExit("output must be an .exr file (render.rs:53)")
+    if opts.compare_to is not None:
+        from . import metrics as M
+        size, want = M.exr_size(opts.compare_to, be), parsed.film()
+        if size != (want.width, want.height) or (opts.ssim and min(size) < A.FTN_METRICS_SSIM_TAPS):
+            print("error: --compare-to %s: %s, the film is %d x %d%s" % (opts.compare_to, "%d x %d pixels" % size if size else "not a readable OpenEXR file",
+                                                                         want.width, want.height, " (--ssim needs at least 11 x 11)" if opts.ssim else ""), file=sys.stderr)
+            return 2
     sampler = parsed.sampler(opts.samples, indexed=not opts.exact_stream)
     if opts.denoise_guided and sampler.desc.samples_per_pixel < 2:
         print("error: --denoise-guided needs at least 2 samples per pixel: a pixel's variance is unknown below that (here %d)"
@@ -218,6 +245,10 @@ def main(argv=None):
     print("Completed rendering in %.3f s (%.1f Mrays/s%s)" % (dt, rays / dt / 1e6, " on rank 0 of %d" % world if world > 1 else ""), file=sys.stderr)
     img, (w, h) = film.into_spectrum_buffer()
     write_exr(filename, img, be)
+    if opts.compare_to is not None:
+        from .api import read_exr
+        r = M.compare(be, img, read_exr(opts.compare_to, be), M.MetricsParams(be, ssim=opts.ssim), device=opts.gpu)
+        print("metrics: " + M.report_line(r, opts.ssim))
     bloom_params = B.params_from_arguments(be, opts) if opts.bloom is not None else None
     bloomed = (lambda a: B.bloom(be, a, bloom_params, device=opts.gpu)) if bloom_params else (lambda a: a)
     shown = bloomed(img)
