@@ -93,7 +93,8 @@ struct DScene {
     uint32_t material_types;                /* bit t set: some material has ftn_material.type == t */
     /* scenes lit by ONE light that is an InfiniteAreaLight (the usual environment-lit scene): its record also travels in the kernel
      * arguments, so the shading kernels specialised for it (k_wf_shade<.., ENV>) read it with scalar loads and drop the other kinds */
-    uint32_t env_only, _pad2;
+    uint32_t env_only;
+    uint32_t null_prims;                    /* 1: some primitive has shading class 7 (no material: its paths pass through, path.rs:77-81) */
     DLight env0;
     /* shading records (NULL: not built): everything make_interaction needs about a primitive in ONE 128-byte line, instead of
      * geom (48 B) + prim_info (2 x 16 B) + three normals and three uvs gathered through the vertex indices (5-9 lines for a hit at a

@@ -208,7 +208,7 @@ int wavefront_gbuffer(WavefrontState** state, const RenderParams& P, const std::
     const uint32_t S = plan.samples;
     if ((rc = trace4_prepare(st, P.S))) return rc;
     WfBuffers W = st->W;
-    W.br = nullptr; W.pd = nullptr; W.pd_md = 0; W.pd_occ = 0; W.drain_sig = nullptr; W.drain_seq = 0; W.serial = 0; W.rng_replay = 0; W.mis_any = 0;
+    W.br = nullptr; W.pd = nullptr; W.pd_md = 0; W.pd_occ = 0; W.drain_sig = nullptr; W.drain_seq = 0; W.serial = 0; W.rng_replay = 0; W.mis_any = 0; W.late_finish = 0;
     W.gen_blocks = knob("FTN_GEN_BLOCKS", 1);
     uint32_t valid = 0; for (const DTile& t : tiles) valid += (uint32_t)((t.x1 - t.x0) * (t.y1 - t.y0));
     W.valid_per_sample = valid;

@@ -203,7 +203,7 @@ struct Upload {
     std::vector<float4> geom; std::vector<uint4> info; std::vector<uint8_t> leaf_end;     /* per primitive in BVH order: leaf-test records, prim_info, last of its leaf */
     std::vector<ftn_material> mats; std::vector<DLight> lights; std::vector<uint32_t> inf;
     uint32_t n_fat = 0, n_quads = 0, quad_bound = 0, n_quad64 = 0, quad64_bound = 0, n_octs = 0, oct_bound = 0;
-    bool geom_in_srec = false, has_tex = false;
+    bool geom_in_srec = false, has_tex = false, null_prims = false;      /* null_prims: some primitive has shading class 7 (prim_classes) */
     Upload(const ftn_scene_desc* d_, ftn_scene* sc_, const SceneKnobs& k) : d(d_), sc(sc_), hs(sc_->host), knobs(k), np(sc_->host.order.size()) {}
 };
 
@@ -405,6 +405,8 @@ static int spheres_and_materials(Upload& U) {
 static int prim_classes(Upload& U) {
     std::vector<unsigned char> cls(U.np);
     for (size_t i = 0; i < U.np; i++) { const int m = (int)U.info[2 * i].x; cls[i] = (unsigned char)(m < 0 || (size_t)m >= U.mats.size() ? 7u : std::min<uint32_t>(2u + U.mats[(size_t)m].type, 7u)); }
+    U.null_prims = false;
+    for (const unsigned char c : cls) if (c == 7u) U.null_prims = true;
     return U.sc->prim_class.upload(cls.data(), cls.size());
 }
 
@@ -532,7 +534,7 @@ static void fill_dscene(Upload& U) {
     D.nodes = sc->nodes.p; D.geom = U.geom_in_srec ? sc->srec.p : sc->geom.p; D.geom_stride = U.geom_in_srec ? 8u : (uint32_t)FTN_GS; D.prim_info = sc->prim_info.p; D.N = sc->N.p; D.UV = sc->UV.p; D.T = sc->T.p; D.spheres = sc->spheres.p;
     D.materials = sc->materials.p; D.lights = sc->lights.p; D.inf_lights = sc->inf_lights.p;
     D.n_nodes = (uint32_t)hs.nodes.size(); D.n_prims = (uint32_t)U.np; D.n_lights = (uint32_t)U.lights.size(); D.n_inf_lights = (uint32_t)U.inf.size(); D.n_spheres = U.d->n_spheres;
-    D.srec = sc->srec.p; D.prim_class = sc->prim_class.p;
+    D.srec = sc->srec.p; D.prim_class = sc->prim_class.p; D.null_prims = U.null_prims ? 1u : 0u;
     D.quad = sc->quad.p; D.n_quads = U.n_quads; D.quad_stack_bound = U.quad_bound;
     D.oct = sc->oct.p; D.oct_xbox = sc->oct_xbox.p; D.n_octs = U.n_octs; D.oct_stack_bound = U.oct_bound;
     D.quad64 = sc->quad64.p; D.quad64_xbox = sc->quad64_xbox.p; D.n_quad64 = U.n_quad64; D.quad64_stack_bound = U.quad64_bound;

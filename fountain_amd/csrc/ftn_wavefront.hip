@@ -20,7 +20,10 @@
  *                    material type present, BSDF code specialised at compile time; ENV: the scene's only light is an
  *                    InfiniteAreaLight whose record travels in the kernel arguments.
  *   k_wf_ray_keys + rocPRIM radix sort: orders the closest-hit queue by Morton(origin cell) | direction octant (coherence)
- *   k_wf_accumulate  Film::add_sample_to_tile for the pass's samples of each pixel IN SAMPLE ORDER (film.rs:136-172).
+ *   k_wf_accumulate  Film::add_sample_to_tile for the pass's samples of each pixel IN SAMPLE ORDER (film.rs:136-172).  In an environment-lit
+ *                    scene it also finishes the paths (late finish, WfBuffers::late_finish): an ended path is not queued again for its
+ *                    pending direct term and a path whose ray escaped or that reached max_depth leaves the queues in k_wf_classify; this
+ *                    kernel adds what their radiance still needs (wf_finish_path) while it reads the paths in order.
  *
  * Small wavefronts (<= 32 Mi paths) run the any-hit trace of a bounce on a second stream beside the closest-hit trace.
  *
@@ -361,7 +364,7 @@ __device__ inline uint32_t wf_class_of(const RenderParams& P, const WfBuffers& W
  * atomic per class and round the kernel ran at the rate of same-address atomics (65 k of them on the busiest counter) -- and
  * then writes its paths.  The shade kernel derives the 256-aligned virtual layout from the 8 counts itself. */
 #define WF_CLS_ROUNDS 32
-__global__ void __launch_bounds__(256) k_wf_classify(RenderParams P, WfBuffers W, int in_q) {
+__global__ void __launch_bounds__(256) k_wf_classify(RenderParams P, WfBuffers W, int in_q, uint32_t drop /* classes whose entries leave the queues here (late finish) */) {
     __shared__ unsigned char s_cls[WF_CLS_ROUNDS][256];
     __shared__ uint32_t s_cnt[WF_CLS_ROUNDS][WF_NCLASS][4];        /* per round, class, wave */
     __shared__ uint32_t s_pre[WF_CLS_ROUNDS][WF_NCLASS];           /* slots of the class used by earlier rounds of this workgroup */
@@ -374,7 +377,7 @@ __global__ void __launch_bounds__(256) k_wf_classify(RenderParams P, WfBuffers W
         for (uint32_t r = 0; r < nr; r++) {                        /* 1: classify */
             const uint32_t qi = (r0 + r) * stride + blockIdx.x * 256u + threadIdx.x;
             uint32_t c = WF_NCLASS;
-            if (qi < count) c = wf_class_of(P, W, W.q_active[in_q][qi]);
+            if (qi < count) { c = wf_class_of(P, W, W.q_active[in_q][qi]); if ((drop >> c) & 1u) c = WF_NCLASS; }
             s_cls[r][threadIdx.x] = (unsigned char)c;
 #pragma unroll
             for (int k = 0; k < WF_NCLASS; k++) {
@@ -418,6 +421,36 @@ __global__ void __launch_bounds__(256) k_wf_classify(RenderParams P, WfBuffers W
 #ifndef FTN_SHADE_WAVES_OTHER
 #define FTN_SHADE_WAVES_OTHER 3
 #endif
+/* ---- finishing a path: the terminal arithmetic of a shading event, values in and radiance out (no struct of floats goes through a
+ * reference: DESIGN section 5, round 3 item 2).  k_wf_shade runs the two steps around its own work; wf_finish_path is the two in a row for
+ * a path that nothing else happens to, which k_wf_accumulate runs under late finish (WfBuffers::late_finish): one source for every float
+ * operation, and the order per path stays L + direct, then L + beta * Le. */
+/* the pending estimate_direct of the previous bounce (integrator/mod.rs:330-392): q0 = {Ld_light, mis weight}, q1 = {f, pdf}, q2 = {beta_prev};
+ * shadow_lit: a shadow ray was traced and found nothing; inc: what arrives along the MIS ray (black: no such ray, occluded, or no light there) */
+__device__ inline Rgb wf_add_direct(Rgb L, bool shadow_lit, float4 q0, float4 q1, float4 q2, Rgb inc, uint32_t n_lights) {
+    Rgb radiance(0.0f);
+    if (shadow_lit) radiance = radiance + Rgb(q0.x, q0.y, q0.z);
+    if (!inc.is_black()) radiance = radiance + Rgb(q1.x, q1.y, q1.z) * inc * q0.w / q1.w;
+    Rgb direct = Rgb(q2.x, q2.y, q2.z) * ((float)n_lights * radiance);
+    return L + direct;
+}
+/* what a camera ray or a specular bounce sees where it ends (path.rs:45-58): e = emitted radiance of the surface hit / of the environment */
+__device__ inline Rgb wf_add_seen(Rgb L, Rgb beta, Rgb e) { return L + beta * e; }
+template <bool ENV> __device__ inline Rgb wf_escaped_Le(const DScene& S, V3 d) { return ENV ? Rgb(0.0f) + light_Le_env(S.env0, d) : scene_env_Le(S, d); }
+/* A path of an environment-only scene whose MIS rays went through the any-hit kernels (PS_MIS_ANY, results in q3.w: store_occluded), from its
+ * br record {beta, ps} {L, -} and pd record q0..q3 once every ray of it has been traced.  Still PS_ALIVE: its last ray escaped (hit = false,
+ * d = the ray's direction) or it reached max_depth (k_wf_classify's class 1), and nothing but what that ray sees is left to add. */
+__device__ inline Rgb wf_finish_path(const DScene& S, Rgb beta, Rgb L, uint32_t ps, float4 q0, float4 q1, float4 q2, float4 q3, bool hit, V3 d) {
+    if (ps & PS_DIRECT) {
+        const uint32_t occ_word = __float_as_uint(q3.w);
+        Rgb inc(0.0f);
+        if ((ps & PS_MIS_ANY) && !((occ_word & 0xff00u) != 0u)) inc = light_Le_env(S.env0, V3(q3.x, q3.y, q3.z));
+        L = wf_add_direct(L, (ps & PS_SHADOW) && !((occ_word & 0xffu) != 0u), q0, q1, q2, inc, S.n_lights);
+    }
+    if ((ps & PS_ALIVE) && ((ps & PS_BOUNCE_MASK) == 0u || (ps & PS_SPECULAR) != 0u)) L = wf_add_seen(L, beta, hit ? Rgb(0.0f) : wf_escaped_Le<true>(S, d));
+    return L;
+}
+
 /* MT: -1 = every class in `class_mask`, material type read at run time (textured scenes);  0..4 = ONE material class, its BSDF code
  * specialised at compile time (fewer registers: 3 waves/SIMD instead of 2, 4 for mirrors);  -2 = the classes without a BSDF
  * (finished paths, misses / depth limit, null materials), the material branch compiled out. */
@@ -462,21 +495,18 @@ __global__ void __launch_bounds__(256, (MT == -1 ? FTN_SHADE_MIN_WAVES : (MT == 
                 float4 q0, q1, q2, q3 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
                 if (W.pd) { const float4* Q = W.pd + 4 * (size_t)p; q0 = Q[0]; q1 = Q[1]; q2 = Q[2]; if (W.pd_md) q3 = Q[3]; } else { q0 = W.pend0[p]; q1 = W.pend1[p]; q2 = W.pend2[p]; }
                 const uint32_t occ_word = __float_as_uint(q3.w);      /* pd_occ: the any-hit results of this path's two rays (store_occluded) */
-                Rgb radiance(0.0f);
-                if ((ps & PS_SHADOW) && !(W.pd_occ ? (occ_word & 0xffu) != 0u : W.occluded[p] != 0)) radiance = radiance + Rgb(q0.x, q0.y, q0.z);
+                const bool shadow_lit = (ps & PS_SHADOW) && !(W.pd_occ ? (occ_word & 0xffu) != 0u : W.occluded[p] != 0);
+                Rgb inc(0.0f);                                   /* what arrives along the MIS ray */
                 if (ps & PS_MIS_ANY) {                           /* infinite light: the BSDF-sampled ray either escapes to it or contributes nothing (mod.rs:367-384) */
                     const int light_index = (int)__float_as_uint(lq.w);
                     const DLight& Lt = ENV ? S.env0 : S.lights[light_index];
                     const float4 md = W.pd_md ? q3 : W.ray[2 * (size_t)(p + W.n_paths) + 1];
-                    Rgb inc(0.0f);
                     if (!(W.pd_occ ? (occ_word & 0xff00u) != 0u : W.occluded[p + W.n_paths] != 0)) inc = light_Le_env(Lt, V3(md.x, md.y, md.z));
-                    if (!inc.is_black()) radiance = radiance + Rgb(q1.x, q1.y, q1.z) * inc * q0.w / q1.w;
                 } else if (ps & PS_MIS) {
                     const int light_index = (int)__float_as_uint(lq.w);
                     const DLight& Lt = ENV ? S.env0 : S.lights[light_index];
                     const DHit mh = load_hit(W, p + W.n_paths);
                     const float4 mo = W.ray[2 * (size_t)(p + W.n_paths)], md = W.ray[2 * (size_t)(p + W.n_paths) + 1];
-                    Rgb inc(0.0f);
                     if (mh.prim >= 0) {
                       if (!ENV) {                                /* ENV: no primitive carries an area light */
                         int h_mat, h_light; prim_mat_light(S, mh.prim, &h_mat, &h_light);
@@ -487,10 +517,8 @@ __global__ void __launch_bounds__(256, (MT == -1 ? FTN_SHADE_MIN_WAVES : (MT == 
                         }
                       }
                     } else if (ENV || Lt.kind == LK_INFINITE) inc = light_Le_env(Lt, V3(md.x, md.y, md.z));
-                    if (!inc.is_black()) radiance = radiance + Rgb(q1.x, q1.y, q1.z) * inc * q0.w / q1.w;
                 }
-                Rgb direct = Rgb(q2.x, q2.y, q2.z) * ((float)S.n_lights * radiance);
-                L = L + direct;
+                L = wf_add_direct(L, shadow_lit, q0, q1, q2, inc, S.n_lights);
                 ps &= ~(PS_DIRECT | PS_SHADOW | PS_MIS | PS_MIS_ANY);
             }
             if (!(ps & PS_ALIVE)) {
@@ -517,8 +545,8 @@ __global__ void __launch_bounds__(256, (MT == -1 ? FTN_SHADE_MIN_WAVES : (MT == 
                     if (hit) {
                         Rgb e(0.0f);
                         if (!ENV && si.light >= 0) e = area_Le(S.lights[si.light], si.hit.n, -ray0.d);
-                        L = L + beta * e;
-                    } else L = L + beta * (ENV ? Rgb(0.0f) + light_Le_env(S.env0, ray0.d) : scene_env_Le(S, ray0.d));
+                        L = wf_add_seen(L, beta, e);
+                    } else L = wf_add_seen(L, beta, wf_escaped_Le<ENV>(S, ray0.d));
                 }
                 bool alive = true;
                 uint32_t light_word = 0;
@@ -646,9 +674,9 @@ __global__ void __launch_bounds__(256, (MT == -1 ? FTN_SHADE_MIN_WAVES : (MT == 
                     else if (alive || W.serial) { W.rng01[p] = make_ulonglong2(rng.s0, rng.s1); W.rng23[p] = make_ulonglong2(rng.s2, rng.s3); }      /* (an ended path draws nothing more; the tile-serial stream goes on behind it) */
                 }
                 ps = (ps & ~(PS_BOUNCE_MASK | PS_ALIVE)) | (bounces & PS_BOUNCE_MASK) | (alive ? PS_ALIVE : 0u);
-                push_active = alive || (ps & PS_DIRECT);        /* finished paths with a pending direct term come back once */
+                push_active = alive || (!W.late_finish && (ps & PS_DIRECT));        /* finished paths with a pending direct term come back once (late finish: k_wf_accumulate resolves it) */
                 if (W.br) {
-                    if (push_active) { W.br[2 * (size_t)p] = make_float4(beta.r, beta.g, beta.b, __uint_as_float(ps)); W.br[2 * (size_t)p + 1] = make_float4(L.r, L.g, L.b, __uint_as_float(light_word)); }
+                    if (push_active || W.late_finish) {      /* (late finish: the record of an ended path is what k_wf_accumulate reads) */ W.br[2 * (size_t)p] = make_float4(beta.r, beta.g, beta.b, __uint_as_float(ps)); W.br[2 * (size_t)p + 1] = make_float4(L.r, L.g, L.b, __uint_as_float(light_word)); }
                     else W.rad[p] = make_float4(L.r, L.g, L.b, 0.0f);
                 } else {
                     if (push_active) W.beta[p] = make_float4(beta.r, beta.g, beta.b, __uint_as_float(ps));        /* (a retired path's throughput is never read again) */
@@ -961,10 +989,15 @@ __global__ void k_wf_reset(WfBuffers W, int mode, int in_q, DevStats* stats) {
 /* ------------------------------------------------------------------ accumulate: add_sample_to_tile in sample order */
 /* One thread per pixel slot adds its samples in sample order (film.rs:127-130 is order dependent in the last bit).  The samples of a
  * slot are neighbours in memory (path id = slot * samples + s), so a thread reading its own run would touch one cache line per lane and
- * load; the workgroup stages 8 samples of its 256 slots through LDS with coalesced loads instead. */
+ * load; the workgroup stages 8 samples of its 256 slots through LDS with coalesced loads instead.
+ * Late finish (WfBuffers::late_finish): the staging phase does not read a finished radiance but the path's records -- br always, pd when a
+ * direct term is pending, hit_prim when the path was dropped alive, the ray's direction when the environment along it is needed -- and
+ * finishes the path (wf_finish_path).  The same dense walk, ~100 instead of 16 bytes per path: 1.7 -> 6.3 ms per step of the benchmark
+ * against 12.9 ms of scattered shade launches it replaces (profiles/late_finish).  The second phase is the same either way. */
 #define WF_ACC_CHUNK 8u
 __global__ void __launch_bounds__(256) k_wf_accumulate(RenderParams P, WfBuffers W) {
     __shared__ float4 s_rad[256 * WF_ACC_CHUNK];
+    __shared__ unsigned char s_valid[256];
     const uint32_t slot = blockIdx.x * 256u + threadIdx.x;
     uint32_t spill = 0, bc = 0, cam = 0; int err = 0;
     const FilmSlot fs = film_slot(P, W.n_slots, slot);
@@ -972,12 +1005,32 @@ __global__ void __launch_bounds__(256) k_wf_accumulate(RenderParams P, WfBuffers
     float4 acc = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     if (in_crop) acc = P.accA[ai];
     const size_t block_first = (size_t)blockIdx.x * 256u * W.samples;          /* first path of this workgroup's 256 slots */
+    if (W.late_finish) { s_valid[threadIdx.x] = valid ? 1 : 0; __syncthreads(); }
     for (uint32_t s0 = 0; s0 < W.samples; s0 += WF_ACC_CHUNK) {
         const uint32_t n = W.samples - s0 < WF_ACC_CHUNK ? W.samples - s0 : WF_ACC_CHUNK;
         for (uint32_t e = threadIdx.x; e < 256u * n; e += 256u) {                /* n consecutive samples of slot e / n */
             const uint32_t sl = e / n, k = e - sl * n;
             const size_t p = block_first + (size_t)sl * W.samples + s0 + k;
-            if (p < W.n_paths) s_rad[sl * WF_ACC_CHUNK + k] = W.rad[p];
+            if (p >= W.n_paths) continue;
+            if (!W.late_finish) { s_rad[sl * WF_ACC_CHUNK + k] = W.rad[p]; continue; }
+            /* late finish: the path's records as its last shading event and the traces behind it left them; consecutive threads read
+             * consecutive records.  (A slot outside its tile has no path: its records are whatever an earlier pass left.) */
+            float4 r = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            if (s_valid[sl]) {
+                const float4 bq = W.br[2 * p], lq = W.br[2 * p + 1];
+                const uint32_t ps = __float_as_uint(bq.w);
+                float4 q0 = r, q1 = r, q2 = r, q3 = r;
+                if (ps & PS_DIRECT) { const float4* Q = W.pd + 4 * p; q0 = Q[0]; q1 = Q[1]; q2 = Q[2]; q3 = Q[3]; }
+                bool hit = false; V3 d(0.0f, 0.0f, 1.0f);
+                if (ps & PS_ALIVE) {                                             /* dropped by k_wf_classify: escaped, or at max_depth */
+                    hit = W.hit_prim[p] >= 0;
+                    if (!hit && ((ps & PS_BOUNCE_MASK) == 0u || (ps & PS_SPECULAR) != 0u)) { const float4 rdv = W.ray[2 * p + 1]; d = V3(rdv.x, rdv.y, rdv.z); }
+                }
+                const Rgb L = wf_finish_path(P.S, Rgb(bq.x, bq.y, bq.z), Rgb(lq.x, lq.y, lq.z), ps, q0, q1, q2, q3, hit, d);
+                r = make_float4(L.r, L.g, L.b, 0.0f);
+            }
+            if (W.late_finish == 2u) W.rad[p] = r;                               /* a pass hook reads the pass's radiance there */
+            s_rad[sl * WF_ACC_CHUNK + k] = r;
         }
         __syncthreads();
         if (valid) {
@@ -1426,7 +1479,7 @@ static int wavefront_render_serial(WavefrontState* st, const RenderParams& P, ui
     WfBuffers W = st->W;
     W.serial = 1; W.ser_cursor = (uint2*)st->ser_mem[0]; W.ser_pfilm = (float2*)st->ser_mem[1]; W.ser_retired = (unsigned char*)st->ser_mem[2]; W.dfd = (float4*)st->ser_mem[3];
     W.n_slots = 0; W.samples = 1; W.n_paths = n_tiles; W.first_sample = 0; W.seg_cap = (uint32_t)st->cap_paths; W.valid_per_sample = 0;
-    W.gen_blocks = 0; W.rng_replay = 0; W.br = nullptr; W.pd = nullptr; W.pd_md = 0; W.pd_occ = 0;
+    W.gen_blocks = 0; W.rng_replay = 0; W.br = nullptr; W.pd = nullptr; W.pd_md = 0; W.pd_occ = 0; W.late_finish = 0;
     const int count_mode = count ? (count_production ? 2 : 1) : 0;
     W.mis_any = ((!count || count_production) && knob("FTN_MIS_ANY", 1)) ? 1u : 0u;
     const bool spheres = P.S.n_spheres != 0;
@@ -1457,7 +1510,7 @@ static int wavefront_render_serial(WavefrontState* st, const RenderParams& P, ui
         if (it > 0 && !beside) launch_trace(st, true, count_mode, spheres, tg, lds, stream, P, W, W.q_shadow, &W.counters[CTR(3)], &W.counters[CTR(24)], 2 * n_tiles);
         if (beside) WF_TRY(hipStreamWaitEvent(stream, st->ev_side, 0));
         hipLaunchKernelGGL(k_wf_reset, dim3(1), dim3(64), 0, stream, W, 2, in_q, P.stats);
-        hipLaunchKernelGGL(k_wf_classify, sgrid, dim3(256), 0, stream, P, W, in_q);
+        hipLaunchKernelGGL(k_wf_classify, sgrid, dim3(256), 0, stream, P, W, in_q, 0u);
         hipLaunchKernelGGL(k_wf_reset, dim3(1), dim3(64), 0, stream, W, 1, in_q, P.stats);
 #define FTN_SH2(T, M, E, mask) hipLaunchKernelGGL((k_wf_shade<T, M, E>), sgrid, dim3(256), 0, stream, P, W, in_q, mask, 0u)
 #define FTN_SH(M, mask) do { if (tex) { if (env) FTN_SH2(true, M, true, mask); else FTN_SH2(true, M, false, mask); } \
@@ -1541,6 +1594,11 @@ int wavefront_render(WavefrontState** state, const RenderParams& P0, const std::
     W.pd_md = (W.pd && knob("FTN_WF_PD", 3) >= 2) ? 1u : 0u;
     W.pd_occ = (W.pd && knob("FTN_WF_PD", 3) >= 3) ? 1u : 0u;
     W.gen_blocks = knob("FTN_GEN_BLOCKS", 1);      /* camera rays of a full tile queued in 2 x 2 pixel blocks: first closest-hit launch 37.3 -> 36.6 ms */
+    /* FTN_WF_LATE_FINISH (default 1; 0: ended paths come back through the queues): ended paths are finished by k_wf_accumulate instead of by the shade launch
+     * of the classes without a BSDF (WfBuffers::late_finish).  Only where one record per path can say everything: the environment-only
+     * shade variants, MIS rays through the any-hit kernels and their results in the pd record */
+    W.late_finish = (!dl_mode && W.br && W.pd && W.pd_md && W.pd_occ && W.mis_any && P.S.env_only && knob("FTN_SHADE_ENV", 1) && knob("FTN_SHADE_SPECIALISE", 1) &&
+                     knob("FTN_WF_LATE_FINISH", 1)) ? (hook ? 2u : 1u) : 0u;
     const size_t lds = (size_t)P.stack_entries * 256 * sizeof(uint32_t);
     const unsigned blocks_per_cu = (unsigned)std::max<size_t>(1, std::min<size_t>(8, (size_t)(160 * 1024) / std::max<size_t>(lds, 1)));
     const unsigned trace_grid_max = (unsigned)st->n_cu * blocks_per_cu;
@@ -1635,7 +1693,9 @@ int wavefront_render(WavefrontState** state, const RenderParams& P0, const std::
                 const int e_cls = span_begin(stream);
                 const unsigned cg = std::min<unsigned>(shade_grid_max, (W.n_paths + 255) / 256);
                 hipLaunchKernelGGL(k_wf_reset, dim3(1), dim3(64), 0, stream, W, 2, in_q, P.stats);
-                hipLaunchKernelGGL(k_wf_classify, dim3(cg), dim3(256), 0, stream, P, W, in_q);
+                /* late finish: behind the first pass (fresh paths have no br record yet) the classes that only end -- 0: none is queued any more,
+                 * 1: ray escaped / max_depth reached -- leave the queues here; k_wf_accumulate finishes them */
+                hipLaunchKernelGGL(k_wf_classify, dim3(cg), dim3(256), 0, stream, P, W, in_q, (W.late_finish && it > 0) ? 0x3u : 0u);
                 span_end(e_cls, 2, stream);
             }
             /* shading needs the occlusion results (classify above did not).  The shade span starts BEHIND this wait: with the any-hit launch
@@ -1663,7 +1723,8 @@ int wavefront_render(WavefrontState** state, const RenderParams& P0, const std::
                                     hipLaunchKernelGGL((k_wf_shade<T, M, E>), dim3(std::min<unsigned>((unsigned)st->n_cu * per_cu, (W.n_paths + 255) / 256)), dim3(256), 0, stream, P, W, in_q, mask, first); } while (0)
 #define FTN_SH(M, mask) do { if (tex) { if (env) FTN_SH2(true, M, true, mask); else FTN_SH2(true, M, false, mask); } \
                              else { if (env) FTN_SH2(false, M, true, mask); else FTN_SH2(false, M, false, mask); } } while (0)
-                    FTN_SH(-2, 0x83u);
+                    if (!W.late_finish || first) FTN_SH(-2, 0x83u);
+                    else if (P.S.null_prims) FTN_SH(-2, 0x80u);      /* (late finish: only the primitives without a material are left of these classes) */
                     if (P.S.material_types & 1u) FTN_SH(0, 1u << 2);
                     if (P.S.material_types & 2u) FTN_SH(1, 1u << 3);
                     if (P.S.material_types & 4u) FTN_SH(2, 1u << 4);
@@ -1701,6 +1762,14 @@ int wavefront_render(WavefrontState** state, const RenderParams& P0, const std::
                 n_active = st->host_counters[CTR(in_q == 0 ? 0 : 1)];
                 if (n_active == 0) break;
             }
+        }
+        /* late finish: no ended path keeps the queue alive for one more round, so the last round's shadow and MIS rays (a null-material
+         * pass-through can shade beyond round max_depth) may still be waiting: traced here, before k_wf_accumulate reads their results */
+        if (W.late_finish && st->host_counters[CTR(3)] != 0) {
+            if (ev_used + 2 > 64) { rc = flush_events(); if (rc) return rc; }
+            const int e = span_begin(stream);
+            launch_trace(st, true, count_mode, spheres, std::min<unsigned>(trace_grid_max, (2 * W.n_paths + 255) / 256), lds, stream, P, W, q_sh, &W.counters[CTR(3)], &W.counters[CTR(24)], 2 * W.n_paths, false);
+            span_end(e, 1, stream);
         }
         if (W.mis_any) mis_any_rays += st->host_counters[CTR(10)];   /* the last poll of the pass saw the pass's total */
         hipLaunchKernelGGL(k_wf_accumulate, dim3((n_slots + 255) / 256), dim3(256), 0, stream, P, W);

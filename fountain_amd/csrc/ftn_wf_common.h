@@ -66,6 +66,10 @@ struct WfBuffers {
     uint32_t gen_blocks;        /* 1: k_wf_generate queues the pixels of a full 16 x 16 tile in 2 x 2 blocks (Morton order) instead of rows: the 64 rays of a
                                  * wave of the first trace are then a 2 x 2 pixel block at 16 spp, not a 4 x 1 strip.  Queue ORDER only: no result depends on it */
     uint32_t mis_any;           /* 1: MIS rays toward an infinite light only need hit / miss -> any-hit kernel (off in the counting build, whose node tallies must equal the reference's closest-hit walk) */
+    uint32_t late_finish;       /* path integrator, environment-only scenes with br / pd / pd_md / pd_occ / mis_any (FTN_WF_LATE_FINISH): a path that ends is not queued
+                                 * again for its pending direct term, and a path whose ray escaped or that reached max_depth is dropped by k_wf_classify: every
+                                 * path leaves ONE br record (+ pd, hit_prim, ray) that says what its radiance still needs, and k_wf_accumulate adds it
+                                 * (wf_finish_path) while it walks the paths in order anyway.  2: k_wf_accumulate also stores the final radiance in rad[] (pass hooks) */
 };
 
 /* flags in an ACTIVE-queue entry (path ids stay below 2^28: wavefront_render): what k_wf_classify needs to know about the path without
