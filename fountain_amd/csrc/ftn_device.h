@@ -115,7 +115,7 @@ struct DScene {
      * box is not their one triangle's).  Record q here is record q of `quad`; quad64_stack_bound = quad_stack_bound */
     const uint4* quad64; const float4* quad64_xbox;
     uint32_t n_quad64, quad64_stack_bound;
-    /* shading class of every primitive (k_wf_classify, ftn_wavefront.hip): 2 + material type, 7 for a primitive without material.  One
+    /* shading class of every primitive (k_wf_classify, ftn_wf_shade.hip): 2 + material type, 7 for a primitive without material.  One
      * byte per primitive -- cache resident where prim_info (32 bytes per primitive) is not.  Never NULL for a scene with primitives. */
     const unsigned char* prim_class;
 };

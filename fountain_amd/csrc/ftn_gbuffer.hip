@@ -93,8 +93,9 @@ __global__ void __launch_bounds__(256) k_gb_shade(RenderParams P, WfBuffers W, G
 /* between two rounds: the trace kernels' queue heads and hand-back queues, and the count of the queue the next shading pass fills */
 __global__ void k_gb_reset(WfBuffers W, uint32_t out_ctr) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    W.counters[CTR(11)] = 0;
-    for (int i = 16; i < 56; i++) W.counters[CTR(i)] = 0;
+    W.counters[CTR(WFC_DRY_WAVES)] = 0;
+    static_assert(WFC_HEADS_END == WFC_EXC_FIRST, "the two ranges are cleared as one");
+    for (int i = WFC_HEADS_FIRST; i < WFC_EXC_END; i++) W.counters[CTR(i)] = 0;
     W.counters[CTR(out_ctr)] = 0;
 }
 
@@ -215,9 +216,8 @@ int wavefront_gbuffer(WavefrontState** state, const RenderParams& P, const std::
     GbParams G;
     memcpy(G.w2c, w2c, sizeof(G.w2c)); G.out = d_out; G.spillA = spill_a; G.spillB = spill_b; G.spillC = spill_c; G.rec = st->pd;         /* the path integrator's 64-byte records: 3 float4 per path used */
     const bool spheres = P.S.n_spheres != 0, tex = P.S.n_textures != 0;
-    const size_t lds = (size_t)P.stack_entries * 256 * sizeof(uint32_t);
-    const unsigned blocks_per_cu = (unsigned)std::max<size_t>(1, std::min<size_t>(8, (size_t)(160 * 1024) / std::max<size_t>(lds, 1)));
-    const unsigned trace_grid_max = (unsigned)st->n_cu * blocks_per_cu;
+    const size_t lds = wf_trace_lds(P.stack_entries);
+    const unsigned trace_grid_max = wf_trace_grid_max(st, lds);
     double trace_ms = 0.0;
     for (uint32_t s0 = 0; s0 < total_samples; s0 += S) {
         const uint32_t Sp = std::min(S, total_samples - s0);
@@ -227,14 +227,14 @@ int wavefront_gbuffer(WavefrontState** state, const RenderParams& P, const std::
         const unsigned tg = std::min<unsigned>(trace_grid_max, (2 * W.n_paths + 255) / 256);
         uint32_t n_q = Sp * valid;
         for (uint32_t r = 0;; r++) {
-            /* round r traces the queue of round r - 1's pass-throughs; the two queues alternate between q_closest (count CTR(2)) and q_shadow (CTR(3)) */
+            /* round r traces the queue of round r - 1's pass-throughs; the two queues alternate between q_closest (count WFC_CLOSEST) and q_shadow (WFC_SHADOW) */
             const bool odd = (r & 1u) != 0;
             const uint32_t* q_in = odd ? W.q_shadow : W.q_closest;
             uint32_t* q_out = odd ? W.q_closest : W.q_shadow;
-            const uint32_t c_in = odd ? 3u : 2u, c_out = odd ? 2u : 3u;
+            const uint32_t c_in = odd ? WFC_SHADOW : WFC_CLOSEST, c_out = odd ? WFC_CLOSEST : WFC_SHADOW;
             if (r > 0) hipLaunchKernelGGL(k_gb_reset, dim3(1), dim3(64), 0, stream, W, c_out);
             WF_TRY(hipEventRecord(st->ev[0], stream));
-            launch_trace(st, false, 0, spheres, tg, lds, stream, P, W, q_in, &W.counters[CTR(c_in)], &W.counters[CTR(16)], 2 * W.n_paths,
+            launch_trace(st, false, 0, spheres, tg, lds, stream, P, W, q_in, &W.counters[CTR(c_in)], &W.counters[CTR(WFC_HEAD_CLOSEST)], 2 * W.n_paths,
                          r == 0 && W.samples >= knob("FTN_T4_LOCKSTEP_MIN_SPP", 1) /* the camera rays: lockstep parameters, as the beauty's first launch */);
             WF_TRY(hipEventRecord(st->ev[1], stream));
             const dim3 sg(std::max<uint32_t>(1u, (n_q + 255) / 256));

@@ -21,7 +21,7 @@
  *      reference's test multiplies 0 by infinity, and the resulting NaN drops a constraint from the child's test that the parent's
  *      test still has -- a child can pass where its parent fails (tests/test_quad_bvh.py has the cases).  Rays with a non-finite 1/d
  *      component are therefore not walked here at all: the kernel appends them to an exception queue (WfBuffers::q_exc_*) and the
- *      host launches the reference-order kernel (k_wf_trace, ftn_wavefront.hip) over that queue right behind this one.  Jittered
+ *      host launches the reference-order kernel (k_wf_trace, ftn_wf_trace.hip) over that queue right behind this one.  Jittered
  *      camera rays, BSDF-sampled and light-sampled directions practically never qualify; hand-made axis-parallel ray batches do.
  * Any-hit rays (k_wf_trace4_any): t_max never shrinks and only the boolean matters, so order is free and entries need no t0.
  * Triangle-only scenes walk the same records in 64 bytes (k_wf_trace4<.., Q64>, DScene::quad64): boxes quantised outwards, tested
@@ -265,7 +265,7 @@ __global__ void __launch_bounds__(256, (SPHERES ? 1 : (Q64 ? T4Q_WAVES : 5))) k_
             const uint32_t need = (uint32_t)__popcll(idle);
             if (wq_refill(Q, count, head, lane)) {
                 /* the launch starts to drain: let the stream that waits for it (the any-hit trace) go ahead */
-                if (W.drain_sig && lane == 0 && atomicAdd(&W.counters[CTR(11)], 1u) + 1u == W.drain_at)
+                if (W.drain_sig && lane == 0 && atomicAdd(&W.counters[CTR(WFC_DRY_WAVES)], 1u) + 1u == W.drain_at)
                     __hip_atomic_store(W.drain_sig, W.drain_seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);          /* a timing hint only: no data is handed over */
             }
             const uint32_t avail = Q.chunk_end - Q.chunk_next;
@@ -285,7 +285,7 @@ __global__ void __launch_bounds__(256, (SPHERES ? 1 : (Q64 ? T4Q_WAVES : 5))) k_
                 else if (S.root_is_leaf) { L.lp = 0; L.mode = T4_LEAF; }
                 else L.mode = T4_NODE;
             }
-            if (__ballot(hand_back) != 0) wave_push(hand_back, q_entry, W.q_exc_closest, &W.counters[CTR(32)]);
+            if (__ballot(hand_back) != 0) wave_push(hand_back, q_entry, W.q_exc_closest, &W.counters[CTR(WFC_EXC_CLOSEST)]);
             Q.chunk_next += (need < avail ? need : avail);
         }
         const unsigned long long m_node = __ballot(L.mode == T4_NODE), m_leaf = __ballot(L.mode >= T4_LEAF);
@@ -421,7 +421,7 @@ __global__ void __launch_bounds__(256) k_wf_trace4_any(DScene S, WfBuffers W, co
                 else if (S.root_is_leaf) { L.lp = 0; L.mode = T4_LEAF; }
                 else L.mode = T4_NODE;
             }
-            if (__ballot(hand_back) != 0) wave_push(hand_back, q_entry, W.q_exc_any, &W.counters[CTR(33)]);
+            if (__ballot(hand_back) != 0) wave_push(hand_back, q_entry, W.q_exc_any, &W.counters[CTR(WFC_EXC_ANY)]);
             Q.chunk_next += (need < avail ? need : avail);
         }
         const unsigned long long m_node = __ballot(L.mode == T4_NODE), m_leaf = __ballot(L.mode == T4_LEAF);
@@ -553,7 +553,7 @@ __global__ void __launch_bounds__(256) k_wf_trace8_any(DScene S, WfBuffers W, co
                 else if (!slab_test(rlo, rhi, R.o, R.inv, R.t_max)) store_occluded(W, rid, false);       /* the root's own box (bvh.rs:228 at node 0) */
                 else L.mode = T8_NODE;
             }
-            if (__ballot(hand_back) != 0) wave_push(hand_back, q_entry, W.q_exc_any, &W.counters[CTR(33)]);
+            if (__ballot(hand_back) != 0) wave_push(hand_back, q_entry, W.q_exc_any, &W.counters[CTR(WFC_EXC_ANY)]);
             Q.chunk_next += (need < avail ? need : avail);
         }
         const unsigned long long m_node = __ballot(L.mode == T8_NODE), m_leaf = __ballot(L.mode >= T8_LEAF);

@@ -1,5 +1,5 @@
 /*
- * ftn_wavefront.h -- host interface of the wavefront pipeline (ftn_wavefront.hip): SoA path state and ray queues in HBM,
+ * ftn_wavefront.h -- host interface of the wavefront pipeline (drivers: ftn_wavefront.hip; ray batches: ftn_wf_trace.hip; buffers and errors: ftn_wf_state.cpp): SoA path state and ray queues in HBM,
  * separate generate / trace / shade kernels per bounce (BASELINE configs 3-5).
  */
 #ifndef FTN_WAVEFRONT_H

@@ -1,8 +1,9 @@
 /*
  * ftn_wf_common.h -- device-side declarations shared by the wavefront pipeline's translation units (ftn_wavefront.hip: generate /
- * classify / shade / accumulate and the reference-order traversal kernels; ftn_trace4.hip: the production traversal kernels over
- * 128-byte four-box records; ftn_gbuffer.hip and ftn_moments.hip: the passes beside the beauty): path-state bits, the SoA buffers of a
- * wavefront, queue helpers, the hit record, the leaf primitive test, and through ftn_film.h the film context of the accumulate kernels.
+ * reset / accumulate; ftn_wf_trace.hip: the reference-order traversal kernels; ftn_wf_shade.hip: classify and
+ * the integrators' shading kernels; ftn_trace4.hip: the production traversal kernels over 128-byte four-box records; ftn_gbuffer.hip
+ * and ftn_moments.hip: the passes beside the beauty): path-state bits, the SoA buffers of a wavefront, the names of its counter slots,
+ * queue helpers, the hit record, the leaf primitive test, and through ftn_film.h the film context of the accumulate kernels.
  */
 #ifndef FTN_WF_COMMON_H
 #define FTN_WF_COMMON_H
@@ -42,11 +43,11 @@ struct WfBuffers {
     uint32_t* q_sorted;         /* the active queue grouped by shading class (material-sorted shading) */
     uint32_t* cls;              /* per-class path counts, one 128-byte line each (CTR(k)) */
     uint32_t seg_cap;           /* capacity of one class segment of q_sorted */
-    uint32_t* counters;         /* one 128-byte line each (CTR(i) = 32*i): 0 active A, 1 active B, 2 closest, 3 shadow, 4 head closest, 5 head shadow */
+    uint32_t* counters;         /* WFC_SLOTS counters, one 128-byte line each (CTR(i) = 32*i): the WFC_* enum below names the slots */
     uint32_t valid_per_sample;  /* camera samples per spp pass (sum of the tiles' pixel counts) */
     uint32_t* drain_sig; uint32_t drain_seq, drain_at;   /* closest-hit trace: where (signal memory) and what to store once a wave finds the queue dry (NULL: nobody waits) */
     /* rays the four-box kernels hand back to the reference-order kernels (a direction component of zero: see ftn_trace4.hip), queue
-     * entries as in the queue they came from; counts at CTR(32) closest / CTR(33) any-hit, slice heads at CTR(40..47) / CTR(48..55) */
+     * entries as in the queue they came from; counts at WFC_EXC_CLOSEST / WFC_EXC_ANY, slice heads from WFC_EXC_HEAD_CLOSEST / WFC_EXC_HEAD_ANY */
     uint32_t *q_exc_closest, *q_exc_any;
     /* DirectLightingIntegrator / WhittedIntegrator (k_wf_shade_dl): per-level terms of the nested product, level-major: dlA[d * n_paths + p] =
      * {local.rgb, pdf}, dlB = {f.rgb, |cos|}; whT[l * n_paths + p] = Whitted's term of light l (added if its shadow ray is unoccluded) */
@@ -79,6 +80,23 @@ struct WfBuffers {
 #define WF_Q_ID_MASK 0x0fffffffu
 
 #define CTR(i) ((i) * 32)
+/* the slots of WfBuffers::counters (index with CTR(slot)).  A range is [FIRST, END); k_wf_reset clears the ranges before every shading pass */
+enum : int {
+    WFC_ACTIVE_A = 0, WFC_ACTIVE_B = 1,      /* lengths of q_active[0] / q_active[1] */
+    WFC_CLOSEST = 2, WFC_SHADOW = 3,         /* lengths of q_closest / q_shadow */
+    WFC_NODE_STEPS = 6, WFC_LEAF_STEPS = 7, WFC_IDLE_LANES = 8, WFC_LEAFWAIT_LANES = 9,      /* counting build of k_wf_trace: wave-level step tallies (FTN_WF_DEBUG) */
+    WFC_MIS_ANY = 10,                        /* MIS rays traced as any-hit rays (a tally: they are queued in q_shadow) */
+    WFC_DRY_WAVES = 11,                      /* waves of the closest-hit launch that found the queue dry (WfBuffers::drain_at) */
+    WFC_DRAIN_PROBE = 13,                    /* FTN_DRAIN_PROBE builds: four words per bounce, eight bounces, inside this one line */
+    WFC_HEADS_FIRST = 16,                    /* per-XCD queue heads of the two trace launches of a bounce, eight slots each */
+    WFC_HEAD_CLOSEST = 16, WFC_HEAD_ANY = 24,
+    WFC_HEADS_END = 32,
+    WFC_EXC_FIRST = 32,                      /* exception queues of the four-box kernels (q_exc_closest / q_exc_any): lengths, then per-XCD heads */
+    WFC_EXC_CLOSEST = 32, WFC_EXC_ANY = 33, WFC_EXC_HEAD_CLOSEST = 40, WFC_EXC_HEAD_ANY = 48,
+    WFC_EXC_END = 56,
+    WFC_SLOTS = 64
+};
+#define WF_NCLASS 8                 /* shading classes (k_wf_classify); WfBuffers::cls holds one count per class at CTR(class) */
 __device__ inline uint32_t lane_id() { return threadIdx.x & 63u; }
 /* wave-level queue append: one atomic per wave (ballot / popc compaction) */
 __device__ inline void wave_push(bool pred, uint32_t value, uint32_t* queue, uint32_t* counter) {

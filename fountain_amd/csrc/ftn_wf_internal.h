@@ -1,7 +1,15 @@
 /*
- * ftn_wf_internal.h -- what the driver of a pass on the wavefront pipeline (ftn_gbuffer.hip) may use of ftn_wavefront.hip beyond the
- * public ftn_wavefront.h: the scene's WavefrontState and its buffers, the knobs, the pass plan, the traversal launches and launchers
- * for the two kernels every pass starts with.  Declarations only, all of hidden visibility: the library exports the C ABI alone.
+ * ftn_wf_internal.h -- what the units of the wavefront pipeline share on the host side, beyond the public ftn_wavefront.h:
+ *
+ *   ftn_wf_state.cpp      error text, knobs, WavefrontState and its buffers, the pass plan, the traversal grid
+ *   ftn_wf_trace.hip      the reference-order traversal kernels, the coherence sort, launch_trace, the ray-batch entry point
+ *   ftn_wf_shade.hip      k_wf_classify, k_wf_shade (path integrator), k_wf_shade_dl (direct lighting / Whitted) and k_batch_finish with
+ *                         their launchers
+ *   ftn_wavefront.hip     generate / reset / accumulate / serial-advance and the two render drivers
+ *   ftn_gbuffer.hip       the G-buffer pass and its driver
+ *
+ * A kernel is launched from the unit that defines it; what another unit needs of it is a launcher declared here.  Declarations only,
+ * all of hidden visibility: the library exports the C ABI alone.
  */
 #ifndef FTN_WF_INTERNAL_H
 #define FTN_WF_INTERNAL_H
@@ -30,6 +38,11 @@ struct WavefrontState {
     void* t4_spill_c = nullptr; void* t4_spill_a = nullptr; size_t t4_spill_c_bytes = 0, t4_spill_a_bytes = 0;
 };
 
+/* limits of k_wf_shade_dl that the pass plan reads: chain levels kept per path; lights under WhittedIntegrator */
+#define WF_DL_MAX 8u
+#define WF_WH_MAX_LIGHTS 32u     /* one bit per light in the path's pending-light word */
+
+/* ------------------------------------------------------------------ ftn_wf_state.cpp */
 /* the text wavefront_error() returns on this thread */
 void wf_set_error(const std::string& msg);
 #define WF_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { wf_set_error(std::string(#expr ": ") + hipGetErrorString(e_)); return e_ == hipErrorOutOfMemory ? FTN_ERR_OUT_OF_MEMORY : FTN_ERR_NO_DEVICE; } } while (0)
@@ -45,7 +58,13 @@ void wf_free(WavefrontState* st);
 /* buffers of k_wf_shade_dl for n paths, `levels` chain levels and `slots` shadow rays per path; tex: the differentials of textured scenes */
 int wf_reserve_dl(WavefrontState* st, size_t n, uint32_t levels, uint32_t slots, bool tex);
 void wf_free_dl(WavefrontState* st);
+/* buffers of the tile-serial sampler for n_tiles tiles (WavefrontState::ser_mem); tex: the differentials of textured scenes */
+int wf_reserve_serial(WavefrontState* st, uint32_t n_tiles, bool tex);
+/* a grow-only device buffer: at least `need` bytes behind *p.  When the allocation fails, *p and *bytes are left zero */
+int wf_grow(void** p, size_t* bytes, size_t need);
 
+/* refuses more than 2^28 pixel slots in one call */
+int wf_refuse_slots(size_t n_slots);
 /* The pass plan of a call over n_slots pixel slots and total_samples samples of each: how many samples one pass takes (FTN_WF_PATHS_M,
  * at most 2^28 paths; with dl, the direct-lighting / Whitted cap on slots x paths), halved while the buffers do not fit, and those
  * buffers reserved (dl: wf_reserve_dl's too).  Refuses more than 2^28 slots and, with dl, more than 32 lights under WhittedIntegrator
@@ -53,15 +72,41 @@ void wf_free_dl(WavefrontState* st);
 struct WfPassPlan { uint32_t samples, dl_levels, dl_slots; };
 int wf_plan_passes(WavefrontState* st, const RenderParams& P, size_t n_slots, uint32_t total_samples, bool dl, WfPassPlan* plan);
 
+/* the persistent traversal launches: dynamic LDS of a 256-thread workgroup whose lanes keep stack_entries node-stack levels each, and the
+ * largest grid worth launching with it (CUs x the workgroups, at most 8, that 160 KiB of LDS hold) */
+size_t wf_trace_lds(uint32_t stack_entries);
+unsigned wf_trace_grid_max(const WavefrontState* st, size_t lds);
+
+/* ------------------------------------------------------------------ ftn_wf_trace.hip */
 /* Sizes the four-box kernels' launches for this call and makes sure their spill areas exist */
 int trace4_prepare(WavefrontState* st, const DScene& S);
 /* count: 0 = production kernels, 1 = counting build of the REFERENCE walk (node / primitive tallies equal the oracle's), 2 = counting
  * build of the production kernels (what bench.py's byte model uses).  max_rays: upper bound of the queue's length (sizes the grid). */
 void launch_trace(WavefrontState* st, bool any, int count, bool spheres, unsigned grid, size_t lds, hipStream_t stream, const RenderParams& P, const WfBuffers& W,
                   const uint32_t* queue, const uint32_t* count_ptr, uint32_t* head, uint32_t max_rays, bool camera_rays = false);
+/* sorts queue[0, cnt) by the rays' coherence keys into `out`; *sorted_q = out (or the queue itself when it is too short to bother) */
+int sort_ray_queue(WavefrontState* st, const RenderParams& P, const WfBuffers& W, bool any, uint32_t* queue, uint32_t cnt, uint32_t* out,
+                   uint32_t* k_in, uint32_t* k_out, uint32_t bits, hipStream_t stream, const uint32_t** sorted_q);
+#ifdef FTN_DRAIN_PROBE
+/* experiment build (tools/gpu_drain_probe.py): the bounce whose any-hit launch reports next */
+void wf_set_probe_bounce(uint32_t bounce);
+#endif
 
+/* ------------------------------------------------------------------ ftn_wf_shade.hip */
+/* groups the active queue in_q by shading class; drop: classes whose entries leave the queues here (late finish) */
+void launch_wf_classify(const RenderParams& P, const WfBuffers& W, int in_q, uint32_t drop, unsigned grid, hipStream_t stream);
+/* The path integrator's shading pass over the classified queue: one launch per material type present in the scene and one for the classes
+ * without a BSDF (FTN_SHADE_SPECIALISE=0: one launch for everything).  first: the pass right behind k_wf_generate.  fixed_grid = 0: every
+ * variant takes the grid its registers let the CUs hold (FTN_SHADE_GRID, FTN_SHADE_GRID_NOBSDF); != 0 (the tile-serial driver): every
+ * variant launches at this grid */
+void launch_wf_shade(WavefrontState* st, const RenderParams& P, const WfBuffers& W, int in_q, uint32_t first, unsigned fixed_grid, hipStream_t stream);
+void launch_wf_shade_dl(bool whitted, bool tex, const RenderParams& P, const WfBuffers& W, int in_q, unsigned grid, hipStream_t stream);
+/* what a batch of n closest-hit rays returns (wavefront_trace_batch): t, primitive, barycentrics, and in out24 the surface interaction */
+void launch_batch_finish(const DScene& S, const float* d_rays8, uint32_t n, const float4* hit, const int* hit_prim, float* t_hit, int* prim, float* bary, float* out24, hipStream_t stream);
+
+/* ------------------------------------------------------------------ ftn_wavefront.hip */
 /* the first two launches of a pass: k_wf_reset in mode 0 (counters, queue lengths of the camera rays, camera_samples) and k_wf_generate
- * with their launch parameters (a kernel is launched from the unit that defines it) */
+ * with their launch parameters */
 void launch_wf_new_pass(const WfBuffers& W, DevStats* stats, hipStream_t stream);
 void launch_wf_generate(const RenderParams& P, const WfBuffers& W, int write_state, hipStream_t stream);
 

@@ -800,7 +800,8 @@ def test_path_record_layouts_change_nothing(gpu, orc_det, monkeypatch):
         si = SamplerIntegrator(cam, PathIntegrator.new(5, 1.0))
         out = {}
         for name, env in (("default", {}), ("soa", {"FTN_WF_BR": "0", "FTN_WF_PD": "0"}), ("pd1", {"FTN_WF_PD": "1"}), ("pd2", {"FTN_WF_PD": "2"}), ("pd3 br0", {"FTN_WF_PD": "3", "FTN_WF_BR": "0"}),
-                          ("carried streams", {"FTN_RNG_REPLAY": "0"}), ("two streams", {"FTN_WF_OVERLAP": "1"})):
+                          ("carried streams", {"FTN_RNG_REPLAY": "0"}), ("two streams", {"FTN_WF_OVERLAP": "1"}),
+                          ("one shade launch", {"FTN_SHADE_SPECIALISE": "0"}), ("general light code", {"FTN_SHADE_ENV": "0"})):
             for k, v in env.items(): monkeypatch.setenv(k, v)
             f = Film(gpu, res)
             st = si.render_parallel(sc, f, smp, pipeline=WAVE)

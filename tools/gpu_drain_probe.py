@@ -1,6 +1,8 @@
-"""Drain of the any-hit launches.  Needs a library built with -DFTN_DRAIN_PROBE (ftn_wavefront.hip): each launch then reports on stderr
-when its first / last wave found the queue dry and when it ended.  FTN_LIB selects the library, e.g.
-    hipcc ... -DFTN_DRAIN_PROBE -c ftn_wavefront.hip -o build/probe.o && hipcc -shared ... -o ../libfountain_hip_probe.so
+"""Drain of the any-hit launches.  Needs a library built with -DFTN_DRAIN_PROBE (ftn_wf_trace.hip: the kernel's time stamps;
+ftn_wavefront.hip: the driver that clears and prints them): each launch then reports on stderr when its first / last wave found the
+queue dry and when it ended.  FTN_LIB selects the library, e.g.
+    hipcc ... -DFTN_DRAIN_PROBE -c ftn_wf_trace.hip -o build/probe_trace.o && hipcc ... -DFTN_DRAIN_PROBE -c ftn_wavefront.hip -o build/probe_driver.o
+        && hipcc -shared ... -o ../libfountain_hip_probe.so          (or the whole library: make SUFFIX=_probe EXTRA=-DFTN_DRAIN_PROBE)
     FTN_LIB=libfountain_hip_probe.so python tools/gpu_drain_probe.py"""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

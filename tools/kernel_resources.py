@@ -6,7 +6,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "fountain_amd", "csrc")
 FLAGS = "--offload-arch=gfx950 -std=c++17 -O3 -fPIC -ffp-contract=off -fno-fast-math -fhip-fp32-correctly-rounded-divide-sqrt -Rpass-analysis=kernel-resource-usage".split()
 print("Registers, scratch, LDS and occupancy of every kernel of the final build (hipcc -Rpass-analysis=kernel-resource-usage, gfx950;\nthe dynamic LDS of the traversal kernels is set at launch and not in these figures)\n")
-for f in sys.argv[1:] or ("ftn_trace4.hip", "ftn_wavefront.hip", "ftn_kernels.hip", "ftn_gbuffer.hip", "ftn_moments.hip", "ftn_adaptive.hip"):
+for f in sys.argv[1:] or ("ftn_trace4.hip", "ftn_wavefront.hip", "ftn_wf_trace.hip", "ftn_wf_shade.hip", "ftn_kernels.hip", "ftn_gbuffer.hip", "ftn_moments.hip", "ftn_adaptive.hip"):
     r = subprocess.run(["/opt/rocm/bin/hipcc"] + FLAGS + ["-c", os.path.join(SRC, f), "-o", "/dev/null"], capture_output=True, text=True)
     cur = {}
     for line in r.stderr.splitlines():

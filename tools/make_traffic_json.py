@@ -21,7 +21,8 @@ import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SOURCES = ["fountain_amd/csrc/ftn_trace4.hip", "fountain_amd/csrc/ftn_wavefront.hip", "fountain_amd/csrc/ftn_wf_common.h", "fountain_amd/csrc/ftn_wf_internal.h", "fountain_amd/csrc/ftn_film.h", "fountain_amd/csrc/ftn_device.h",
+SOURCES = ["fountain_amd/csrc/ftn_trace4.hip", "fountain_amd/csrc/ftn_wavefront.hip", "fountain_amd/csrc/ftn_wf_trace.hip", "fountain_amd/csrc/ftn_wf_shade.hip",
+           "fountain_amd/csrc/ftn_wf_state.cpp", "fountain_amd/csrc/ftn_wf_path.h", "fountain_amd/csrc/ftn_wf_common.h", "fountain_amd/csrc/ftn_wf_internal.h", "fountain_amd/csrc/ftn_film.h", "fountain_amd/csrc/ftn_device.h",
            "fountain_amd/csrc/ftn_kernels.hip", "fountain_amd/csrc/ftn_kernels.h", "fountain_amd/csrc/ftn_wavefront.h", "fountain_amd/csrc/ftn_math.h", "fountain_amd/csrc/detmath.h", "fountain_amd/csrc/ftn_texture.h",
            # the host units that decide what those kernels read and how they are launched: scene construction, BVH construction, the render
            # driver and what they share -- not the geometry ABI (ftn_geometry_host.cpp) and not the test hooks
