@@ -152,6 +152,19 @@ class ftn_gbuffer_pixel(C.Structure):
 FTN_GBUFFER_ABI_VERSION = 1  # include/fountain_hip_gbuffer.h (an extension with a version of its own; FTN_ABI_VERSION is unchanged)
 
 
+FTN_IDMATTE_SLOTS = 8
+
+
+class ftn_idmatte_pixel(C.Structure):
+    """include/fountain_hip_idmatte.h: a pixel's table of (id, weight) in first-seen order, and what did not enter it."""
+    _fields_ = [("id", c_u32 * FTN_IDMATTE_SLOTS), ("weight", c_f * FTN_IDMATTE_SLOTS), ("overflow", c_f), ("miss", c_f), ("total", c_f), ("n_used", c_u32)]
+
+
+FTN_IDMATTE_ABI_VERSION = 1  # include/fountain_hip_idmatte.h (an extension with a version of its own; FTN_ABI_VERSION is unchanged)
+FTN_IDMATTE_RESOLVED_WORDS = 20
+FTN_IDMATTE_SELECT_OVERFLOW, FTN_IDMATTE_SELECT_MISS = 1, 2
+
+
 class ftn_denoise_params(C.Structure):
     """include/fountain_hip_denoise.h: parameters of the a-trous denoiser (ftn_denoise_params_default fills the defaults)."""
     _fields_ = [("levels", C.c_int32), ("flags", c_u32), ("sigma_color", c_f), ("sigma_normal", c_f), ("sigma_plane", c_f),
@@ -298,7 +311,7 @@ SIZES = {
     "ftn_sphere": 288, "ftn_material": 48, "ftn_light": 160, "ftn_envmap": 16, "ftn_camera_desc": 296,
     "ftn_film_desc": 32, "ftn_sampler_desc": 24, "ftn_integrator_desc": 16, "ftn_tile_range": 16,
     "ftn_render_options": 16, "ftn_stats": 152, "ftn_scene_memory": 96, "ftn_texture": 48, "ftn_image": 24, "ftn_material_textures": 32,
-    "ftn_gbuffer_pixel": 48, "ftn_denoise_params": 32, "ftn_denoise_guided_params": 32, "ftn_moment_pixel": 16, "ftn_adaptive_params": 16, "ftn_adaptive_info": 24,
+    "ftn_gbuffer_pixel": 48, "ftn_idmatte_pixel": 80, "ftn_denoise_params": 32, "ftn_denoise_guided_params": 32, "ftn_moment_pixel": 16, "ftn_adaptive_params": 16, "ftn_adaptive_info": 24,
     "ftn_temporal_pixel": 32, "ftn_temporal_params": 32, "ftn_filter_desc": 32, "ftn_display_params": 48, "ftn_display_info": 32,
     "ftn_bloom_params": 32, "ftn_subdiv_info": 184,
     "ftn_metrics_params": 16, "ftn_metrics_totals": 112, "ftn_metrics_result": 136,
@@ -444,3 +457,18 @@ SUBDIV_PROTOTYPES = {
     "ftn_subdiv_abi_version": ([], C.c_int),
 }
 SUBDIV_FUNCTIONS = sorted(SUBDIV_PROTOTYPES)
+
+# Every function the extension header include/fountain_hip_idmatte.h declares (kept apart from the lists above: the reference renders
+# no mattes, so these have no orc_* twin either), with its prototype: name -> (argument types, result type).
+_STRINGS = C.POINTER(C.c_char_p)
+IDMATTE_PROTOTYPES = {
+    "ftn_render_idmatte": ([C.c_void_p] * 7 + [C.c_size_t, C.c_void_p, C.c_void_p], C.c_int),
+    "ftn_render_idmatte_device": ([C.c_void_p] * 7 + [C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
+    "ftn_idmatte_resolve": ([C.c_void_p, C.c_size_t, C.c_void_p], C.c_int),
+    "ftn_idmatte_resolve_device": ([C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p], C.c_int),
+    "ftn_idmatte_select": ([C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, c_u32, C.c_void_p], C.c_int),
+    "ftn_idmatte_select_device": ([C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, c_u32, C.c_void_p, C.c_void_p], C.c_int),
+    "ftn_exr_write_channels": ([C.c_char_p, c_i32, c_i32, c_i32, _STRINGS, C.POINTER(C.c_void_p), c_i32, _STRINGS, _STRINGS], C.c_int),
+    "ftn_idmatte_abi_version": ([], C.c_int),
+}
+IDMATTE_FUNCTIONS = sorted(IDMATTE_PROTOTYPES)

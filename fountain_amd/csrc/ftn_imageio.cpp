@@ -7,6 +7,7 @@
  * reference's writer produce, plus the usual encoding of environment maps and textures found in PBRT scenes; zlib inflates).
  */
 #include "../../include/fountain_hip.h"
+#include "../../include/fountain_hip_idmatte.h"
 #include "detmath.h"
 
 #include <algorithm>
@@ -107,6 +108,62 @@ int ftn_exr_write(const char* path, const float* rgb, uint32_t w, uint32_t h) {
         for (uint32_t x = 0; x < w; x++) { row[x] = src[3 * x + 2]; row[w + x] = src[3 * x + 1]; row[2 * (size_t)w + x] = src[3 * x]; }
         const int32_t hdr2[2] = {(int32_t)y, (int32_t)row_bytes};
         ok = fwrite(hdr2, 4, 2, f) == 2 && fwrite(row.data(), 4, row.size(), f) == row.size();
+    }
+    ok = (fclose(f) == 0) && ok;
+    return ok ? FTN_OK : io_fail(FTN_ERR_INTERNAL, std::string("short write to ") + path);
+}
+
+/* include/fountain_hip_idmatte.h: any number of named FLOAT channels and string attributes (the Cryptomatte layers of idmatte.py) */
+int ftn_exr_write_channels(const char* path, int32_t w, int32_t h, int32_t n_channels, const char* const* names, const float* const* planes,
+                           int32_t n_attrs, const char* const* attr_names, const char* const* attr_values) {
+    if (!path || !names || !planes || w <= 0 || h <= 0 || n_channels <= 0 || n_attrs < 0 || (n_attrs > 0 && (!attr_names || !attr_values)))
+        return io_fail(FTN_ERR_INVALID_ARGUMENT, "ftn_exr_write_channels: bad arguments");
+    std::vector<int32_t> order((size_t)n_channels);
+    for (int32_t c = 0; c < n_channels; c++) {
+        if (!names[c] || !planes[c]) return io_fail(FTN_ERR_INVALID_ARGUMENT, "ftn_exr_write_channels: null channel name or plane");
+        const size_t len = strnlen(names[c], 256);
+        if (len == 0 || len >= 256) return io_fail(FTN_ERR_INVALID_ARGUMENT, "ftn_exr_write_channels: a channel name must have 1 to 255 bytes");
+        order[(size_t)c] = c;
+    }
+    for (int32_t a = 0; a < n_attrs; a++) {
+        if (!attr_names[a] || !attr_values[a]) return io_fail(FTN_ERR_INVALID_ARGUMENT, "ftn_exr_write_channels: null attribute");
+        const size_t len = strnlen(attr_names[a], 256);
+        if (len == 0 || len >= 256) return io_fail(FTN_ERR_INVALID_ARGUMENT, "ftn_exr_write_channels: an attribute name must have 1 to 255 bytes");
+        if (strlen(attr_values[a]) > (size_t)0x7fffffff) return io_fail(FTN_ERR_INVALID_ARGUMENT, "ftn_exr_write_channels: attribute value too long");
+    }
+    /* the channel list and every scanline hold the channels sorted by name (bytewise) */
+    std::sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return strcmp(names[a], names[b]) < 0; });
+    for (int32_t c = 1; c < n_channels; c++)
+        if (strcmp(names[order[(size_t)c - 1]], names[order[(size_t)c]]) == 0) return io_fail(FTN_ERR_INVALID_ARGUMENT, std::string("ftn_exr_write_channels: duplicate channel name ") + names[order[(size_t)c]]);
+    const size_t row_bytes = (size_t)w * 4 * (size_t)n_channels;
+    if (row_bytes > (size_t)0x7fffffff) return io_fail(FTN_ERR_INVALID_ARGUMENT, "ftn_exr_write_channels: a scanline of all channels must stay below 2 GiB");
+    std::vector<unsigned char> hd;
+    const unsigned char magic[8] = {0x76, 0x2f, 0x31, 0x01, 2, 0, 0, 0};
+    hd.insert(hd.end(), magic, magic + 8);
+    std::vector<unsigned char> d;
+    for (int32_t c : order) { put_str(d, names[c]); put_i32(d, 2 /* FLOAT */); d.push_back(0 /* pLinear */); d.push_back(0); d.push_back(0); d.push_back(0); put_i32(d, 1); put_i32(d, 1); }
+    d.push_back(0);
+    put_attr(hd, "channels", "chlist", d);
+    put_attr(hd, "compression", "compression", {0});
+    d.clear(); put_i32(d, 0); put_i32(d, 0); put_i32(d, w - 1); put_i32(d, h - 1);
+    put_attr(hd, "dataWindow", "box2i", d);
+    put_attr(hd, "displayWindow", "box2i", d);
+    put_attr(hd, "lineOrder", "lineOrder", {0});
+    d.clear(); put_f32(d, 1.0f); put_attr(hd, "pixelAspectRatio", "float", d);
+    d.clear(); put_f32(d, 0.0f); put_f32(d, 0.0f); put_attr(hd, "screenWindowCenter", "v2f", d);
+    d.clear(); put_f32(d, 1.0f); put_attr(hd, "screenWindowWidth", "float", d);
+    for (int32_t a = 0; a < n_attrs; a++) { d.assign(attr_values[a], attr_values[a] + strlen(attr_values[a])); put_attr(hd, attr_names[a], "string", d); }
+    hd.push_back(0);
+    FILE* f = fopen(path, "wb");
+    if (!f) return io_fail(FTN_ERR_INVALID_ARGUMENT, std::string("cannot create ") + path);
+    const size_t block = 8 + row_bytes;
+    std::vector<uint64_t> offs((size_t)h);
+    for (int32_t y = 0; y < h; y++) offs[(size_t)y] = hd.size() + (size_t)h * 8 + (size_t)y * block;
+    bool ok = fwrite(hd.data(), 1, hd.size(), f) == hd.size() && fwrite(offs.data(), 8, (size_t)h, f) == (size_t)h;
+    for (int32_t y = 0; y < h && ok; y++) {
+        const int32_t hdr2[2] = {y, (int32_t)row_bytes};
+        ok = fwrite(hdr2, 4, 2, f) == 2;
+        for (size_t c = 0; c < order.size() && ok; c++) ok = fwrite(planes[order[c]] + (size_t)y * (size_t)w, 4, (size_t)w, f) == (size_t)w;
     }
     ok = (fclose(f) == 0) && ok;
     return ok ? FTN_OK : io_fail(FTN_ERR_INTERNAL, std::string("short write to ") + path);

@@ -8,7 +8,9 @@ reduce (RCCL when every rank has its own GPU, gloo with --dist-backend gloo); ra
 per-tile RandomSampler stream (one lane per 16x16 tile: for validation, slow); the default re-seeds per (pixel, sample) so that
 samples run in parallel (samplers).  --gbuffer also writes the first-hit G-buffer of the same camera samples
 (fountain_amd/gbuffer.py) beside the image: <name>_albedo.exr, <name>_normal.exr, <name>_position.exr and <name>_depth.exr (camera-space
-depth repeated in R, G and B); it needs the default sampler and one GPU.  --denoise then renders that G-buffer (also without
+depth repeated in R, G and B); it needs the default sampler and one GPU.  --idmatte KIND[,KIND] (material, shape, primitive) also
+writes <name>_crypto.exr: the ID mattes of the same camera samples (fountain_amd/idmatte.py) as Cryptomatte layers CryptoMaterial,
+CryptoObject and CryptoPrimitive, one per kind; it has the same needs as --gbuffer.  --denoise then renders that G-buffer (also without
 --gbuffer) and writes <name>_denoised.exr: the image filtered by the edge-avoiding a-trous denoiser (fountain_amd/denoise.py, default
 parameters); the image itself is written unchanged.  It has the same needs as --gbuffer.  --variance renders the image together with
 the second moments of its camera samples (fountain_amd/moments.py), the same pixels bit for bit, and writes <name>_variance.exr: the
@@ -19,10 +21,10 @@ unchanged.  It has the needs of --gbuffer and at least 2 samples per pixel, and 
 --adaptive T renders with per-tile adaptive sampling (fountain_amd/adaptive.py): every 16x16 tile gets --min-samples samples (default
 8, at most the samples per pixel), then twice as many, and so on up to --samples, until the estimated relative standard error of
 each of its pixels' mean luminance is at most T.  It writes <name>_spp.exr beside the image: each pixel's final sample count in R, G and B.  --variance works with it (from
-the same moments); --gbuffer, --denoise, --exact-stream and more than one GPU do not.
+the same moments); --gbuffer, --idmatte, --denoise, --exact-stream and more than one GPU do not.
 --pixel-filter {scene,box,triangle,gaussian,mitchell,sinc} renders the image through a reconstruction filter (fountain_amd/filters.py):
 `scene` takes the file's PixelFilter statement (an error if it has none), the others the defaults of that filter; --filter-width X [Y]
-sets the radius.  A wide filter mixes the samples of neighbouring pixels, so --gbuffer, --denoise, --denoise-guided, --variance and
+sets the radius.  A wide filter mixes the samples of neighbouring pixels, so --gbuffer, --idmatte, --denoise, --denoise-guided, --variance and
 --adaptive, which assume that a pixel's samples are its own, are refused with it, as are --exact-stream and more than one GPU.
 Without the option the image is the reference's: a box of radius 0.5, whatever the file says.
 --png also writes <name>.png beside <name>.exr through the display stage (fountain_amd/display.py): --exposure EV (default 0) or
@@ -60,6 +62,8 @@ def main(argv=None):
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"])
     ap.add_argument("--gpus", type=int, default=None, help="render on N GPUs of this node: film tiles r, r+N, ... per rank, one reduce at the end")
     ap.add_argument("--gbuffer", action="store_true", help="also write the first-hit albedo / normal / position / depth buffers as <name>_<buffer>.exr")
+    ap.add_argument("--idmatte", default=None, metavar="KIND[,KIND]",
+                    help="also write <name>_crypto.exr: Cryptomatte layers of the image's camera samples, one per kind (material, shape, primitive)")
     ap.add_argument("--denoise", action="store_true", help="also write <name>_denoised.exr, the image denoised with the first-hit G-buffer of its camera samples")
     ap.add_argument("--variance", action="store_true", help="also write <name>_variance.exr, the estimated variance of each pixel's mean (r, g, b)")
     ap.add_argument("--denoise-guided", action="store_true",
@@ -107,8 +111,14 @@ def main(argv=None):
     if opts.filter_width is not None and (opts.pixel_filter is None or len(opts.filter_width) > 2):
         print("error: --filter-width X [Y] belongs to --pixel-filter", file=sys.stderr)
         return 2
+    if opts.idmatte is not None:
+        from .idmatte import LAYERS
+        opts.idmatte = opts.idmatte.split(",")
+        if not all(k in LAYERS for k in opts.idmatte) or len(set(opts.idmatte)) != len(opts.idmatte):
+            print("error: --idmatte takes a list of different kinds out of %s" % ", ".join(LAYERS), file=sys.stderr)
+            return 2
     if opts.pixel_filter is not None:
-        for flag, on in (("--gbuffer", opts.gbuffer), ("--denoise", opts.denoise), ("--denoise-guided", opts.denoise_guided), ("--variance", opts.variance),
+        for flag, on in (("--gbuffer", opts.gbuffer), ("--idmatte", opts.idmatte is not None), ("--denoise", opts.denoise), ("--denoise-guided", opts.denoise_guided), ("--variance", opts.variance),
                          ("--adaptive", opts.adaptive is not None), ("--exact-stream", opts.exact_stream),
                          ("more than one GPU (--gpus)", opts.gpus is not None and opts.gpus > 1)):
             if on:
@@ -119,7 +129,7 @@ def main(argv=None):
         print("error: --min-samples belongs to --adaptive", file=sys.stderr)
         return 2
     if opts.adaptive is not None:
-        for flag, on in (("--exact-stream", opts.exact_stream), ("--gbuffer", opts.gbuffer), ("--denoise", opts.denoise),
+        for flag, on in (("--exact-stream", opts.exact_stream), ("--gbuffer", opts.gbuffer), ("--idmatte", opts.idmatte is not None), ("--denoise", opts.denoise),
                          ("--denoise-guided", opts.denoise_guided), ("more than one GPU (--gpus)", opts.gpus is not None and opts.gpus > 1)):
             if on:
                 print("error: --adaptive does not work with %s: it renders each tile at its own sample count on one GPU with the default sampler"
@@ -128,7 +138,8 @@ def main(argv=None):
         if not opts.adaptive >= 0.0 or opts.adaptive == float("inf"):
             print("error: --adaptive takes a finite threshold >= 0", file=sys.stderr)
             return 2
-    for flag, on in (("--gbuffer", opts.gbuffer), ("--denoise", opts.denoise), ("--variance", opts.variance), ("--denoise-guided", opts.denoise_guided)):
+    for flag, on in (("--gbuffer", opts.gbuffer), ("--idmatte", opts.idmatte is not None), ("--denoise", opts.denoise), ("--variance", opts.variance),
+                     ("--denoise-guided", opts.denoise_guided)):
         if on and opts.exact_stream:
             print("error: %s needs the default sampler: with --exact-stream a sample's camera ray depends on everything its tile drew before it" % flag, file=sys.stderr)
             return 2
@@ -142,8 +153,9 @@ def main(argv=None):
         # started plainly: start the N ranks as a child process (before anything here has touched HIP) and hand back its exit code
         return spawn_ranks(opts.gpus, sys.argv[1:] if argv is None else list(argv), module="fountain_amd.render")
     world, rank = (env_world[0], env_world[1]) if env_world is not None else (1, 0)
-    if (opts.gbuffer or opts.denoise or opts.variance or opts.denoise_guided or opts.adaptive is not None or opts.pixel_filter is not None or opts.png) and world > 1:
-        flag = "--png" if opts.png else "--gbuffer" if opts.gbuffer else "--denoise" if opts.denoise else "--variance" if opts.variance else \
+    if (opts.gbuffer or opts.idmatte is not None or opts.denoise or opts.variance or opts.denoise_guided or opts.adaptive is not None or opts.pixel_filter is not None
+            or opts.png) and world > 1:
+        flag = "--png" if opts.png else "--gbuffer" if opts.gbuffer else "--idmatte" if opts.idmatte is not None else "--denoise" if opts.denoise else "--variance" if opts.variance else \
             "--denoise-guided" if opts.denoise_guided else "--adaptive" if opts.adaptive is not None else "--pixel-filter"
         print("error: %s renders on one GPU, not under a launcher of %d ranks" % (flag, world), file=sys.stderr)
         return 2
@@ -268,6 +280,8 @@ def main(argv=None):
             out = write_denoised_guided(be, img, gb, variance, filename, opts.gpu)
             if png:
                 png.write(bloomed(out), denoised_guided_path(filename))
+    if opts.idmatte is not None:
+        write_idmatte(be, scene, parsed, film, sampler, filename, opts.gpu, opts.idmatte)
     if opts.adaptive is not None:
         import numpy as np
         path = spp_path(filename)
@@ -329,6 +343,27 @@ def write_gbuffer(be, scene, camera, film, sampler, filename, device, write=True
         write_exr(paths["depth"], np.repeat(res["depth"], 3, axis=-1), be)
         print("G-buffer: %s (%.1f ms on the GPU)" % (", ".join(paths[k] for k in ("albedo", "normal", "position", "depth")), st["kernel_ms"]), file=sys.stderr)
     return np.concatenate([res[k] for k in CHANNELS], axis=-1)
+
+
+def idmatte_path(filename):
+    """out.exr -> out_crypto.exr"""
+    base = filename[:-4] if filename.endswith(".exr") else filename
+    return "%s_crypto.exr" % base
+
+
+def write_idmatte(be, scene, parsed, film, sampler, filename, device, kinds):
+    """The ID mattes of the beauty's camera samples (same film, sampler and tiles), one Cryptomatte layer per kind, written as
+    <name>_crypto.exr."""
+    from . import idmatte as I
+    layers, ms = {}, 0.0
+    for kind in kinds:
+        ids, names = I.prim_ids(parsed, kind)
+        resolved, _, st = I.render_idmatte(be, None, parsed.camera, None, sampler, ids, scene=scene, film=film, device=device)
+        layers[I.LAYERS[kind]] = (resolved, names)
+        ms += st["kernel_ms"]
+    path = idmatte_path(filename)
+    I.write_cryptomatte(path, layers, be)
+    print("ID mattes: %s (%s; %.1f ms on the GPU)" % (path, ", ".join(layers), ms), file=sys.stderr)
 
 
 def write_denoised(be, img, gb12, filename, device):
