@@ -1,8 +1,8 @@
 /*
  * ftn_gbuffer.hip -- the first-hit G-buffer pass (include/fountain_hip_gbuffer.h) on the wavefront pipeline.
  *
- * A unit of its own: the driver uses the wavefront pipeline through ftn_wf_internal.h (the scene's WavefrontState and its buffers, the
- * pass plan, the traversal launches, the launchers of k_wf_reset and k_wf_generate), the kernels share ftn_wf_common.h with the beauty's.
+ * A unit of its own: the kernels are here and share ftn_wf_common.h with the beauty's; the passes and their pass-through rounds are
+ * wf_first_hit_passes' (ftn_wf_internal.h, ftn_wavefront.hip), which wavefront_gbuffer hands the launches of k_gb_shade and k_gb_accumulate.
  */
 #include "ftn_wf_internal.h"
 #include "ftn_texture.h"
@@ -15,9 +15,8 @@ namespace ftn {
 /* ================================================================== first-hit G-buffer (include/fountain_hip_gbuffer.h)
  * The camera samples of ftn_render for the same sampler, tiles and film: k_wf_generate makes the camera rays from the sample keys, the
  * production closest-hit kernels trace them, and k_gb_shade records the first surface that has a material.  A null-material hit spawns
- * the ray on along the same direction (path.rs:77-80) into the other queue and the round repeats, at most GB_MAX_PASS_THROUGH times.
+ * the ray on along the same direction (path.rs:77-80) into the other queue and the round repeats (wf_first_hit_passes).
  * k_gb_accumulate then adds the pass's samples of every pixel in sample order, as k_wf_accumulate adds the beauty's. */
-#define GB_MAX_PASS_THROUGH 4096u
 struct GbParams {
     float w2c[16];        /* camera_to_world.inv: camera-space z of a hit (transform.rs:224) */
     float* out;           /* 12 floats per crop pixel (ftn_gbuffer_pixel), added into */
@@ -88,15 +87,6 @@ __global__ void __launch_bounds__(256) k_gb_shade(RenderParams P, WfBuffers W, G
     uint32_t* const qs[1] = {q_out};
     uint32_t* const cs[1] = {count_out};
     block_push<1>(pred, val, qs, cs);
-}
-
-/* between two rounds: the trace kernels' queue heads and hand-back queues, and the count of the queue the next shading pass fills */
-__global__ void k_gb_reset(WfBuffers W, uint32_t out_ctr) {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    W.counters[CTR(WFC_DRY_WAVES)] = 0;
-    static_assert(WFC_HEADS_END == WFC_EXC_FIRST, "the two ranges are cleared as one");
-    for (int i = WFC_HEADS_FIRST; i < WFC_EXC_END; i++) W.counters[CTR(i)] = 0;
-    W.counters[CTR(out_ctr)] = 0;
 }
 
 /* one sample's record into every pixel of its box-filter footprint (film_add): the own pixel in registers, others into the spill sums */
@@ -196,66 +186,22 @@ void launch_gbuffer_resolve(const float* in, size_t n, float* out12, hipStream_t
 
 int wavefront_gbuffer(WavefrontState** state, const RenderParams& P, const std::vector<DTile>& tiles, const float w2c[16], float* d_out,
                       float4* spill_a, float4* spill_b, float4* spill_c, hipStream_t stream, double* trace_ms_out) {
-    knobs_begin();
-    { int rc0 = wf_state_init(state); if (rc0) return rc0; }
-    WavefrontState* st = *state;
-    const uint32_t n_slots = (uint32_t)tiles.size() * 256u;
-    const uint32_t total_samples = P.last_sample - P.first_sample;
-    if (n_slots == 0 || total_samples == 0) return FTN_OK;
-    /* the beauty's passes (wf_plan_passes) without the direct-lighting buffers: only camera rays are traced */
-    WfPassPlan plan;
-    int rc = wf_plan_passes(st, P, tiles.size() * 256u, total_samples, false, &plan);
-    if (rc) return rc;
-    const uint32_t S = plan.samples;
-    if ((rc = trace4_prepare(st, P.S))) return rc;
-    WfBuffers W = st->W;
-    W.br = nullptr; W.pd = nullptr; W.pd_md = 0; W.pd_occ = 0; W.drain_sig = nullptr; W.drain_seq = 0; W.serial = 0; W.rng_replay = 0; W.mis_any = 0; W.late_finish = 0;
-    W.gen_blocks = knob("FTN_GEN_BLOCKS", 1);
-    uint32_t valid = 0; for (const DTile& t : tiles) valid += (uint32_t)((t.x1 - t.x0) * (t.y1 - t.y0));
-    W.valid_per_sample = valid;
     GbParams G;
-    memcpy(G.w2c, w2c, sizeof(G.w2c)); G.out = d_out; G.spillA = spill_a; G.spillB = spill_b; G.spillC = spill_c; G.rec = st->pd;         /* the path integrator's 64-byte records: 3 float4 per path used */
-    const bool spheres = P.S.n_spheres != 0, tex = P.S.n_textures != 0;
-    const size_t lds = wf_trace_lds(P.stack_entries);
-    const unsigned trace_grid_max = wf_trace_grid_max(st, lds);
-    double trace_ms = 0.0;
-    for (uint32_t s0 = 0; s0 < total_samples; s0 += S) {
-        const uint32_t Sp = std::min(S, total_samples - s0);
-        W.n_slots = n_slots; W.samples = Sp; W.n_paths = Sp * n_slots; W.first_sample = P.first_sample + s0; W.seg_cap = (uint32_t)st->cap_paths;
-        launch_wf_new_pass(W, P.stats, stream);
-        launch_wf_generate(P, W, 0, stream);
-        const unsigned tg = std::min<unsigned>(trace_grid_max, (2 * W.n_paths + 255) / 256);
-        uint32_t n_q = Sp * valid;
-        for (uint32_t r = 0;; r++) {
-            /* round r traces the queue of round r - 1's pass-throughs; the two queues alternate between q_closest (count WFC_CLOSEST) and q_shadow (WFC_SHADOW) */
-            const bool odd = (r & 1u) != 0;
-            const uint32_t* q_in = odd ? W.q_shadow : W.q_closest;
-            uint32_t* q_out = odd ? W.q_closest : W.q_shadow;
-            const uint32_t c_in = odd ? WFC_SHADOW : WFC_CLOSEST, c_out = odd ? WFC_CLOSEST : WFC_SHADOW;
-            if (r > 0) hipLaunchKernelGGL(k_gb_reset, dim3(1), dim3(64), 0, stream, W, c_out);
-            WF_TRY(hipEventRecord(st->ev[0], stream));
-            launch_trace(st, false, 0, spheres, tg, lds, stream, P, W, q_in, &W.counters[CTR(c_in)], &W.counters[CTR(WFC_HEAD_CLOSEST)], 2 * W.n_paths,
-                         r == 0 && W.samples >= knob("FTN_T4_LOCKSTEP_MIN_SPP", 1) /* the camera rays: lockstep parameters, as the beauty's first launch */);
-            WF_TRY(hipEventRecord(st->ev[1], stream));
-            const dim3 sg(std::max<uint32_t>(1u, (n_q + 255) / 256));
-            if (tex) hipLaunchKernelGGL(k_gb_shade<true>, sg, dim3(256), 0, stream, P, W, G, q_in, &W.counters[CTR(c_in)], q_out, &W.counters[CTR(c_out)]);
-            else hipLaunchKernelGGL(k_gb_shade<false>, sg, dim3(256), 0, stream, P, W, G, q_in, &W.counters[CTR(c_in)], q_out, &W.counters[CTR(c_out)]);
-            WF_TRY(hipMemcpyAsync(st->host_counters, W.counters, 16 * 32 * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-            WF_TRY(hipStreamSynchronize(stream));
-            float ms = 0.0f; (void)hipEventElapsedTime(&ms, st->ev[0], st->ev[1]); trace_ms += ms;
-            n_q = st->host_counters[CTR(c_out)];
-            if (n_q == 0) break;
-            if (r == GB_MAX_PASS_THROUGH) {
-                wf_set_error("a camera ray passed through more than 4096 null-material surfaces: the G-buffer would be incomplete");
-                return FTN_ERR_INTERNAL;
-            }
-        }
-        hipLaunchKernelGGL(k_gb_accumulate, dim3((n_slots + 255) / 256), dim3(256), 0, stream, P, W, G);
-    }
+    memcpy(G.w2c, w2c, sizeof(G.w2c)); G.out = d_out; G.spillA = spill_a; G.spillB = spill_b; G.spillC = spill_c; G.rec = nullptr;
+    const bool tex = P.S.n_textures != 0;
+    WfFirstHitPass pass;
+    pass.what = "the G-buffer";
+    pass.setup = [&](WavefrontState* st, uint32_t) { G.rec = st->pd; return FTN_OK; };          /* the path integrator's 64-byte records: 3 float4 per path used */
+    pass.shade = [&](const WfBuffers& W, const uint32_t* q_in, const uint32_t* count_in, uint32_t* q_out, uint32_t* count_out, dim3 grid, hipStream_t sm) {
+        if (tex) hipLaunchKernelGGL(k_gb_shade<true>, grid, dim3(256), 0, sm, P, W, G, q_in, count_in, q_out, count_out);
+        else hipLaunchKernelGGL(k_gb_shade<false>, grid, dim3(256), 0, sm, P, W, G, q_in, count_in, q_out, count_out);
+    };
+    pass.accumulate = [&](const WfBuffers& W, dim3 grid, hipStream_t sm) { hipLaunchKernelGGL(k_gb_accumulate, grid, dim3(256), 0, sm, P, W, G); };
+    const int rc = wf_first_hit_passes(state, P, tiles, pass, stream, trace_ms_out);
+    if (rc || !G.rec) return rc;          /* (no record buffer: no tiles or no samples, nothing was launched) */
     const size_t npix = (size_t)std::max(0, P.crop[2] - P.crop[0]) * (size_t)std::max(0, P.crop[3] - P.crop[1]);
     if (npix) hipLaunchKernelGGL(k_gb_merge, dim3((unsigned)std::min<size_t>((npix + 255) / 256, 4096)), dim3(256), 0, stream, G, npix, (const DevStats*)P.stats);
     WF_TRY(hipGetLastError());
-    if (trace_ms_out) *trace_ms_out = trace_ms;
     return FTN_OK;
 }
 

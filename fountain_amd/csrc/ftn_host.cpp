@@ -150,6 +150,28 @@ int render_error(int error) {
     return FTN_OK;
 }
 
+int first_hit_render(ftn_scene* s, const ftn_camera_desc* cam, const ftn_film_desc* film, const ftn_sampler_desc* sd, const ftn_tile_range* tr, hipStream_t stream, ftn_stats* st,
+                     const std::function<int(const RenderParams& P, double* trace_ms)>& run) {
+    ftn_integrator_desc first_hit; memset(&first_hit, 0, sizeof(first_hit)); first_hit.kind = FTN_INTEGRATOR_PATH;
+    RenderParams P = render_params(s, cam, film, sd, &first_hit);
+    int rc;
+    if ((rc = scene_tiles(s, film, tr, stream, &P)) || (rc = prepare_film(s, false, stream, &P))) return rc;
+    EventPair ev; if ((rc = ev.start(stream))) return rc;
+    double trace_ms = 0.0;
+    if ((rc = run(P, &trace_ms))) {
+        (void)hipStreamSynchronize(stream);              /* what the caller uploaded for the call is freed on return */
+        return fail(rc, wavefront_error());
+    }
+    float ms; if ((rc = ev.stop(stream, &ms))) return rc;
+    DevStats ds; if ((rc = read_stats(s, false, &ds))) return rc;
+    if (st) {
+        memset(st, 0, sizeof(*st));
+        st->rays_closest = ds.rays_closest; st->camera_samples = ds.camera_samples; st->spill_samples = ds.spill_samples;
+        st->kernel_ms = ms; st->trace_ms = trace_ms;
+    }
+    return FTN_OK;
+}
+
 extern "C" {
 
 const char* ftn_last_error(void) { return g_err.c_str(); }

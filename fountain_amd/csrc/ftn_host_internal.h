@@ -12,6 +12,7 @@
 #include "ftn_wavefront.h"
 
 #include <algorithm>
+#include <functional>
 #include <string>
 #include <thread>
 #include <vector>
@@ -150,6 +151,25 @@ template <class Run> int render_to_host(size_t npix, std::initializer_list<HostO
         float* h = (float*)o.host;
         for (size_t i = 0; i < b.size(); i++) h[i] += b[i];
     }
+    return rc;
+}
+
+/* The device entry of a first-hit pass (G-buffer, ID mattes) behind its refusals and bind_scene_device: the steps above with PathIntegrator
+ * of max_depth 0 in the parameters, around run(P, &trace_ms), the pass's wavefront call.  When run fails the stream is drained before the
+ * return (the caller may free what it uploaded for the call) and the status comes with wavefront_error().  st: rays_closest,
+ * camera_samples, spill_samples, kernel_ms, trace_ms; the rest zero. */
+int first_hit_render(ftn_scene* s, const ftn_camera_desc* cam, const ftn_film_desc* film, const ftn_sampler_desc* sd, const ftn_tile_range* tr, hipStream_t stream, ftn_stats* st,
+                     const std::function<int(const ftn::RenderParams& P, double* trace_ms)>& run);
+
+/* host-buffer twins of the first-hit passes: the caller's npix pixels go to the device, run(device pixels) continues them there, and they
+ * come back -- every pixel's own samples are added to the caller's sums one at a time (not summed apart and added at the end), so
+ * splitting a sample range over calls gives the bits of one call */
+template <class T, class Run> int continue_on_device(T* host_pixels, size_t npix, Run run) {
+    DevBuf<T> dev;
+    int rc = dev.upload(host_pixels, npix);
+    if (rc == FTN_OK) rc = run(dev.p ? (void*)dev.p : (void*)host_pixels);
+    if (rc == FTN_OK && npix && hipMemcpy(host_pixels, dev.p, npix * sizeof(T), hipMemcpyDeviceToHost) != hipSuccess) rc = fail(FTN_ERR_NO_DEVICE, "copy back failed");
+    dev.release();
     return rc;
 }
 

@@ -1,9 +1,10 @@
 /*
  * ftn_idmatte.hip -- the ID-matte pass (include/fountain_hip_idmatte.h) on the wavefront pipeline, with its resolve and matte extraction.
  *
- * A unit of its own, the second of the kind of ftn_gbuffer.hip: the driver uses the wavefront pipeline through ftn_wf_internal.h (the
- * scene's WavefrontState and its buffers, the pass plan, the traversal launches, the launchers of k_wf_reset and k_wf_generate), the
- * kernels share ftn_wf_common.h with the beauty's.  What the pass needs of ftn_gbuffer.hip's internals is restated here.
+ * A unit of its own, the second of the kind of ftn_gbuffer.hip: the kernels are here and share ftn_wf_common.h with the beauty's; the
+ * passes and their pass-through rounds are wf_first_hit_passes' (ftn_wf_internal.h, ftn_wavefront.hip), which wavefront_idmatte hands the
+ * launches of k_im_shade and k_im_accumulate.  The foreign list -- its allocation before the first pass, its sort and k_im_apply after the
+ * last -- is this unit's.
  */
 #include "ftn_wf_internal.h"
 #include "ftn_idmatte.h"
@@ -16,10 +17,9 @@ namespace ftn {
 /* ================================================================== the pass
  * The camera samples of ftn_render for the same sampler, tiles and film: k_wf_generate makes the camera rays from the sample keys, the
  * production closest-hit kernels trace them, and k_im_shade records the id of the first surface that has a material.  A null-material
- * hit spawns the ray on along the same direction (path.rs:77-80) into the other queue and the round repeats, at most
- * IM_MAX_PASS_THROUGH times.  k_im_accumulate then takes the pass's samples of every pixel into the pixel's table in sample order; what
+ * hit spawns the ray on along the same direction (path.rs:77-80) into the other queue and the round repeats
+ * (wf_first_hit_passes).  k_im_accumulate then takes the pass's samples of every pixel into the pixel's table in sample order; what
  * a sample adds to OTHER pixels goes to the foreign list, which k_im_apply works off after the last pass, sorted. */
-#define IM_MAX_PASS_THROUGH 4096u
 /* the foreign list: key = destination crop pixel << 32 | (sample - first sample of the call) << 4 | 3 (dy + 1) + (dx + 1), where (dx, dy)
  * is the source pixel's offset from the destination; value = id | hit << 32.  ctr[0]: entries asked for (beyond cap: not written),
  * ctr[1]: samples whose footprint reached further than one pixel (never with a radius of at most 1) */
@@ -59,15 +59,6 @@ __global__ void __launch_bounds__(256) k_im_shade(RenderParams P, WfBuffers W, I
     uint32_t* const qs[1] = {q_out};
     uint32_t* const cs[1] = {count_out};
     block_push<1>(pred, val, qs, cs);
-}
-
-/* between two rounds: the trace kernels' queue heads and hand-back queues, and the count of the queue the next shading pass fills */
-__global__ void __launch_bounds__(64) k_im_reset(WfBuffers W, uint32_t out_ctr) {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    W.counters[CTR(WFC_DRY_WAVES)] = 0;
-    static_assert(WFC_HEADS_END == WFC_EXC_FIRST, "the two ranges are cleared as one");
-    for (int i = WFC_HEADS_FIRST; i < WFC_EXC_END; i++) W.counters[CTR(i)] = 0;
-    W.counters[CTR(out_ctr)] = 0;
 }
 
 /* one sample into every pixel of its box-filter footprint: the own pixel's table in registers, the others as entries of the foreign list */
@@ -177,33 +168,20 @@ struct ImSpill {                                        /* the foreign list of o
 
 int wavefront_idmatte(WavefrontState** state, const RenderParams& P, const std::vector<DTile>& tiles, const uint32_t* d_ids, uint32_t* d_out,
                       hipStream_t stream, double* trace_ms_out) {
-    knobs_begin();
-    { int rc0 = wf_state_init(state); if (rc0) return rc0; }
-    WavefrontState* st = *state;
-    const uint32_t n_slots = (uint32_t)tiles.size() * 256u;
-    const uint32_t total_samples = P.last_sample - P.first_sample;
-    if (n_slots == 0 || total_samples == 0) return FTN_OK;
-    /* the beauty's passes (wf_plan_passes) without the direct-lighting buffers: only camera rays are traced */
-    WfPassPlan plan;
-    int rc = wf_plan_passes(st, P, tiles.size() * 256u, total_samples, false, &plan);
-    if (rc) return rc;
-    const uint32_t S = plan.samples;
-    if ((rc = trace4_prepare(st, P.S))) return rc;
-    WfBuffers W = st->W;
-    W.br = nullptr; W.pd = nullptr; W.pd_md = 0; W.pd_occ = 0; W.drain_sig = nullptr; W.drain_seq = 0; W.serial = 0; W.rng_replay = 0; W.mis_any = 0; W.late_finish = 0;
-    W.gen_blocks = knob("FTN_GEN_BLOCKS", 1);
-    uint32_t valid = 0; for (const DTile& t : tiles) valid += (uint32_t)((t.x1 - t.x0) * (t.y1 - t.y0));
-    W.valid_per_sample = valid;
-
-    /* the foreign list's capacity.  A footprint spans at most 2 pixels of an axis whose radius is at most 0.5 and 3 up to a radius of 1,
-     * so a sample makes at most nx * ny - 1 entries.  A wider radius gets room for all of them; with at most 0.5 in both axes only
-     * rounding makes a footprint leave its pixel (about one sample in 10^5), and one entry per 64 samples is room a thousandfold */
-    const unsigned long long n_samples = (unsigned long long)valid * total_samples;
-    const unsigned long long per_sample = (unsigned long long)((P.radius[0] <= 0.5f ? 2 : 3) * (P.radius[1] <= 0.5f ? 2 : 3) - 1);
-    unsigned long long cap = n_samples * per_sample;
-    if (P.radius[0] <= 0.5f && P.radius[1] <= 0.5f) cap = std::min(cap, std::max(4096ull, n_samples / 64ull));
     ImSpill sp;
-    {
+    unsigned long long cap = 0;
+    ImParams G;
+    G.out = d_out; G.ids = d_ids;
+    WfFirstHitPass pass;
+    pass.what = "the matte";
+    pass.setup = [&](WavefrontState* st, uint32_t valid) -> int {
+        /* the foreign list's capacity.  A footprint spans at most 2 pixels of an axis whose radius is at most 0.5 and 3 up to a radius of 1,
+         * so a sample makes at most nx * ny - 1 entries.  A wider radius gets room for all of them; with at most 0.5 in both axes only
+         * rounding makes a footprint leave its pixel (about one sample in 10^5), and one entry per 64 samples is room a thousandfold */
+        const unsigned long long n_samples = (unsigned long long)valid * (P.last_sample - P.first_sample);
+        const unsigned long long per_sample = (unsigned long long)((P.radius[0] <= 0.5f ? 2 : 3) * (P.radius[1] <= 0.5f ? 2 : 3) - 1);
+        cap = n_samples * per_sample;
+        if (P.radius[0] <= 0.5f && P.radius[1] <= 0.5f) cap = std::min(cap, std::max(4096ull, n_samples / 64ull));
         size_t free_b = 0, total_b = 0;
         WF_TRY(hipMemGetInfo(&free_b, &total_b));
         if (cap >= (1ull << 31) || cap * 40ull > (unsigned long long)free_b) {
@@ -216,46 +194,17 @@ int wavefront_idmatte(WavefrontState** state, const RenderParams& P, const std::
         for (int k = 0; k < 2; k++) { sp.key[k] = base + (size_t)cap * k; sp.val[k] = base + (size_t)cap * (2 + k); }
         sp.ctr = base + (size_t)cap * 4;
         WF_TRY(hipMemsetAsync(sp.ctr, 0, 16, stream));
-    }
-    ImParams G;
-    G.out = d_out; G.ids = d_ids; G.rec = reinterpret_cast<uint2*>(st->pd);        /* the path integrator's 64-byte records: 8 bytes per path used */
-    G.sp_key = sp.key[0]; G.sp_val = sp.val[0]; G.ctr = sp.ctr; G.sp_cap = cap;
-    const bool spheres = P.S.n_spheres != 0;
-    const size_t lds = wf_trace_lds(P.stack_entries);
-    const unsigned trace_grid_max = wf_trace_grid_max(st, lds);
-    double trace_ms = 0.0;
-    for (uint32_t s0 = 0; s0 < total_samples; s0 += S) {
-        const uint32_t Sp = std::min(S, total_samples - s0);
-        W.n_slots = n_slots; W.samples = Sp; W.n_paths = Sp * n_slots; W.first_sample = P.first_sample + s0; W.seg_cap = (uint32_t)st->cap_paths;
-        launch_wf_new_pass(W, P.stats, stream);
-        launch_wf_generate(P, W, 0, stream);
-        const unsigned tg = std::min<unsigned>(trace_grid_max, (2 * W.n_paths + 255) / 256);
-        uint32_t n_q = Sp * valid;
-        for (uint32_t r = 0;; r++) {
-            /* round r traces the queue of round r - 1's pass-throughs; the two queues alternate between q_closest (count WFC_CLOSEST) and q_shadow (WFC_SHADOW) */
-            const bool odd = (r & 1u) != 0;
-            const uint32_t* q_in = odd ? W.q_shadow : W.q_closest;
-            uint32_t* q_out = odd ? W.q_closest : W.q_shadow;
-            const uint32_t c_in = odd ? WFC_SHADOW : WFC_CLOSEST, c_out = odd ? WFC_CLOSEST : WFC_SHADOW;
-            if (r > 0) hipLaunchKernelGGL(k_im_reset, dim3(1), dim3(64), 0, stream, W, c_out);
-            WF_TRY(hipEventRecord(st->ev[0], stream));
-            launch_trace(st, false, 0, spheres, tg, lds, stream, P, W, q_in, &W.counters[CTR(c_in)], &W.counters[CTR(WFC_HEAD_CLOSEST)], 2 * W.n_paths,
-                         r == 0 && W.samples >= knob("FTN_T4_LOCKSTEP_MIN_SPP", 1) /* the camera rays: lockstep parameters, as the beauty's first launch */);
-            WF_TRY(hipEventRecord(st->ev[1], stream));
-            const dim3 sg(std::max<uint32_t>(1u, (n_q + 255) / 256));
-            hipLaunchKernelGGL(k_im_shade, sg, dim3(256), 0, stream, P, W, G, q_in, &W.counters[CTR(c_in)], q_out, &W.counters[CTR(c_out)]);
-            WF_TRY(hipMemcpyAsync(st->host_counters, W.counters, 16 * 32 * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-            WF_TRY(hipStreamSynchronize(stream));
-            float ms = 0.0f; (void)hipEventElapsedTime(&ms, st->ev[0], st->ev[1]); trace_ms += ms;
-            n_q = st->host_counters[CTR(c_out)];
-            if (n_q == 0) break;
-            if (r == IM_MAX_PASS_THROUGH) {
-                wf_set_error("a camera ray passed through more than 4096 null-material surfaces: the matte would be incomplete");
-                return FTN_ERR_INTERNAL;
-            }
-        }
-        hipLaunchKernelGGL(k_im_accumulate, dim3((n_slots + 255) / 256), dim3(256), 0, stream, P, W, G, P.first_sample);
-    }
+        G.rec = reinterpret_cast<uint2*>(st->pd);        /* the path integrator's 64-byte records: 8 bytes per path used */
+        G.sp_key = sp.key[0]; G.sp_val = sp.val[0]; G.ctr = sp.ctr; G.sp_cap = cap;
+        return FTN_OK;
+    };
+    pass.shade = [&](const WfBuffers& W, const uint32_t* q_in, const uint32_t* count_in, uint32_t* q_out, uint32_t* count_out, dim3 grid, hipStream_t sm) {
+        hipLaunchKernelGGL(k_im_shade, grid, dim3(256), 0, sm, P, W, G, q_in, count_in, q_out, count_out);
+    };
+    pass.accumulate = [&](const WfBuffers& W, dim3 grid, hipStream_t sm) { hipLaunchKernelGGL(k_im_accumulate, grid, dim3(256), 0, sm, P, W, G, P.first_sample); };
+    const int rc = wf_first_hit_passes(state, P, tiles, pass, stream, trace_ms_out);
+    if (rc || !sp.mem) return rc;          /* (no list: no tiles or no samples, nothing was launched) */
+    WavefrontState* const st = *state;
     unsigned long long ctr[2] = {0, 0};
     WF_TRY(hipMemcpyAsync(ctr, sp.ctr, 16, hipMemcpyDeviceToHost, stream));
     WF_TRY(hipStreamSynchronize(stream));
@@ -279,7 +228,6 @@ int wavefront_idmatte(WavefrontState** state, const RenderParams& P, const std::
         WF_TRY(hipStreamSynchronize(stream));            /* the list is freed on return */
     }
     WF_TRY(hipGetLastError());
-    if (trace_ms_out) *trace_ms_out = trace_ms;
     return FTN_OK;
 }
 

@@ -21,16 +21,11 @@ int ftn_idmatte_abi_version(void) { return FTN_IDMATTE_ABI_VERSION; }
 static int idmatte_refusals(const ftn_scene* cs, const ftn_camera_desc* cam, const ftn_film_desc* film, const ftn_sampler_desc* sd, const ftn_render_options* opt,
                             const uint32_t* prim_ids, size_t n_prim_ids, const void* out) {
     if (!cs || !cam || !film || !sd || !prim_ids || !out) return fail(FTN_ERR_INVALID_ARGUMENT, "null argument");
-    if (sd->kind == FTN_SAMPLER_TILE_SERIAL)
-        return fail(FTN_ERR_UNSUPPORTED, "the ID-matte pass needs FTN_SAMPLER_INDEXED: with the tile-serial sampler a sample's camera ray depends on everything its tile drew before it");
-    if (sd->kind != FTN_SAMPLER_INDEXED) return fail(FTN_ERR_INVALID_ARGUMENT, "unknown sampler kind");
-    const uint32_t pipeline = opt ? opt->pipeline : FTN_PIPELINE_AUTO;
-    if (pipeline == FTN_PIPELINE_MEGAKERNEL) return fail(FTN_ERR_UNSUPPORTED, "the ID-matte pass runs on the wavefront pipeline (FTN_PIPELINE_AUTO or FTN_PIPELINE_WAVEFRONT)");
-    if (pipeline != FTN_PIPELINE_AUTO && pipeline != FTN_PIPELINE_WAVEFRONT) return fail(FTN_ERR_INVALID_ARGUMENT, "unknown pipeline");
+    if (int no = indexed_sampler_check(sd, "ID-matte")) return no;
+    if (int no = wavefront_pipeline_check(opt, "ID-matte")) return no;
     if (!(film->filter_radius[0] <= 1.0f) || !(film->filter_radius[1] <= 1.0f))
         return fail(FTN_ERR_UNSUPPORTED, "the ID-matte pass takes footprints of up to 3 x 3 pixels: a filter radius of at most 1 in each axis");
-    if ((uint64_t)sd->first_sample > (uint64_t)sd->samples_per_pixel || (uint64_t)sd->first_sample + (uint64_t)sd->sample_count > (uint64_t)sd->samples_per_pixel)
-        return fail(FTN_ERR_INVALID_ARGUMENT, "sample range outside [0, samples_per_pixel]");
+    if (int no = sample_range_check(sd)) return no;
     if (sd->samples_per_pixel >= (1u << IM_SAMPLE_BITS)) return fail(FTN_ERR_UNSUPPORTED, "the ID-matte pass takes fewer than 2^28 samples per pixel");
     const int64_t npix = (int64_t)std::max(0, film->crop[2] - film->crop[0]) * (int64_t)std::max(0, film->crop[3] - film->crop[1]);
     if (npix >= ((int64_t)1 << 31)) return fail(FTN_ERR_INVALID_ARGUMENT, "the crop window must be below 2^31 pixels");
@@ -57,24 +52,9 @@ int ftn_render_idmatte_device(const ftn_scene* cs, const ftn_camera_desc* cam, c
     StageBufs bufs;
     uint32_t* d_ids = nullptr;
     if ((rc = bufs.upload(ids.data(), ids.size(), &d_ids))) return rc;
-
-    ftn_integrator_desc first_hit; memset(&first_hit, 0, sizeof(first_hit)); first_hit.kind = FTN_INTEGRATOR_PATH;
-    RenderParams P = render_params(s, cam, film, sd, &first_hit);
-    if ((rc = scene_tiles(s, film, tr, stream, &P)) || (rc = prepare_film(s, false, stream, &P))) return rc;
-    EventPair ev; if ((rc = ev.start(stream))) return rc;
-    double trace_ms = 0.0;
-    if ((rc = wavefront_idmatte(&s->wf, P, s->sel, d_ids, (uint32_t*)device_pixels, stream, &trace_ms))) {
-        (void)hipStreamSynchronize(stream);              /* d_ids is freed on return */
-        return fail(rc, wavefront_error());
-    }
-    float ms; if ((rc = ev.stop(stream, &ms))) return rc;
-    DevStats ds; if ((rc = read_stats(s, false, &ds))) return rc;
-    if (st) {
-        memset(st, 0, sizeof(*st));
-        st->rays_closest = ds.rays_closest; st->camera_samples = ds.camera_samples; st->spill_samples = ds.spill_samples;
-        st->kernel_ms = ms; st->trace_ms = trace_ms;
-    }
-    return FTN_OK;
+    return first_hit_render(s, cam, film, sd, tr, stream, st, [&](const RenderParams& P, double* trace_ms) {        /* (it drains the stream before a failing return: d_ids is freed here) */
+        return wavefront_idmatte(&s->wf, P, s->sel, d_ids, (uint32_t*)device_pixels, stream, trace_ms);
+    });
 }
 
 int ftn_render_idmatte(const ftn_scene* cs, const ftn_camera_desc* cam, const ftn_film_desc* film, const ftn_sampler_desc* sd,
@@ -83,15 +63,10 @@ int ftn_render_idmatte(const ftn_scene* cs, const ftn_camera_desc* cam, const ft
     if (int no = idmatte_refusals(cs, cam, film, sd, opt, prim_ids, n_prim_ids, out_pixels)) return no;
     if (int no = need_device()) return no;
     if (n_prim_ids != cs->host.order.size()) return fail(FTN_ERR_INVALID_ARGUMENT, "n_prim_ids must be the scene's primitive count (" + std::to_string(cs->host.order.size()) + ")");
-    int rc = bind_scene_device(cs, opt); if (rc) return rc;
+    if (int rc = bind_scene_device(cs, opt)) return rc;
     const size_t npix = (size_t)std::max(0, film->crop[2] - film->crop[0]) * (size_t)std::max(0, film->crop[3] - film->crop[1]);
     /* the caller's tables go to the device and come back: the call continues them */
-    DevBuf<ftn_idmatte_pixel> dev;
-    if ((rc = dev.upload(out_pixels, npix))) { dev.release(); return rc; }
-    rc = ftn_render_idmatte_device(cs, cam, film, sd, tr, opt, prim_ids, n_prim_ids, dev.p ? (void*)dev.p : (void*)out_pixels, nullptr, st);
-    if (rc == FTN_OK && npix && hipMemcpy(out_pixels, dev.p, npix * sizeof(ftn_idmatte_pixel), hipMemcpyDeviceToHost) != hipSuccess) rc = fail(FTN_ERR_NO_DEVICE, "copy back failed");
-    dev.release();
-    return rc;
+    return continue_on_device(out_pixels, npix, [&](void* d) { return ftn_render_idmatte_device(cs, cam, film, sd, tr, opt, prim_ids, n_prim_ids, d, nullptr, st); });
 }
 
 int ftn_idmatte_resolve(const ftn_idmatte_pixel* in, size_t n, void* out20) {

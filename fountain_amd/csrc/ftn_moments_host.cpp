@@ -14,16 +14,11 @@ using namespace ftn;
 
 /* every refusal of the moments pass: host-side checks only, before any device work */
 int moments_refusals(const ftn_scene* s, const ftn_sampler_desc* sd, const ftn_integrator_desc* id, const ftn_render_options* opt) {
-    if (sd->kind == FTN_SAMPLER_TILE_SERIAL)
-        return fail(FTN_ERR_UNSUPPORTED, "the moments pass needs FTN_SAMPLER_INDEXED: it runs on the wavefront pipeline's sample-indexed passes");
-    if (sd->kind != FTN_SAMPLER_INDEXED) return fail(FTN_ERR_INVALID_ARGUMENT, "unknown sampler kind");
-    if ((uint64_t)sd->first_sample > (uint64_t)sd->samples_per_pixel || (uint64_t)sd->first_sample + (uint64_t)sd->sample_count > (uint64_t)sd->samples_per_pixel)
-        return fail(FTN_ERR_INVALID_ARGUMENT, "sample range outside [0, samples_per_pixel]");
+    if (int no = indexed_sampler_check(sd, "moments", "it runs on the wavefront pipeline's sample-indexed passes")) return no;
+    if (int no = sample_range_check(sd)) return no;
     if (id->kind != FTN_INTEGRATOR_PATH && id->kind != FTN_INTEGRATOR_DIRECT_LIGHTING && id->kind != FTN_INTEGRATOR_WHITTED) return fail(FTN_ERR_INVALID_ARGUMENT, "unknown integrator kind");
     if (id->max_depth > 65535u) return fail(FTN_ERR_INVALID_ARGUMENT, "max_depth is a u16 in the reference (integrator/path.rs:14)");
-    const uint32_t pipeline = opt ? opt->pipeline : FTN_PIPELINE_AUTO;
-    if (pipeline == FTN_PIPELINE_MEGAKERNEL) return fail(FTN_ERR_UNSUPPORTED, "the moments pass runs on the wavefront pipeline (FTN_PIPELINE_AUTO or FTN_PIPELINE_WAVEFRONT)");
-    if (pipeline != FTN_PIPELINE_AUTO && pipeline != FTN_PIPELINE_WAVEFRONT) return fail(FTN_ERR_INVALID_ARGUMENT, "unknown pipeline");
+    if (int no = wavefront_pipeline_check(opt, "moments")) return no;
     if (id->kind == FTN_INTEGRATOR_WHITTED && s->d.n_lights > 32u)
         return fail(FTN_ERR_UNSUPPORTED, "the wavefront pipeline renders WhittedIntegrator with up to 32 lights (one bit per light in a path's pending-light word)");
     return FTN_OK;

@@ -1,7 +1,9 @@
 /*
  * ftn_stage_host.h -- what the host files of the image-space stages share (ftn_denoise_host.cpp, ftn_temporal_host.cpp,
  * ftn_display_host.cpp, ftn_bloom_host.cpp, ftn_metrics_host.cpp): the refusals every stage makes in the same words, the overlap and alignment rules over byte
- * ranges, the launch result, and the device buffers of a host-buffer entry.  need_device() also serves the other host files.
+ * ranges, the launch result, and the device buffers of a host-buffer entry.  need_device() also serves the other host files, and the sampler,
+ * pipeline and sample-range refusals are those of the passes on the wavefront pipeline (ftn_gbuffer_host.cpp, ftn_idmatte_host.cpp,
+ * ftn_moments_host.cpp).
  *
  * Like ftn_host_internal.h, which it builds on, everything here has hidden visibility and exports nothing.
  */
@@ -12,6 +14,27 @@
 #pragma GCC visibility push(hidden)
 
 inline int need_device() { return ftn_device_count() <= 0 ? fail(FTN_ERR_NO_DEVICE, kNoDevice) : FTN_OK; }
+
+/* The refusals the passes on the wavefront pipeline's sample-indexed passes make in the same words (G-buffer, ID mattes, moments): one
+ * check each, so that every entry keeps the order of its own.  pass: "G-buffer", "ID-matte", "moments" */
+inline int indexed_sampler_check(const ftn_sampler_desc* sd, const char* pass,
+                                 const char* why = "with the tile-serial sampler a sample's camera ray depends on everything its tile drew before it") {
+    if (sd->kind == FTN_SAMPLER_TILE_SERIAL) return fail(FTN_ERR_UNSUPPORTED, std::string("the ") + pass + " pass needs FTN_SAMPLER_INDEXED: " + why);
+    if (sd->kind != FTN_SAMPLER_INDEXED) return fail(FTN_ERR_INVALID_ARGUMENT, "unknown sampler kind");
+    return FTN_OK;
+}
+inline int wavefront_pipeline_check(const ftn_render_options* opt, const char* pass) {
+    const uint32_t pipeline = opt ? opt->pipeline : FTN_PIPELINE_AUTO;
+    if (pipeline == FTN_PIPELINE_MEGAKERNEL)
+        return fail(FTN_ERR_UNSUPPORTED, std::string("the ") + pass + " pass runs on the wavefront pipeline (FTN_PIPELINE_AUTO or FTN_PIPELINE_WAVEFRONT)");
+    if (pipeline != FTN_PIPELINE_AUTO && pipeline != FTN_PIPELINE_WAVEFRONT) return fail(FTN_ERR_INVALID_ARGUMENT, "unknown pipeline");
+    return FTN_OK;
+}
+inline int sample_range_check(const ftn_sampler_desc* sd) {
+    if ((uint64_t)sd->first_sample > (uint64_t)sd->samples_per_pixel || (uint64_t)sd->first_sample + (uint64_t)sd->sample_count > (uint64_t)sd->samples_per_pixel)
+        return fail(FTN_ERR_INVALID_ARGUMENT, "sample range outside [0, samples_per_pixel]");
+    return FTN_OK;
+}
 
 inline int image_check(int32_t w, int32_t h) {
     if (w <= 0 || h <= 0) return fail(FTN_ERR_INVALID_ARGUMENT, "image width and height must be positive");

@@ -5,10 +5,12 @@
  * Here a PASS renders S samples of every owned pixel at once (one wavefront of up to 256 Mi paths, path id = slot * S + sample);
  * paths live as float4 SoA records in HBM and every bounce runs kernels over queues of path / ray ids.  The units:
  *
- *   ftn_wavefront.hip     (this file) the two render drivers -- indexed sampler in passes, tile-serial sampler in rounds -- and the
- *                         kernels around a pass: k_wf_generate (get_camera_sample + generate_ray; all paths -> closest queue),
- *                         k_wf_reset (counters between kernels), k_wf_accumulate (Film::add_sample_to_tile in sample order; under late
- *                         finish it also finishes the ended paths, wf_finish_path), k_wf_serial_advance (the tile-serial streams)
+ *   ftn_wavefront.hip     (this file) the two render drivers -- indexed sampler in passes, tile-serial sampler in rounds --, the driver
+ *                         of the first-hit passes (wf_first_hit_passes: G-buffer, ID mattes) and the kernels around a pass:
+ *                         k_wf_generate (get_camera_sample + generate_ray; all paths -> closest queue), k_wf_reset (counters between
+ *                         kernels), k_wf_round_reset (between the rounds of a first-hit pass), k_wf_accumulate
+ *                         (Film::add_sample_to_tile in sample order; under late finish it also finishes the ended paths,
+ *                         wf_finish_path), k_wf_serial_advance (the tile-serial streams)
  *   ftn_wf_trace.hip      k_wf_trace<ANY>, k_wf_trace_any2, the coherence sort, launch_trace, wavefront_trace_batch
  *   ftn_trace4.hip        the production traversal kernels over four-box records that launch_trace prefers
  *   ftn_wf_shade.hip      k_wf_classify, k_wf_shade<TEX, MT, ENV>, k_wf_shade_dl (DirectLightingIntegrator / WhittedIntegrator) and
@@ -17,8 +19,8 @@
  *
  * Small wavefronts (<= 32 Mi paths) run the any-hit trace of a bounce on a second stream beside the closest-hit trace.
  *
- * Interfaces: ftn_wavefront.h is what the host library calls; ftn_wf_internal.h declares what the units above and the drivers of the
- * other passes (ftn_gbuffer.hip) share on the host side; ftn_wf_common.h and ftn_wf_path.h hold the device-side pieces their kernels share.
+ * Interfaces: ftn_wavefront.h is what the host library calls; ftn_wf_internal.h declares what the units above and the other
+ * passes' units (ftn_gbuffer.hip, ftn_idmatte.hip) share on the host side; ftn_wf_common.h and ftn_wf_path.h hold the device-side pieces their kernels share.
  *
  * All per-path arithmetic and the order of the RNG draws are those of the reference (and of the megakernel), so both
  * pipelines produce identical radiance.  Dominant kernel: the closest-hit traversal; roofline = HBM (node + triangle fetches), in
@@ -93,6 +95,16 @@ __global__ void k_wf_reset(WfBuffers W, int mode, int in_q, DevStats* stats) {
     } else if (mode == 3) {                                                                  /* tile-serial pass: the queues start empty, k_wf_serial_advance fills them */
         for (int i = 0; i < WFC_SLOTS; i++) W.counters[CTR(i)] = 0;
     }
+}
+
+/* between two pass-through rounds of a first-hit pass (wf_first_hit_passes): the trace kernels' queue heads and hand-back queues, and the
+ * count of the queue the next shading pass fills */
+__global__ void __launch_bounds__(64) k_wf_round_reset(WfBuffers W, uint32_t out_ctr) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    W.counters[CTR(WFC_DRY_WAVES)] = 0;
+    static_assert(WFC_HEADS_END == WFC_EXC_FIRST, "the two ranges are cleared as one");
+    for (int i = WFC_HEADS_FIRST; i < WFC_EXC_END; i++) W.counters[CTR(i)] = 0;
+    W.counters[CTR(out_ctr)] = 0;
 }
 
 /* ------------------------------------------------------------------ accumulate: add_sample_to_tile in sample order */
@@ -508,6 +520,70 @@ int wavefront_render(WavefrontState** state, const RenderParams& P0, const std::
         times->trace_ms = trace_ms; times->trace_launches = trace_launches; times->mis_any_rays = mis_any_rays;
         times->any_ms = group_ms[1]; times->any_launches = group_n[1]; times->shade_ms = group_ms[2]; times->shade_launches = group_n[2]; times->sort_ms = group_ms[3];
     }
+    return FTN_OK;
+}
+
+/* ------------------------------------------------------------------ the first-hit passes (G-buffer, ID mattes): the camera samples of ftn_render for
+ * the same sampler, tiles and film.  k_wf_generate makes the camera rays from the sample keys, the production closest-hit kernels trace
+ * them, and the pass's shade kernel records the first surface that has a material.  A null-material hit spawns the ray on along the same
+ * direction (path.rs:77-80) into the other queue and the round repeats, at most WF_MAX_PASS_THROUGH times; the pass's accumulate kernel
+ * then takes the samples of every pixel in sample order. */
+#define WF_MAX_PASS_THROUGH 4096u
+int wf_first_hit_passes(WavefrontState** state, const RenderParams& P, const std::vector<DTile>& tiles, const WfFirstHitPass& pass, hipStream_t stream, double* trace_ms_out) {
+    knobs_begin();
+    { int rc0 = wf_state_init(state); if (rc0) return rc0; }
+    WavefrontState* st = *state;
+    const uint32_t n_slots = (uint32_t)tiles.size() * 256u;
+    const uint32_t total_samples = P.last_sample - P.first_sample;
+    if (n_slots == 0 || total_samples == 0) return FTN_OK;
+    /* the beauty's passes (wf_plan_passes) without the direct-lighting buffers: only camera rays are traced */
+    WfPassPlan plan;
+    int rc = wf_plan_passes(st, P, tiles.size() * 256u, total_samples, false, &plan);
+    if (rc) return rc;
+    const uint32_t S = plan.samples;
+    if ((rc = trace4_prepare(st, P.S))) return rc;
+    WfBuffers W = st->W;
+    W.br = nullptr; W.pd = nullptr; W.pd_md = 0; W.pd_occ = 0; W.drain_sig = nullptr; W.drain_seq = 0; W.serial = 0; W.rng_replay = 0; W.mis_any = 0; W.late_finish = 0;
+    W.gen_blocks = knob("FTN_GEN_BLOCKS", 1);
+    uint32_t valid = 0; for (const DTile& t : tiles) valid += (uint32_t)((t.x1 - t.x0) * (t.y1 - t.y0));
+    W.valid_per_sample = valid;
+    if ((rc = pass.setup(st, valid))) return rc;
+    const bool spheres = P.S.n_spheres != 0;
+    const size_t lds = wf_trace_lds(P.stack_entries);
+    const unsigned trace_grid_max = wf_trace_grid_max(st, lds);
+    double trace_ms = 0.0;
+    for (uint32_t s0 = 0; s0 < total_samples; s0 += S) {
+        const uint32_t Sp = std::min(S, total_samples - s0);
+        W.n_slots = n_slots; W.samples = Sp; W.n_paths = Sp * n_slots; W.first_sample = P.first_sample + s0; W.seg_cap = (uint32_t)st->cap_paths;
+        launch_wf_new_pass(W, P.stats, stream);
+        launch_wf_generate(P, W, 0, stream);
+        const unsigned tg = std::min<unsigned>(trace_grid_max, (2 * W.n_paths + 255) / 256);
+        uint32_t n_q = Sp * valid;
+        for (uint32_t r = 0;; r++) {
+            /* round r traces the queue of round r - 1's pass-throughs; the two queues alternate between q_closest (count WFC_CLOSEST) and q_shadow (WFC_SHADOW) */
+            const bool odd = (r & 1u) != 0;
+            const uint32_t* q_in = odd ? W.q_shadow : W.q_closest;
+            uint32_t* q_out = odd ? W.q_closest : W.q_shadow;
+            const uint32_t c_in = odd ? WFC_SHADOW : WFC_CLOSEST, c_out = odd ? WFC_CLOSEST : WFC_SHADOW;
+            if (r > 0) hipLaunchKernelGGL(k_wf_round_reset, dim3(1), dim3(64), 0, stream, W, c_out);
+            WF_TRY(hipEventRecord(st->ev[0], stream));
+            launch_trace(st, false, 0, spheres, tg, lds, stream, P, W, q_in, &W.counters[CTR(c_in)], &W.counters[CTR(WFC_HEAD_CLOSEST)], 2 * W.n_paths,
+                         r == 0 && W.samples >= knob("FTN_T4_LOCKSTEP_MIN_SPP", 1) /* the camera rays: lockstep parameters, as the beauty's first launch */);
+            WF_TRY(hipEventRecord(st->ev[1], stream));
+            pass.shade(W, q_in, &W.counters[CTR(c_in)], q_out, &W.counters[CTR(c_out)], dim3(std::max<uint32_t>(1u, (n_q + 255) / 256)), stream);
+            WF_TRY(hipMemcpyAsync(st->host_counters, W.counters, 16 * 32 * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+            WF_TRY(hipStreamSynchronize(stream));
+            float ms = 0.0f; (void)hipEventElapsedTime(&ms, st->ev[0], st->ev[1]); trace_ms += ms;
+            n_q = st->host_counters[CTR(c_out)];
+            if (n_q == 0) break;
+            if (r == WF_MAX_PASS_THROUGH) {
+                wf_set_error(std::string("a camera ray passed through more than 4096 null-material surfaces: ") + pass.what + " would be incomplete");
+                return FTN_ERR_INTERNAL;
+            }
+        }
+        pass.accumulate(W, dim3((n_slots + 255) / 256), stream);
+    }
+    if (trace_ms_out) *trace_ms_out = trace_ms;
     return FTN_OK;
 }
 

@@ -5,8 +5,12 @@
  *   ftn_wf_trace.hip      the reference-order traversal kernels, the coherence sort, launch_trace, the ray-batch entry point
  *   ftn_wf_shade.hip      k_wf_classify, k_wf_shade (path integrator), k_wf_shade_dl (direct lighting / Whitted) and k_batch_finish with
  *                         their launchers
- *   ftn_wavefront.hip     generate / reset / accumulate / serial-advance and the two render drivers
- *   ftn_gbuffer.hip       the G-buffer pass and its driver
+ *   ftn_wavefront.hip     generate / reset / accumulate / serial-advance, the two render drivers and the first-hit passes' driver
+ *   ftn_gbuffer.hip       the G-buffer pass: its kernels, and what it hands wf_first_hit_passes
+ *   ftn_idmatte.hip       the ID-matte pass, likewise, with its foreign list, resolve and matte extraction
+ *
+ * The passes beside the beauty need nothing declared here: ftn_moments.hip hooks its kernel behind every pass of the public
+ * wavefront_render (ftn_wavefront.h, ftn_wf_common.h), and ftn_adaptive.hip decides between rounds that are such calls.
  *
  * A kernel is launched from the unit that defines it; what another unit needs of it is a launcher declared here.  Declarations only,
  * all of hidden visibility: the library exports the C ABI alone.
@@ -14,7 +18,9 @@
 #ifndef FTN_WF_INTERNAL_H
 #define FTN_WF_INTERNAL_H
 #include "ftn_wf_common.h"
+#include <functional>
 #include <string>
+#include <vector>
 
 #pragma GCC visibility push(hidden)
 namespace ftn {
@@ -109,6 +115,22 @@ void launch_batch_finish(const DScene& S, const float* d_rays8, uint32_t n, cons
  * with their launch parameters */
 void launch_wf_new_pass(const WfBuffers& W, DevStats* stats, hipStream_t stream);
 void launch_wf_generate(const RenderParams& P, const WfBuffers& W, int write_state, hipStream_t stream);
+
+/* What a first-hit pass (G-buffer, ID mattes) hands the driver below.  The kernels stay in the pass's unit; these launch them. */
+struct WfFirstHitPass {
+    const char* what;          /* "the G-buffer", "the matte": what would be incomplete after 4096 pass-through rounds */
+    /* once per call, behind the pass plan: the per-path record buffer is st->pd (64 bytes per path), valid_per_sample the tiles' pixel count */
+    std::function<int(WavefrontState* st, uint32_t valid_per_sample)> setup;
+    /* one round's shade kernel over q_in[0, *count_in): records first hits, pushes null-material pass-throughs to q_out / *count_out */
+    std::function<void(const WfBuffers& W, const uint32_t* q_in, const uint32_t* count_in, uint32_t* q_out, uint32_t* count_out, dim3 grid, hipStream_t stream)> shade;
+    /* one pass's accumulate kernel: one thread per pixel slot */
+    std::function<void(const WfBuffers& W, dim3 grid, hipStream_t stream)> accumulate;
+};
+/* Renders P's sample range of the tiles' camera samples through `pass`, in the beauty's passes (wf_plan_passes without direct lighting):
+ * per pass k_wf_reset, k_wf_generate, then rounds of closest-hit trace and pass.shade until no ray passed through a null material
+ * (k_wf_round_reset between them; more than 4096 rounds: FTN_ERR_INTERNAL), then pass.accumulate.  Without tiles or samples it returns
+ * FTN_OK before pass.setup.  *trace_ms_out: the trace launches' time.  The caller runs what follows the last pass. */
+int wf_first_hit_passes(WavefrontState** state, const RenderParams& P, const std::vector<DTile>& tiles, const WfFirstHitPass& pass, hipStream_t stream, double* trace_ms_out);
 
 }  // namespace ftn
 #pragma GCC visibility pop

@@ -259,3 +259,18 @@ def textured_floor(be, res=(64, 48), null_layer=True):
     b.attribute_begin(); b.material("matte", Kd=(0.3, 0.6, 0.3)); b.translate((-0.8, 0.2, 0.35)); b.shape("sphere", radius=0.35); b.attribute_end()
     cam = PerspectiveCamera.look_at(be, (0.0, -3.0, 0.6), (0.0, 6.0, 0.25), (0, 0, 1), res, fov=60.0)
     return b, cam, res
+
+
+def null_layers_over_plane(be, kd=(0.4, 0.5, 0.6), h=4.0, layers=(1.0, 2.0, 3.0)):
+    """a matte plane at z = 0 under one null-material quad per entry of `layers` (its z), seen from straight above at height h on a
+    24 x 24 film: every camera ray passes through every layer, one pass-through round each, before it finds the plane"""
+    from fountain_amd import PerspectiveCamera, SceneBuilder, scenes
+    b = SceneBuilder(be)
+    b.light_source("point", I=(5, 5, 5), from_=(0, 0, 3))
+    b.material("matte", Kd=kd)
+    scenes._quad(b, (-50, -50, 0), (50, -50, 0), (50, 50, 0), (-50, 50, 0))
+    b.material("none")
+    for z in layers:
+        scenes._quad(b, (-50, -50, z), (50, -50, z), (50, 50, z), (-50, 50, z))
+    cam = PerspectiveCamera.look_at(be, (0, 0, h), (0, 0, 0), (0, 1, 0), (24, 24), fov=50.0)
+    return b, cam, (24, 24)

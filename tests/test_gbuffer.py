@@ -131,6 +131,24 @@ def test_null_material_pass_through(gpu):
     assert st["rays_closest"] == 2 * st["camera_samples"]          # every camera ray passed through the quad once
 
 
+def test_three_null_layers_pass_through(gpu):
+    """three null-material quads over the plane: four rounds of the pass-through loop, so both of its queues are read, refilled and
+    reset in turn (one layer leaves the loop after its first swap)"""
+    kd, h, spp = (0.4, 0.5, 0.6), 4.0, 2
+    b, cam, res = GR.null_layers_over_plane(gpu, kd, h, (1.0, 2.0, 3.0))
+    r, raw, st = G.render_gbuffer(gpu, b, cam, res, RandomSampler(spp, 3, indexed=True))
+    assert st["camera_samples"] == spp * res[0] * res[1] and st["spill_samples"] == 0
+    assert (raw[..., 10] == float(spp)).all() and (raw[..., 11] == float(spp)).all()          # every sample of every pixel hit
+    kd2 = np.array(kd, F32) + np.array(kd, F32)                                                 # the sum of two samples: exact
+    assert np.array_equal(bits(raw[..., 0:3]), bits(np.broadcast_to(kd2, raw[..., 0:3].shape)))
+    assert np.array_equal(bits(r["albedo"]), bits(np.broadcast_to(np.array(kd, F32), r["albedo"].shape)))
+    n = raw[..., 3:6].reshape(-1, 3)
+    assert np.array_equal(bits(np.abs(n)), bits(np.broadcast_to(np.array([0, 0, spp], F32), n.shape))) and len({tuple(v) for v in n.tolist()}) == 1
+    assert np.abs(raw[..., 8]).max() <= 1e-5 * np.abs(raw[..., 6:8]).max()
+    assert np.allclose(raw[..., 9], spp * h, rtol=1e-5)
+    assert st["rays_closest"] == 4 * st["camera_samples"]          # every camera ray passed through the three quads
+
+
 # ------------------------------------------------------------------ 4. splits and the device path
 def test_sample_splits_and_device_path(gpu):
     import torch

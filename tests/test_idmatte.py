@@ -78,6 +78,23 @@ def test_reconstruction_crops_strides_ranges_radii(gpu, orc_det, radius, crop, t
     assert_equal_tables(raw, ref["raw"], "radius %r crop %r tiles %r" % (radius, crop, tiles))
 
 
+def test_three_null_layers_pass_through(gpu):
+    """three null-material quads over a matte plane (tests/test_gbuffer.py has the same case): four rounds of the pass-through loop, so
+    both of its queues are read, refilled and reset in turn; every sample of every pixel ends on the plane, none on a layer"""
+    spp = 2
+    b, cam, res = GR.null_layers_over_plane(gpu)
+    ids, _ = I.prim_ids(b, "shape")
+    plane = int(ids[0])
+    assert plane not in ids[2:].tolist() and len(ids) == 8          # the plane's two triangles, then the layers': ids of their own
+    _, raw, st = I.render_idmatte(gpu, b, cam, res, RandomSampler(spp, 3, indexed=True), ids)
+    f = I.fields(raw)
+    assert st["camera_samples"] == spp * res[0] * res[1] and st["spill_samples"] == 0
+    assert (f["n_used"] == 1).all() and (f["id"][..., 0] == plane).all() and (f["weight"][..., 0] == float(spp)).all()
+    assert (f["weight"][..., 1:] == 0.0).all() and (f["overflow"] == 0.0).all()
+    assert (f["miss"] == 0.0).all() and (f["total"] == float(spp)).all()
+    assert st["rays_closest"] == 4 * st["camera_samples"]          # every camera ray passed through the three quads
+
+
 def test_device_entry(gpu, orc_det):
     import torch
     spp, seed, radius = 4, 11, (1.0, 1.0)

@@ -22,14 +22,9 @@ static std::string g_err;
 int fail(int code, const std::string& msg) { g_err = msg; return code; }
 extern "C" int ftn_device_count(void) { return 0; }
 int bind_scene_device(const ftn_scene*, const ftn_render_options*) { abort(); }
-int scene_tiles(ftn_scene*, const ftn_film_desc*, const ftn_tile_range*, hipStream_t, ftn::RenderParams*) { abort(); }
-int prepare_film(ftn_scene*, bool, hipStream_t, ftn::RenderParams*) { abort(); }
-ftn::RenderParams render_params(const ftn_scene*, const ftn_camera_desc*, const ftn_film_desc*, const ftn_sampler_desc*, const ftn_integrator_desc*) { abort(); }
-int read_stats(ftn_scene*, bool, ftn::DevStats*) { abort(); }
-int EventPair::start(hipStream_t) { abort(); }
-int EventPair::stop(hipStream_t, float*) { abort(); }
+int first_hit_render(ftn_scene*, const ftn_camera_desc*, const ftn_film_desc*, const ftn_sampler_desc*, const ftn_tile_range*, hipStream_t, ftn_stats*,
+                     const std::function<int(const ftn::RenderParams&, double*)>&) { abort(); }
 namespace ftn {
-const char* wavefront_error() { return ""; }
 int wavefront_idmatte(WavefrontState**, const RenderParams&, const std::vector<DTile>&, const uint32_t*, uint32_t*, hipStream_t, double*) { abort(); }
 void launch_idmatte_resolve(const uint32_t*, size_t, uint32_t*, hipStream_t) { abort(); }
 void launch_idmatte_select(const uint32_t*, size_t, const uint32_t*, size_t, uint32_t, float*, hipStream_t) { abort(); }

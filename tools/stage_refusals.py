@@ -1,7 +1,10 @@
 """The refusals of the image-space stages' C entry points, as a transcript: for every entry of include/fountain_hip_{denoise,
 denoise_guided,temporal,display,bloom}.h a fixed list of bad calls -- each pointer null in turn, w = 0, w * h = 2^31, each params field
 out of range, and for the device entries each overlapping pair of buffers and each buffer misaligned -- and one good call, which on a
-machine without a GPU is the no-device refusal of every entry but the host twins.  Prints `entry, case, status, ftn_last_error()`.
+machine without a GPU is the no-device refusal of every entry but the host twins.  Then the render and resolve entries of the passes
+beside the beauty (include/fountain_hip_{gbuffer,idmatte,moments}.h): each pointer null in turn, the tile-serial and an unknown sampler,
+the megakernel and an unknown pipeline, a filter radius above 1, a sample range outside, pairs of those (which one an entry reports
+first), and the good call.  Prints `entry, case, status, ftn_last_error()`.
 
   python tools/stage_refusals.py [path/to/libfountain_hip.so] > transcript.txt
 
@@ -172,6 +175,78 @@ def cases(call):
         yield "null hist, automatic", {"a0": None, "a1": p}
 
 
+# ---------------------------------------------------------------------- the render passes beside the beauty
+# The render and resolve entries of include/fountain_hip_{gbuffer,idmatte,moments}.h.  Arguments by name, in call order; "scene" is 64 KiB
+# of zeros (no entry looks behind the handle before it has found a device), the pixel buffers are host memory.
+PASS_RENDER = {
+    "gbuffer": ["scene", "cam", "film", "sd", "tr", "opt", "pixels"],
+    "idmatte": ["scene", "cam", "film", "sd", "tr", "opt", "prim_ids", "n_prim_ids", "pixels"],
+    "moments": ["scene", "cam", "film", "sd", "id", "tr", "opt", "pixels", "moments"],
+}
+PASS_RESOLVE = {"gbuffer": ["in", "n", "out"], "idmatte": ["in", "n", "out"], "moments": ["beauty", "in", "n", "out"]}
+PASS_OPTIONAL = ("tr", "opt", "stream", "st")          # null is a good value
+
+
+def pass_args(names):
+    sd = A.ftn_sampler_desc(A.FTN_SAMPLER_INDEXED, 4, 7, 1, 2)
+    made = {"scene": (C.c_char * 65536)(), "cam": camera(), "film": film(), "sd": sd, "id": A.ftn_integrator_desc(A.FTN_INTEGRATOR_PATH, 5, 1.0, 0),
+            "tr": None, "opt": None, "stream": C.c_void_p(None), "st": None, "prim_ids": (C.c_uint32 * 4)(1, 2, 3, 4), "n_prim_ids": C.c_size_t(4),
+            "n": C.c_size_t(W * H)}
+    for k in ("pixels", "moments", "in", "out", "beauty"):
+        made[k] = (C.c_float * (20 * W * H))()
+    return [made[k] for k in names]
+
+
+def pass_cases(names, render):
+    yield "good", {}
+    for k in names:
+        if k not in PASS_OPTIONAL and not k.startswith("n"):
+            yield "null %s" % k, {k: None}
+    if not render:
+        yield "n = 0, all null", {k: (C.c_size_t(0) if k == "n" else None) for k in names if k != "stream"}
+        return
+    for label, kind in (("tile-serial sampler", A.FTN_SAMPLER_TILE_SERIAL), ("unknown sampler", 7)):
+        yield label, {"sd": A.ftn_sampler_desc(kind, 4, 7, 1, 2)}
+    for label, pl in (("megakernel pipeline", A.FTN_PIPELINE_MEGAKERNEL), ("unknown pipeline", 9)):
+        yield label, {"opt": A.ftn_render_options(pl, -1, 0, 0)}
+    f = film()
+    f.filter_radius[1] = 1.5
+    yield "filter radius 1.5", {"film": f}
+    yield "first_sample beyond samples_per_pixel", {"sd": A.ftn_sampler_desc(A.FTN_SAMPLER_INDEXED, 4, 7, 5, 0)}
+    yield "sample range beyond samples_per_pixel", {"sd": A.ftn_sampler_desc(A.FTN_SAMPLER_INDEXED, 4, 7, 3, 2)}
+    # two refusals at once: the first in the entry's order is the one reported
+    yield "tile-serial sampler, megakernel pipeline", {"sd": A.ftn_sampler_desc(A.FTN_SAMPLER_TILE_SERIAL, 4, 7, 1, 2), "opt": A.ftn_render_options(A.FTN_PIPELINE_MEGAKERNEL, -1, 0, 0)}
+    yield "megakernel pipeline, sample range outside", {"sd": A.ftn_sampler_desc(A.FTN_SAMPLER_INDEXED, 4, 7, 3, 2), "opt": A.ftn_render_options(A.FTN_PIPELINE_MEGAKERNEL, -1, 0, 0)}
+    yield "filter radius 1.5, sample range outside", {"film": f, "sd": A.ftn_sampler_desc(A.FTN_SAMPLER_INDEXED, 4, 7, 3, 2)}
+    if "id" in names:
+        yield "unknown integrator, unknown pipeline", {"id": A.ftn_integrator_desc(9, 5, 1.0, 0), "opt": A.ftn_render_options(9, -1, 0, 0)}
+        yield "sample range outside, max_depth 65536", {"sd": A.ftn_sampler_desc(A.FTN_SAMPLER_INDEXED, 4, 7, 3, 2), "id": A.ftn_integrator_desc(A.FTN_INTEGRATOR_PATH, 65536, 1.0, 0)}
+
+
+def pass_entries(lib):
+    """(entry, argument names, is it a render entry) of the three headers"""
+    for p in ("gbuffer", "idmatte", "moments"):
+        yield "ftn_render_%s_device" % p, PASS_RENDER[p] + ["stream", "st"], True
+        yield "ftn_render_%s" % p, PASS_RENDER[p] + ["st"], True
+        yield "ftn_%s_resolve" % p, PASS_RESOLVE[p], False
+        yield "ftn_%s_resolve_device" % p, PASS_RESOLVE[p] + ["stream"], False
+
+
+def run_passes(lib):
+    if lib.ftn_device_count() > 0:          # a call that gets as far as the device would look behind the scene handle
+        print("the render passes' entries: left out, a device is present")
+        return
+    for name, names, render in pass_entries(lib):
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = C.c_int, None
+        good = pass_args(names)
+        for case, replace in pass_cases(names, render):
+            args = [replace.get(k, v) for k, v in zip(names, good)]
+            args = [C.byref(v) if isinstance(v, C.Structure) else v for v in args]
+            status = fn(*args)
+            print("%s, %s, %d, %s" % (name, case, status, lib.ftn_last_error().decode() if status else ""))
+
+
 def main(argv):
     path = argv[1] if len(argv) > 1 else os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "fountain_amd", "libfountain_hip.so")
     lib = C.CDLL(path)
@@ -181,6 +256,7 @@ def main(argv):
         for case, replace in cases(call):
             status = call.run(**replace)
             print("%s, %s, %d, %s" % (name, case, status, lib.ftn_last_error().decode() if status else ""))
+    run_passes(lib)
     return 0
 
 
