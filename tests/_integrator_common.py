@@ -173,6 +173,24 @@ def gallery(be, res=(24, 16)):
     return b, cam, res
 
 
+def emitters(be, res=(16, 16)):
+    """five emitting triangles and an emitting sphere spread over space above a matte floor and in front of a matte wall, and a point light: the order
+    of Scene::lights for several emitters is the BVH's primitive order (scene/mod.rs:38-42), which differs from the order they are stated in; the
+    traversal tests check that order from the tree, so that area_order is a checked fact here"""
+    b = SceneBuilder(be)
+    b.light_source("point", I=(6, 6, 6), from_=(0.0, -1.0, 2.5))
+    b.material("matte", Kd=(0.6, 0.55, 0.5))
+    quad(b, (-4, -4, 0), (4, -4, 0), (4, 4, 0), (-4, 4, 0))
+    b.material("matte", Kd=(0.4, 0.5, 0.6))
+    quad(b, (-4, 4, 0), (4, 4, 0), (4, 4, 4), (-4, 4, 4))
+    for i, (x, y, z) in enumerate(((2.5, 1.0, 2.0), (-2.6, 0.5, 1.5), (0.3, 2.5, 3.0), (-1.0, -1.5, 2.2), (1.4, -0.8, 1.2))):
+        triangle_light(b, z=z, L=(4.0 + i, 5.0, 8.0 - i), half=0.3, at=(x, y))
+    b.attribute_begin(); b.material("matte", Kd=(0, 0, 0)); b.area_light_source("diffuse", L=(5, 5, 4)); b.translate((-0.5, 1.2, 1.0))
+    b.shape("sphere", radius=0.35); b.attribute_end()
+    cam = PerspectiveCamera.look_at(be, (0.2, -5.5, 2.0), (0.0, 0.5, 1.2), (0, 0, 1), res, fov=50.0)
+    return b, cam, res
+
+
 # ------------------------------------------------------------------ configurations
 class Config:
     """floor: the value metric's floor, a hundredth of the largest radiance a light of the scene gives a surface (written next to each configuration,
@@ -225,6 +243,8 @@ _C = [
     # textures: the point light gives the floor I / r^2 = 14 / 2.2^2 = 2.9, the triangle 7 -> 0.07
     Config("checker_path", lambda be: textured_room(be, False), "path", 3, 1.0, 4, 61, 0.07), Config("checker_direct", lambda be: textured_room(be, False), "direct", 3, 0.0, 4, 62, 0.07),
     Config("image_path", lambda be: textured_room(be, True), "path", 3, 1.0, 4, 63, 0.07), Config("image_direct", lambda be: textured_room(be, True), "direct", 3, 0.0, 4, 64, 0.07),
+    # six emitters and a point light: L up to 8 -> 0.08
+    Config("emitters_direct", emitters, "direct", 1, 0.0, 4, 91, 0.08),
 ]
 CONFIGS = {c.name: c for c in _C}
 
@@ -272,6 +292,7 @@ MEASURED = {
     "checker_direct": (4.931e-06, 5.450e-06, 0.000000),
     "image_path": (7.425e-06, 8.405e-06, 0.000000),
     "image_direct": (1.077e-05, 1.780e-05, 0.000000),
+    "emitters_direct": (6.167e-04, 6.885e-04, 0.000977),
 }
 TOLERANCE = {k: (4.0 * v[0], 4.0 * v[1]) for k, v in MEASURED.items()}
 

@@ -201,10 +201,10 @@ class SceneRef:
             self.lights.append(dict(kind="area", L=self.emit[i], shape=self.geo[i]))
 
     # ---- Scene::intersect / intersect_test (scene/mod.rs:51-57) over every primitive
-    def sphere_fragile(self, g, o, d, t_max):
+    def sphere_fragile(self, g, o, d, t_max, with_reach=False):
         """what the sphere's error intervals (sphere.rs:95-110, :126) may decide otherwise than binary64: a ray at the limb, a positive root within
         the origin's transformation error of 0 (the intervals are conservative: a root that is <= 0 stays so), a root just below t_max, a hit at a
-        clip of a partial sphere"""
+        clip of a partial sphere.  with_reach: -> (fragile, reach), reach = how far a root may move"""
         with np.errstate(all="ignore"):
             W = g.w2o
             oo, dd = R.tf_point(W, o), R.tf_vector(W, d)
@@ -222,12 +222,20 @@ class SceneRef:
                 if partial:
                     p, phi = g.at(oo, dd, t)
                     frag |= (axis < g.r) & (t > 0.0) & (t <= t_max) & g.near_a_clip(p, phi)
-        return frag
+            # the reference's quirk: next_float_down(0.0) is NaN (err_float.rs:22-30: -0.0 >= 0.0 holds), so a product that is exactly 0 -- an
+            # object-space direction or origin component that is 0 -- leaves NaN in the intervals of a, b or c, f32::min / max then drop it,
+            # and the tests of sphere.rs:99-110 go by what is left: hit or miss is not what binary64 says
+            o_mag = np.abs(o) @ np.abs(W[:3, :3]).T + np.abs(W[:3, 3])
+            o_err = gamma(3) * o_mag
+            shifted = oo + dd * (dot(np.abs(dd), o_err) / (ld * ld))[:, None]               # transform.rs:291-296
+            zero = (np.abs(dd) <= 4.0 * R.EPS * (np.abs(d) @ np.abs(W[:3, :3]).T) + 1.0e-18).any(axis=1) | (np.abs(shifted) <= 4.0 * R.EPS * o_mag + 1.0e-18).any(axis=1)
+            frag |= (axis < g.r) & zero
+        return (frag, reach) if with_reach else frag
 
-    def intersect(self, o, d):
-        """-> the nearest hit's interaction (FIELDS), `hit`, `prim` (the builder's index), `fragile`"""
+    def intersect(self, o, d, t_max=None):
+        """-> the nearest hit's interaction (FIELDS), `hit`, `prim` (the builder's index), `fragile`; t_max per ray, infinity by default"""
         m = len(o)
-        t_max = np.full(m, np.inf)
+        t_max = np.full(m, np.inf) if t_max is None else np.asarray(t_max, np.float64)
         parts, ts, raws, frs = [], [], [], []
         for g in self.geo:
             if g.kind == "tri":
@@ -263,10 +271,10 @@ class SceneRef:
         out.update(hit=hit, prim=np.where(hit, prim, -1), fragile=fragile)
         return out
 
-    def occluded(self, o, d):
-        """Scene::intersect_test of a shadow ray (t_max = 1 - 0.0001) -> occluded, fragile"""
+    def occluded(self, o, d, t_max=None):
+        """Scene::intersect_test -> occluded, fragile; t_max per ray, a shadow ray's (1 - 0.0001) by default"""
         m = len(o)
-        t_max = np.full(m, SHADOW_T_MAX)
+        t_max = np.full(m, SHADOW_T_MAX) if t_max is None else np.asarray(t_max, np.float64)
         occ, firm, doubt = np.zeros(m, bool), np.zeros(m, bool), np.zeros(m, bool)
         for g in self.geo:
             if g.kind == "tri":

@@ -282,10 +282,12 @@ class Triangle:
         p_err = gamma(6) * (np.abs(b0 * p0) + np.abs(b1 * p1) + np.abs(b2 * p2))
         return dict(p=p, p_err=p_err, n=np.array(sn), bary=np.concatenate([b0, b1, b2], axis=1), fragile=fragile)
 
-    def hit_test(self, o, d, t_max=np.inf):
-        """the hit test of :176-268 and the late `None` of :277-288 -> dict(miss, bary, t, fragile, nan_edges): fragile = binary32 may decide
-        otherwise; nan_edges = an edge function is NaN (sign_differs, :428-434, then goes by the NaN's sign bit, which IEEE 754 leaves to the
-        implementation: hit or miss is not defined by the reference's text)"""
+    def hit_test(self, o, d, t_max=np.inf, exact_origin=False):
+        """the hit test of :176-268 and the late `None` of :277-288 -> dict(miss, bary, t, delta_t, fragile, nan_edges): fragile = binary32 may
+        decide otherwise; delta_t = the reference's own bound on t's error (:252-268, in binary64); nan_edges = an edge function is NaN
+        (sign_differs, :428-434, then goes by the NaN's sign bit, which IEEE 754 leaves to the implementation: hit or miss is not defined by the
+        reference's text).  exact_origin: the origin is a binary32 number both sides use as it is (a ray batch), not a rounded sum (a spawned ray):
+        the origin's half ulp is then left out of `fragile`."""
         p0, p1, p2 = self.p
         with np.errstate(all="ignore"):
             pt = np.stack([p0 - o, p1 - o, p2 - o], axis=1)                           # [row][vertex][xyz]
@@ -325,16 +327,31 @@ class Triangle:
             # grazing an edge: an edge function within binary32's reach of 0 (each is a difference of two products of the sheared coordinates)
             # and the origin itself is a rounded sum: half an ulp of its largest coordinate in every translated vertex
             scale = max_x * max_y
-            ulp_o = 2.0 * EPS * np.abs(o).max(axis=1)
-            fragile = (np.abs(e).min(axis=1) <= 64 * EPS * scale + 4.0 * ulp_o * (max_x + max_y)) | (np.abs(t - delta_t) <= 1.0e-3 * np.abs(delta_t) + 64 * EPS * np.abs(t)) | ~np.isfinite(det)
+            if exact_origin:
+                # what binary32 still rounds: p - o, the shear's product and its sum, each to half an ulp of its own size -- which a ray aimed at
+                # a small triangle from far away cancels down to the triangle's size (|p - o| = 2^38 towards a triangle of 0.25: all three
+                # edge functions are 0 in binary32)
+                mag_x = (np.abs(pt[:, :, 0]) + np.abs(sx[:, None] * pt[:, :, 2])).max(axis=1)
+                mag_y = (np.abs(pt[:, :, 1]) + np.abs(sy[:, None] * pt[:, :, 2])).max(axis=1)
+                origin_term = 4.0 * EPS * (mag_x * max_y + mag_y * max_x)
+            else:
+                ulp_o = 2.0 * EPS * np.abs(o).max(axis=1)
+                origin_term = 4.0 * ulp_o * (max_x + max_y)
+            edge_reach = 64 * EPS * scale + origin_term
+            fragile = (np.abs(e).min(axis=1) <= edge_reach) | (np.abs(t - delta_t) <= 1.0e-3 * np.abs(delta_t) + 64 * EPS * np.abs(t)) | ~np.isfinite(det)
             fragile |= (np.abs(t_scaled) <= 64 * EPS * max_e * max_z) & ~(np.abs(t) < 0.5 * delta_t)     # (a t well inside delta_t is a miss whatever its sign)
             fragile |= np.isfinite(t_max) & (np.abs(t - t_max) <= 64 * EPS * (np.abs(t_max) + max_e * max_z * np.abs(inv)))      # t_scaled against t_max * det
+            if exact_origin:
+                # two edge functions of opposite sign, each beyond binary32's reach: sign_differs says so in binary32 as well, whatever the third
+                # one, t and det come to (a ray batch against every primitive of a scene: nearly every pair is such a miss, and the third edge
+                # function of a small triangle far off the ray is within reach of 0 more often than not)
+                fragile &= ~((e.max(axis=1) > edge_reach) & (e.min(axis=1) < -edge_reach))
             # the same edge functions in binary32, where 3e20 squared is already infinite and inf - inf is NaN
             f = np.float32
             x32 = pt[:, :, 0].astype(f) + (-dp[:, 0].astype(f) / dp[:, 2].astype(f))[:, None] * pt[:, :, 2].astype(f)
             y32 = pt[:, :, 1].astype(f) + (-dp[:, 1].astype(f) / dp[:, 2].astype(f))[:, None] * pt[:, :, 2].astype(f)
             e32 = np.stack([x32[:, 1] * y32[:, 2] - y32[:, 1] * x32[:, 2], x32[:, 2] * y32[:, 0] - y32[:, 2] * x32[:, 0], x32[:, 0] * y32[:, 1] - y32[:, 0] * x32[:, 1]], axis=1)
-        return dict(miss=miss, bary=bary, t=t, inv_det=inv, fragile=fragile, nan_edges=np.isnan(e).any(axis=1) | np.isnan(e32).any(axis=1))
+        return dict(miss=miss, bary=bary, t=t, delta_t=delta_t, inv_det=inv, fragile=fragile, nan_edges=np.isnan(e).any(axis=1) | np.isnan(e32).any(axis=1))
 
     def intersect(self, o, d):
         """:176-393 for a ray with t_max = infinity -> hit, p, n, fragile, whether an edge function is NaN"""
