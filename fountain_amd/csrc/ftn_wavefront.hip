@@ -6,7 +6,7 @@
  * paths live as float4 SoA records in HBM and every bounce runs kernels over queues of path / ray ids.  The units:
  *
  *   ftn_wavefront.hip     (this file) the two render drivers -- indexed sampler in passes, tile-serial sampler in rounds --, the driver
- *                         of the first-hit passes (wf_first_hit_passes: G-buffer, ID mattes) and the kernels around a pass:
+ *                         of the first-hit passes (wf_first_hit_passes: G-buffer, ID mattes, ambient occlusion) and the kernels around a pass:
  *                         k_wf_generate (get_camera_sample + generate_ray; all paths -> closest queue), k_wf_reset (counters between
  *                         kernels), k_wf_round_reset (between the rounds of a first-hit pass), k_wf_accumulate
  *                         (Film::add_sample_to_tile in sample order; under late finish it also finishes the ended paths,
@@ -20,7 +20,7 @@
  * Small wavefronts (<= 32 Mi paths) run the any-hit trace of a bounce on a second stream beside the closest-hit trace.
  *
  * Interfaces: ftn_wavefront.h is what the host library calls; ftn_wf_internal.h declares what the units above and the other
- * passes' units (ftn_gbuffer.hip, ftn_idmatte.hip) share on the host side; ftn_wf_common.h and ftn_wf_path.h hold the device-side pieces their kernels share.
+ * passes' units (ftn_gbuffer.hip, ftn_idmatte.hip, ftn_ao.hip) share on the host side; ftn_wf_common.h and ftn_wf_path.h hold the device-side pieces their kernels share.
  *
  * All per-path arithmetic and the order of the RNG draws are those of the reference (and of the megakernel), so both
  * pipelines produce identical radiance.  Dominant kernel: the closest-hit traversal; roofline = HBM (node + triangle fetches), in
@@ -527,7 +527,8 @@ int wavefront_render(WavefrontState** state, const RenderParams& P0, const std::
  * the same sampler, tiles and film.  k_wf_generate makes the camera rays from the sample keys, the production closest-hit kernels trace
  * them, and the pass's shade kernel records the first surface that has a material.  A null-material hit spawns the ray on along the same
  * direction (path.rs:77-80) into the other queue and the round repeats, at most WF_MAX_PASS_THROUGH times; the pass's accumulate kernel
- * then takes the samples of every pixel in sample order. */
+ * then takes the samples of every pixel in sample order.  A pass that traces rays from the surfaces it recorded (ambient occlusion) does
+ * so in between (WfFirstHitPass::secondary); the G-buffer and the mattes have no such stage and launch what they always did. */
 #define WF_MAX_PASS_THROUGH 4096u
 int wf_first_hit_passes(WavefrontState** state, const RenderParams& P, const std::vector<DTile>& tiles, const WfFirstHitPass& pass, hipStream_t stream, double* trace_ms_out) {
     knobs_begin();
@@ -581,6 +582,7 @@ int wf_first_hit_passes(WavefrontState** state, const RenderParams& P, const std
                 return FTN_ERR_INTERNAL;
             }
         }
+        if (pass.secondary && (rc = pass.secondary(st, W, lds, trace_grid_max, stream))) return rc;
         pass.accumulate(W, dim3((n_slots + 255) / 256), stream);
     }
     if (trace_ms_out) *trace_ms_out = trace_ms;

@@ -8,6 +8,7 @@
  *   ftn_wavefront.hip     generate / reset / accumulate / serial-advance, the two render drivers and the first-hit passes' driver
  *   ftn_gbuffer.hip       the G-buffer pass: its kernels, and what it hands wf_first_hit_passes
  *   ftn_idmatte.hip       the ID-matte pass, likewise, with its foreign list, resolve and matte extraction
+ *   ftn_ao.hip            the ambient-occlusion pass, likewise, with the any-hit steps between its first hits and its film sums
  *
  * The passes beside the beauty need nothing declared here: ftn_moments.hip hooks its kernel behind every pass of the public
  * wavefront_render (ftn_wavefront.h, ftn_wf_common.h), and ftn_adaptive.hip decides between rounds that are such calls.
@@ -125,10 +126,14 @@ struct WfFirstHitPass {
     std::function<void(const WfBuffers& W, const uint32_t* q_in, const uint32_t* count_in, uint32_t* q_out, uint32_t* count_out, dim3 grid, hipStream_t stream)> shade;
     /* one pass's accumulate kernel: one thread per pixel slot */
     std::function<void(const WfBuffers& W, dim3 grid, hipStream_t stream)> accumulate;
+    /* optional (empty for the G-buffer and the mattes, which launch nothing here): once per pass, between the last pass-through round and
+     * accumulate, what the pass traces from the surfaces it recorded (ambient occlusion: its any-hit rays).  It gets what launch_trace
+     * needs -- the state, the pass's buffers, the traversal's dynamic LDS and its largest grid -- and keeps its own times and counts */
+    std::function<int(WavefrontState* st, const WfBuffers& W, size_t lds, unsigned trace_grid_max, hipStream_t stream)> secondary;
 };
 /* Renders P's sample range of the tiles' camera samples through `pass`, in the beauty's passes (wf_plan_passes without direct lighting):
  * per pass k_wf_reset, k_wf_generate, then rounds of closest-hit trace and pass.shade until no ray passed through a null material
- * (k_wf_round_reset between them; more than 4096 rounds: FTN_ERR_INTERNAL), then pass.accumulate.  Without tiles or samples it returns
+ * (k_wf_round_reset between them; more than 4096 rounds: FTN_ERR_INTERNAL), then pass.secondary if there is one, then pass.accumulate.  Without tiles or samples it returns
  * FTN_OK before pass.setup.  *trace_ms_out: the trace launches' time.  The caller runs what follows the last pass. */
 int wf_first_hit_passes(WavefrontState** state, const RenderParams& P, const std::vector<DTile>& tiles, const WfFirstHitPass& pass, hipStream_t stream, double* trace_ms_out);
 

@@ -10,7 +10,10 @@ samples run in parallel (samplers).  --gbuffer also writes the fi
 (fountain_amd/gbuffer.py) beside the image: <name>_albedo.exr, <name>_normal.exr, <name>_position.exr and <name>_depth.exr (camera-space
 depth repeated in R, G and B); it needs the default sampler and one GPU.  --idmatte KIND[,KIND] (material, shape, primitive) also
 writes <name>_crypto.exr: the ID mattes of the same camera samples (fountain_amd/idmatte.py) as Cryptomatte layers CryptoMaterial,
-CryptoObject and CryptoPrimitive, one per kind; it has the same needs as --gbuffer.  --denoise then renders that G-buffer (also without
+CryptoObject and CryptoPrimitive, one per kind; it has the same needs as --gbuffer.  --ao [RAYS] (default 4, at most 64) also writes the
+ambient occlusion of the same camera samples (fountain_amd/ao.py), RAYS cosine-distributed occlusion rays per sample of at most
+--ao-radius R (default: unbounded): <name>_ao.exr (the open fraction in R, G and B, 1 where no surface was hit) and <name>_bent.exr (the
+bent normal); it has the same needs as --gbuffer.  --denoise then renders that G-buffer (also without
 --gbuffer) and writes <name>_denoised.exr: the image filtered by the edge-avoiding a-trous denoiser (fountain_amd/denoise.py, default
 parameters); the image itself is written unchanged.  It has the same needs as --gbuffer.  --variance renders the image together with
 the second moments of its camera samples (fountain_amd/moments.py), the same pixels bit for bit, and writes <name>_variance.exr: the
@@ -64,6 +67,9 @@ def main(argv=None):
     ap.add_argument("--gbuffer", action="store_true", help="also write the first-hit albedo / normal / position / depth buffers as <name>_<buffer>.exr")
     ap.add_argument("--idmatte", default=None, metavar="KIND[,KIND]",
                     help="also write <name>_crypto.exr: Cryptomatte layers of the image's camera samples, one per kind (material, shape, primitive)")
+    ap.add_argument("--ao", type=int, nargs="?", const=4, default=None, metavar="RAYS",
+                    help="also write <name>_ao.exr and <name>_bent.exr: ambient occlusion and bent normals of the image's camera samples, RAYS (default 4) rays each")
+    ap.add_argument("--ao-radius", type=float, default=None, metavar="R", help="with --ao: the length of the occlusion rays (default: unbounded)")
     ap.add_argument("--denoise", action="store_true", help="also write <name>_denoised.exr, the image denoised with the first-hit G-buffer of its camera samples")
     ap.add_argument("--variance", action="store_true", help="also write <name>_variance.exr, the estimated variance of each pixel's mean (r, g, b)")
     ap.add_argument("--denoise-guided", action="store_true",
@@ -111,6 +117,12 @@ def main(argv=None):
     if opts.filter_width is not None and (opts.pixel_filter is None or len(opts.filter_width) > 2):
         print("error: --filter-width X [Y] belongs to --pixel-filter", file=sys.stderr)
         return 2
+    if opts.ao_radius is not None and opts.ao is None:
+        print("error: --ao-radius belongs to --ao", file=sys.stderr)
+        return 2
+    if opts.ao is not None and (not 1 <= opts.ao <= A.FTN_AO_MAX_RAYS or (opts.ao_radius is not None and not opts.ao_radius > 0.0)):
+        print("error: --ao takes 1 to %d rays and --ao-radius a length above zero" % A.FTN_AO_MAX_RAYS, file=sys.stderr)
+        return 2
     if opts.idmatte is not None:
         from .idmatte import LAYERS
         opts.idmatte = opts.idmatte.split(",")
@@ -118,7 +130,7 @@ def main(argv=None):
             print("error: --idmatte takes a list of different kinds out of %s" % ", ".join(LAYERS), file=sys.stderr)
             return 2
     if opts.pixel_filter is not None:
-        for flag, on in (("--gbuffer", opts.gbuffer), ("--idmatte", opts.idmatte is not None), ("--denoise", opts.denoise), ("--denoise-guided", opts.denoise_guided), ("--variance", opts.variance),
+        for flag, on in (("--gbuffer", opts.gbuffer), ("--idmatte", opts.idmatte is not None), ("--ao", opts.ao is not None), ("--denoise", opts.denoise), ("--denoise-guided", opts.denoise_guided), ("--variance", opts.variance),
                          ("--adaptive", opts.adaptive is not None), ("--exact-stream", opts.exact_stream),
                          ("more than one GPU (--gpus)", opts.gpus is not None and opts.gpus > 1)):
             if on:
@@ -129,7 +141,7 @@ def main(argv=None):
         print("error: --min-samples belongs to --adaptive", file=sys.stderr)
         return 2
     if opts.adaptive is not None:
-        for flag, on in (("--exact-stream", opts.exact_stream), ("--gbuffer", opts.gbuffer), ("--idmatte", opts.idmatte is not None), ("--denoise", opts.denoise),
+        for flag, on in (("--exact-stream", opts.exact_stream), ("--gbuffer", opts.gbuffer), ("--idmatte", opts.idmatte is not None), ("--ao", opts.ao is not None), ("--denoise", opts.denoise),
                          ("--denoise-guided", opts.denoise_guided), ("more than one GPU (--gpus)", opts.gpus is not None and opts.gpus > 1)):
             if on:
                 print("error: --adaptive does not work with %s: it renders each tile at its own sample count on one GPU with the default sampler"
@@ -138,7 +150,7 @@ def main(argv=None):
         if not opts.adaptive >= 0.0 or opts.adaptive == float("inf"):
             print("error: --adaptive takes a finite threshold >= 0", file=sys.stderr)
             return 2
-    for flag, on in (("--gbuffer", opts.gbuffer), ("--idmatte", opts.idmatte is not None), ("--denoise", opts.denoise), ("--variance", opts.variance),
+    for flag, on in (("--gbuffer", opts.gbuffer), ("--idmatte", opts.idmatte is not None), ("--ao", opts.ao is not None), ("--denoise", opts.denoise), ("--variance", opts.variance),
                      ("--denoise-guided", opts.denoise_guided)):
         if on and opts.exact_stream:
             print("error: %s needs the default sampler: with --exact-stream a sample's camera ray depends on everything its tile drew before it" % flag, file=sys.stderr)
@@ -153,9 +165,9 @@ def main(argv=None):
         # started plainly: start the N ranks as a child process (before anything here has touched HIP) and hand back its exit code
         return spawn_ranks(opts.gpus, sys.argv[1:] if argv is None else list(argv), module="fountain_amd.render")
     world, rank = (env_world[0], env_world[1]) if env_world is not None else (1, 0)
-    if (opts.gbuffer or opts.idmatte is not None or opts.denoise or opts.variance or opts.denoise_guided or opts.adaptive is not None or opts.pixel_filter is not None
+    if (opts.gbuffer or opts.idmatte is not None or opts.ao is not None or opts.denoise or opts.variance or opts.denoise_guided or opts.adaptive is not None or opts.pixel_filter is not None
             or opts.png) and world > 1:
-        flag = "--png" if opts.png else "--gbuffer" if opts.gbuffer else "--idmatte" if opts.idmatte is not None else "--denoise" if opts.denoise else "--variance" if opts.variance else \
+        flag = "--png" if opts.png else "--gbuffer" if opts.gbuffer else "--idmatte" if opts.idmatte is not None else "--ao" if opts.ao is not None else "--denoise" if opts.denoise else "--variance" if opts.variance else \
             "--denoise-guided" if opts.denoise_guided else "--adaptive" if opts.adaptive is not None else "--pixel-filter"
         print("error: %s renders on one GPU, not under a launcher of %d ranks" % (flag, world), file=sys.stderr)
         return 2
@@ -282,6 +294,8 @@ def main(argv=None):
                 png.write(bloomed(out), denoised_guided_path(filename))
     if opts.idmatte is not None:
         write_idmatte(be, scene, parsed, film, sampler, filename, opts.gpu, opts.idmatte)
+    if opts.ao is not None:
+        write_ao(be, scene, parsed.camera, film, sampler, filename, opts.gpu, opts.ao, opts.ao_radius)
     if opts.adaptive is not None:
         import numpy as np
         path = spp_path(filename)
@@ -364,6 +378,26 @@ def write_idmatte(be, scene, parsed, film, sampler, filename, device, kinds):
     path = idmatte_path(filename)
     I.write_cryptomatte(path, layers, be)
     print("ID mattes: %s (%s; %.1f ms on the GPU)" % (path, ", ".join(layers), ms), file=sys.stderr)
+
+
+def ao_paths(filename):
+    """out.exr -> {"ao": out_ao.exr, "bent": out_bent.exr}"""
+    base = filename[:-4] if filename.endswith(".exr") else filename
+    return {k: "%s_%s.exr" % (base, k) for k in ("ao", "bent")}
+
+
+def write_ao(be, scene, camera, film, sampler, filename, device, rays, radius=None):
+    """The ambient occlusion of the beauty's camera samples (same film, sampler and tiles), written beside the image: the open fraction
+    in R, G and B (1 where no surface was hit) and the bent normal."""
+    import numpy as np
+    from .ao import INF, render_ao
+    res, _, st = render_ao(be, None, camera, None, sampler, rays=rays, radius=INF if radius is None else radius, scene=scene, film=film, device=device)
+    paths = ao_paths(filename)
+    write_exr(paths["ao"], np.repeat(res["ao"], 3, axis=-1), be)
+    write_exr(paths["bent"], res["bent"], be)
+    print("ambient occlusion: %s, %s (%d rays per sample, %.1f ms on the GPU, %.1f M occlusion rays/s)" % (
+        paths["ao"], paths["bent"], rays, st["kernel_ms"], st["rays_any"] / max(st["any_ms"], 1e-9) / 1e3), file=sys.stderr)
+    return res
 
 
 def write_denoised(be, img, gb12, filename, device):
