@@ -1,7 +1,8 @@
 /*
  * ftn_temporal.h -- temporal reprojection and accumulation (include/fountain_hip_temporal.h): the per-pixel code, shared by the kernel
  * (ftn_temporal.hip) and the host twin (ftn_temporal_host.cpp) so that both give the same bits, and the device driver's declaration.
- * Prepare, finish and the finiteness tests are ftn_denoise.h's.
+ * Prepare, finish and the finiteness tests are ftn_denoise.h's.  The same per-pixel code serves include/fountain_hip_motion.h: with a frame's
+ * mv8 (its resolved previous positions and normals) steps 2 and 3 follow what moved; tp_motion, step 2, is also the motion vectors'.
  *
  * Buffers, one entry per pixel: history, two float4 {u, n} and {nu_r, nu_g, nu_b, nu_Y} (an ftn_temporal_pixel), read through float4
  * pointers; everything else as the caller's float arrays.
@@ -52,9 +53,22 @@ FTN_HD V3 tp_project(const TpCamera& c, V3 v, bool point) {
 /* step 3's test of a tap's demodulation divisor against the pixel's: |a - b| <= tol max(a, b) */
 FTN_HD bool tp_same_divisor(float a, float b, float tol) { return fabsf(a - b) <= tol * (a > b ? a : b); }
 
-/* steps 1 to 5 for pixel (x, y); prev_gb12 and prev_hist are null on the first frame.  Writes the pixel's history, rgb and var4. */
+/* bit-equality of two floats (a NaN equals its copy, +0 differs from -0) */
+FTN_HD bool tp_same_bits(float a, float b) { return ftn_det::f2u(a) == ftn_det::f2u(b); }
+
+/* Step 2 for crop pixel (x, y) of a crop at (x0, y0): the two raster positions whose difference is the motion, rc in the current camera and
+ * rp (with the camera-space depth in z) in the previous one.  A covered pixel projects x_cur into the current camera and x_prev into the
+ * previous one as points -- the same point twice in a static scene, the previous-position pass's value (fountain_hip_motion.h) in a
+ * moving one; an uncovered pixel projects its direction into both. */
+FTN_HD void tp_motion(const TpCamera& cur, const TpCamera& prev, bool covered, V3 x_cur, V3 x_prev, int x, int y, int x0, int y0, V3* rc, V3* rp) {
+    if (!covered) x_cur = x_prev = m4_vector(cur.c2w, m4_point(cur.r2c, V3((float)(x + x0) + 0.5f, (float)(y + y0) + 0.5f, 0.0f)));
+    *rc = tp_project(cur, x_cur, covered); *rp = tp_project(prev, x_prev, covered);
+}
+
+/* steps 1 to 5 for pixel (x, y); prev_gb12 and prev_hist are null on the first frame.  Writes the pixel's history, rgb and var4.
+ * mv8 (null: a static scene): the current frame's resolved previous positions and normals, fountain_hip_motion.h's changes to steps 2 and 3. */
 FTN_HD void tp_accumulate_pixel(const float* rgb, const float* gb12, const float* var4, const float* prev_gb12, const float4* prev_hist,
-                                const TpFrame& F, int x, int y, float4* out_hist, float* out_rgb, float* out_var4) {
+                                const TpFrame& F, int x, int y, float4* out_hist, float* out_rgb, float* out_var4, const float* mv8 = nullptr) {
     const size_t p = (size_t)y * (size_t)F.w + (size_t)x;
     const float* gb = gb12 + 12 * p;
     const float* var = var4 + 4 * p;
@@ -79,11 +93,23 @@ FTN_HD void tp_accumulate_pixel(const float* rgb, const float* gb12, const float
 
     float W = 0.0f, sn = 0.0f;
     float su0 = 0.0f, su1 = 0.0f, su2 = 0.0f, sv0 = 0.0f, sv1 = 0.0f, sv2 = 0.0f, sv3 = 0.0f;
-    if (prev_hist) {
-        V3 v;
-        if (cov_p) v = V3(xp.x, xp.y, xp.z);
-        else v = m4_vector(F.cur.c2w, m4_point(F.cur.r2c, V3((float)(x + F.x0) + 0.5f, (float)(y + F.y0) + 0.5f, 0.0f)));
-        const V3 rc = tp_project(F.cur, v, cov_p), rp = tp_project(F.prev, v, cov_p);
+    /* the pixel's surface in the previous frame: where and how it stood (the pixel's own x_p, n_p without mv8), whether it stood still, and
+     * whether mv8 speaks of the same coverage class as gb12 */
+    V3 xq(xp.x, xp.y, xp.z), nq(np.x, np.y, np.z);
+    bool still = true, same_class = true;
+    if (mv8) {
+        const float* mv = mv8 + 8 * p;
+        same_class = (mv[6] > 0.0f) == cov_p;
+        if (cov_p) {
+            xq = V3(mv[0], mv[1], mv[2]); nq = V3(mv[3], mv[4], mv[5]);
+            still = tp_same_bits(xq.x, xp.x) && tp_same_bits(xq.y, xp.y) && tp_same_bits(xq.z, xp.z) &&
+                    tp_same_bits(nq.x, np.x) && tp_same_bits(nq.y, np.y) && tp_same_bits(nq.z, np.z);
+        }
+    }
+    const bool untested = F.same_view && still;          /* equal cameras and a surface that did not move: the pixel is its own only tap */
+    if (prev_hist && same_class) {
+        V3 rc, rp;
+        tp_motion(F.cur, F.prev, cov_p, V3(xp.x, xp.y, xp.z), xq, x, y, F.x0, F.y0, &rc, &rp);
         const float sx = (float)x + (rp.x - rc.x), sy = (float)y + (rp.y - rc.y);
         /* NaN fails every comparison; inside the bounds the conversions to int are exact */
         if (rp.z > 0.0f && sx > -1.0f && sx < (float)F.w && sy > -1.0f && sy < (float)F.h) {
@@ -111,10 +137,10 @@ FTN_HD void tp_accumulate_pixel(const float* rgb, const float* gb12, const float
                         if (!tp_same_divisor(db, qb, F.albedo_tol)) { hu.z = (hu.z * qb) / db; hv.z = (hv.z * (qb * qb)) / d2b; }
                     }
                     if (!dn_finite3(hu) || hv.x != hv.x || hv.y != hv.y || hv.z != hv.z || hv.w != hv.w) continue;
-                    if (cov_p && !F.same_view) {
-                        const float e0 = np.x - gq[3], e1 = np.y - gq[4], e2 = np.z - gq[5];
+                    if (cov_p && !untested) {
+                        const float e0 = nq.x - gq[3], e1 = nq.y - gq[4], e2 = nq.z - gq[5];
                         if (!((e0 * e0 + e1 * e1) + e2 * e2 <= F.normal_tol)) continue;
-                        const float pd = (np.x * (xp.x - gq[6]) + np.y * (xp.y - gq[7])) + np.z * (xp.z - gq[8]);
+                        const float pd = (nq.x * (xq.x - gq[6]) + nq.y * (xq.y - gq[7])) + nq.z * (xq.z - gq[8]);
                         if (!(fabsf(pd) <= plane_max)) continue;
                     }
                     W = W + b;
@@ -148,9 +174,25 @@ FTN_HD void tp_accumulate_pixel(const float* rgb, const float* gb12, const float
     out_var4[4 * p + 3] = nu.w;
 }
 
-/* the device path of ftn_temporal_accumulate_device (arguments already checked): one launch.  Returns the launch error, if any. */
+/* the device path of ftn_temporal_accumulate_device (arguments already checked): one launch.  Returns the launch error, if any.
+ * mv8: the current frame's resolved previous positions (fountain_hip_motion.h), or null */
 hipError_t launch_temporal(const float* rgb, const float* gb12, const float* var4, const float* prev_gb12, const float4* prev_hist,
-                           const TpFrame& frame, float4* out_hist, float* out_rgb, float* out_var4, hipStream_t stream);
+                           const TpFrame& frame, float4* out_hist, float* out_rgb, float* out_var4, hipStream_t stream, const float* mv8 = nullptr);
+
+#pragma GCC visibility push(hidden)
+/* The bodies of ftn_temporal_accumulate_device, ftn_temporal_accumulate and ftn_temporal_accumulate_cpu (ftn_temporal_host.cpp), which those
+ * entry points call with mv8 = null and fountain_hip_motion.h's ftn_temporal_accumulate_motion* with the caller's: refusals, buffers and
+ * the per-pixel code are one. */
+int tp_accumulate_device(const void* rgb, const void* gb12, const void* var4, const void* mv8, const ftn_camera_desc* cur_camera, const ftn_film_desc* film,
+                         int32_t w, int32_t h, const ftn_camera_desc* prev_camera, const void* prev_gb12, const void* prev_history,
+                         const ftn_temporal_params* params, void* out_history, void* out_rgb, void* out_var4, void* stream);
+int tp_accumulate_host(const float* rgb, const float* gb12, const float* var4, const float* mv8, const ftn_camera_desc* cur_camera, const ftn_film_desc* film,
+                       int32_t w, int32_t h, const ftn_camera_desc* prev_camera, const float* prev_gb12, const ftn_temporal_pixel* prev_history,
+                       const ftn_temporal_params* params, ftn_temporal_pixel* out_history, float* out_rgb, float* out_var4, int32_t device);
+int tp_accumulate_cpu(const float* rgb, const float* gb12, const float* var4, const float* mv8, const ftn_camera_desc* cur_camera, const ftn_film_desc* film,
+                      int32_t w, int32_t h, const ftn_camera_desc* prev_camera, const float* prev_gb12, const ftn_temporal_pixel* prev_history,
+                      const ftn_temporal_params* params, ftn_temporal_pixel* out_history, float* out_rgb, float* out_var4);
+#pragma GCC visibility pop
 
 }  // namespace ftn
 #endif

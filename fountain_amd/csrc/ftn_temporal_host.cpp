@@ -59,41 +59,65 @@ void ftn_temporal_params_default(ftn_temporal_params* p) {
 int ftn_temporal_accumulate_device(const void* rgb, const void* gb12, const void* var4, const ftn_camera_desc* cur_camera, const ftn_film_desc* film,
                                    int32_t w, int32_t h, const ftn_camera_desc* prev_camera, const void* prev_gb12, const void* prev_history,
                                    const ftn_temporal_params* p, void* out_history, void* out_rgb, void* out_var4, void* stream) {
-    if (!rgb || !gb12 || !var4 || !out_history || !out_rgb || !out_var4) return fail(FTN_ERR_INVALID_ARGUMENT, "null argument");
-    TpFrame F;
-    int rc = temporal_check(cur_camera, film, w, h, prev_camera, prev_gb12, prev_history, p, &F); if (rc) return rc;
-    const size_t n = (size_t)w * (size_t)h;
-    const Range r_rgb = {rgb, 12 * n, 4}, r_gb = {gb12, 48 * n, 4}, r_var = {var4, 16 * n, 4}, r_pgb = {prev_gb12, 48 * n, 4}, r_ph = {prev_history, 32 * n, 16},
-                r_oh = {out_history, 32 * n, 16}, r_out = {out_rgb, 12 * n, 4}, r_ovar = {out_var4, 16 * n, 4};
-    if ((rc = overlap_check({r_oh, r_out, r_ovar}, {r_rgb, r_gb, r_var, r_pgb, r_ph}, "an output overlaps an input", "two outputs overlap"))) return rc;
-    if ((rc = align_check({r_oh, r_ph, r_rgb, r_gb, r_var, r_pgb, r_out, r_ovar}, "misaligned buffer: the histories need 16 bytes, the images 4"))) return rc;
-    if ((rc = need_device())) return rc;
-    return launched(launch_temporal((const float*)rgb, (const float*)gb12, (const float*)var4, (const float*)prev_gb12, (const float4*)prev_history, F,
-                                    (float4*)out_history, (float*)out_rgb, (float*)out_var4, (hipStream_t)stream), "temporal accumulation");
+    return tp_accumulate_device(rgb, gb12, var4, nullptr, cur_camera, film, w, h, prev_camera, prev_gb12, prev_history, p, out_history, out_rgb, out_var4, stream);
 }
 
 int ftn_temporal_accumulate(const float* rgb, const float* gb12, const float* var4, const ftn_camera_desc* cur_camera, const ftn_film_desc* film,
                             int32_t w, int32_t h, const ftn_camera_desc* prev_camera, const float* prev_gb12, const ftn_temporal_pixel* prev_history,
                             const ftn_temporal_params* p, ftn_temporal_pixel* out_history, float* out_rgb, float* out_var4, int32_t device) {
+    return tp_accumulate_host(rgb, gb12, var4, nullptr, cur_camera, film, w, h, prev_camera, prev_gb12, prev_history, p, out_history, out_rgb, out_var4, device);
+}
+
+int ftn_temporal_accumulate_cpu(const float* rgb, const float* gb12, const float* var4, const ftn_camera_desc* cur_camera, const ftn_film_desc* film,
+                                int32_t w, int32_t h, const ftn_camera_desc* prev_camera, const float* prev_gb12, const ftn_temporal_pixel* prev_history,
+                                const ftn_temporal_params* p, ftn_temporal_pixel* out_history, float* out_rgb, float* out_var4) {
+    return tp_accumulate_cpu(rgb, gb12, var4, nullptr, cur_camera, film, w, h, prev_camera, prev_gb12, prev_history, p, out_history, out_rgb, out_var4);
+}
+
+}  /* extern "C" */
+
+/* ------------------------------------------------------------------ the entry points' bodies (ftn_temporal.h); mv8 may be null */
+namespace ftn {
+
+int tp_accumulate_device(const void* rgb, const void* gb12, const void* var4, const void* mv8, const ftn_camera_desc* cur_camera, const ftn_film_desc* film,
+                         int32_t w, int32_t h, const ftn_camera_desc* prev_camera, const void* prev_gb12, const void* prev_history,
+                         const ftn_temporal_params* p, void* out_history, void* out_rgb, void* out_var4, void* stream) {
+    if (!rgb || !gb12 || !var4 || !out_history || !out_rgb || !out_var4) return fail(FTN_ERR_INVALID_ARGUMENT, "null argument");
+    TpFrame F;
+    int rc = temporal_check(cur_camera, film, w, h, prev_camera, prev_gb12, prev_history, p, &F); if (rc) return rc;
+    const size_t n = (size_t)w * (size_t)h;
+    const Range r_rgb = {rgb, 12 * n, 4}, r_gb = {gb12, 48 * n, 4}, r_var = {var4, 16 * n, 4}, r_pgb = {prev_gb12, 48 * n, 4}, r_ph = {prev_history, 32 * n, 16},
+                r_mv = {mv8, 32 * n, 4}, r_oh = {out_history, 32 * n, 16}, r_out = {out_rgb, 12 * n, 4}, r_ovar = {out_var4, 16 * n, 4};
+    if ((rc = overlap_check({r_oh, r_out, r_ovar}, {r_rgb, r_gb, r_var, r_pgb, r_ph, r_mv}, "an output overlaps an input", "two outputs overlap"))) return rc;
+    if ((rc = align_check({r_oh, r_ph, r_rgb, r_gb, r_var, r_pgb, r_out, r_ovar, r_mv}, "misaligned buffer: the histories need 16 bytes, the images 4"))) return rc;
+    if ((rc = need_device())) return rc;
+    return launched(launch_temporal((const float*)rgb, (const float*)gb12, (const float*)var4, (const float*)prev_gb12, (const float4*)prev_history, F,
+                                    (float4*)out_history, (float*)out_rgb, (float*)out_var4, (hipStream_t)stream, (const float*)mv8), "temporal accumulation");
+}
+
+int tp_accumulate_host(const float* rgb, const float* gb12, const float* var4, const float* mv8, const ftn_camera_desc* cur_camera, const ftn_film_desc* film,
+                       int32_t w, int32_t h, const ftn_camera_desc* prev_camera, const float* prev_gb12, const ftn_temporal_pixel* prev_history,
+                       const ftn_temporal_params* p, ftn_temporal_pixel* out_history, float* out_rgb, float* out_var4, int32_t device) {
     if (!rgb || !gb12 || !var4 || !out_history || !out_rgb || !out_var4) return fail(FTN_ERR_INVALID_ARGUMENT, "null argument");
     TpFrame F;
     int rc = temporal_check(cur_camera, film, w, h, prev_camera, prev_gb12, prev_history, p, &F); if (rc) return rc;
     if ((rc = need_device()) || (rc = set_device(device))) return rc;
     const size_t n = (size_t)w * (size_t)h;
     StageBufs bufs;
-    float *d_rgb, *d_gb, *d_var, *d_pgb, *d_out, *d_ovar;
+    float *d_rgb, *d_gb, *d_var, *d_pgb, *d_out, *d_ovar, *d_mv;
     ftn_temporal_pixel *d_ph, *d_oh;
     if ((rc = bufs.upload(rgb, 3 * n, &d_rgb)) || (rc = bufs.upload(gb12, 12 * n, &d_gb)) || (rc = bufs.upload(var4, 4 * n, &d_var)) ||
         (rc = bufs.upload(prev_gb12, 12 * n, &d_pgb)) || (rc = bufs.upload(prev_history, n, &d_ph)) ||      /* (null on the first frame) */
+        (rc = bufs.upload(mv8, 8 * n, &d_mv)) ||                                                            /* (null for a static scene) */
         (rc = bufs.alloc(n, &d_oh)) || (rc = bufs.alloc(3 * n, &d_out)) || (rc = bufs.alloc(4 * n, &d_ovar))) return rc;
-    if ((rc = ftn_temporal_accumulate_device(d_rgb, d_gb, d_var, cur_camera, film, w, h, prev_camera, d_pgb, d_ph, p, d_oh, d_out, d_ovar, nullptr))) return rc;
+    if ((rc = tp_accumulate_device(d_rgb, d_gb, d_var, d_mv, cur_camera, film, w, h, prev_camera, d_pgb, d_ph, p, d_oh, d_out, d_ovar, nullptr))) return rc;
     if ((rc = bufs.copy_back(out_history, d_oh, n)) || (rc = bufs.copy_back(out_rgb, d_out, 3 * n))) return rc;
     return bufs.copy_back(out_var4, d_ovar, 4 * n);
 }
 
-int ftn_temporal_accumulate_cpu(const float* rgb, const float* gb12, const float* var4, const ftn_camera_desc* cur_camera, const ftn_film_desc* film,
-                                int32_t w, int32_t h, const ftn_camera_desc* prev_camera, const float* prev_gb12, const ftn_temporal_pixel* prev_history,
-                                const ftn_temporal_params* p, ftn_temporal_pixel* out_history, float* out_rgb, float* out_var4) {
+int tp_accumulate_cpu(const float* rgb, const float* gb12, const float* var4, const float* mv8, const ftn_camera_desc* cur_camera, const ftn_film_desc* film,
+                      int32_t w, int32_t h, const ftn_camera_desc* prev_camera, const float* prev_gb12, const ftn_temporal_pixel* prev_history,
+                      const ftn_temporal_params* p, ftn_temporal_pixel* out_history, float* out_rgb, float* out_var4) {
     if (!rgb || !gb12 || !var4 || !out_history || !out_rgb || !out_var4) return fail(FTN_ERR_INVALID_ARGUMENT, "null argument");
     TpFrame F;
     int rc = temporal_check(cur_camera, film, w, h, prev_camera, prev_gb12, prev_history, p, &F); if (rc) return rc;
@@ -110,7 +134,7 @@ int ftn_temporal_accumulate_cpu(const float* rgb, const float* gb12, const float
     parallel_for(n, [&](size_t i0, size_t i1) {
         for (size_t i = i0; i < i1; i++)
             tp_accumulate_pixel(rgb, gb12, var4, prev_gb12, prev, F, (int)(i % (size_t)w), (int)(i / (size_t)w), hist.data(),
-                                out.data(), ovar.data());
+                                out.data(), ovar.data(), mv8);
     });
     memcpy(out_history, hist.data(), n * sizeof(ftn_temporal_pixel));
     memcpy(out_rgb, out.data(), 3 * n * sizeof(float));
@@ -118,4 +142,4 @@ int ftn_temporal_accumulate_cpu(const float* rgb, const float* gb12, const float
     return FTN_OK;
 }
 
-}  /* extern "C" */
+}  // namespace ftn
