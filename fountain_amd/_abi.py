@@ -179,6 +179,15 @@ FTN_AO_ABI_VERSION = 1       # include/fountain_hip_ao.h (an extension with a ve
 FTN_AO_MAX_RAYS = 64
 
 
+class ftn_lightpass_pixel(C.Structure):
+    """include/fountain_hip_lightpass.h: per-pixel sums of the light-group pass (w = box filter weight)."""
+    _fields_ = [("lit", c_f * 3), ("unshadowed", c_f * 3), ("hit_weight", c_f), ("weight", c_f)]
+
+
+FTN_LIGHTPASS_ABI_VERSION = 1       # include/fountain_hip_lightpass.h (an extension with a version of its own; FTN_ABI_VERSION is unchanged)
+FTN_LIGHTPASS_MAX_GROUPS = 16
+
+
 class ftn_motion_pixel(C.Structure):
     """include/fountain_hip_motion.h: per-pixel sums of the previous-position pass (w = box filter weight)."""
     _fields_ = [("prev_position", c_f * 3), ("prev_normal", c_f * 3), ("hit_weight", c_f), ("weight", c_f)]
@@ -333,7 +342,7 @@ SIZES = {
     "ftn_sphere": 288, "ftn_material": 48, "ftn_light": 160, "ftn_envmap": 16, "ftn_camera_desc": 296,
     "ftn_film_desc": 32, "ftn_sampler_desc": 24, "ftn_integrator_desc": 16, "ftn_tile_range": 16,
     "ftn_render_options": 16, "ftn_stats": 152, "ftn_scene_memory": 96, "ftn_texture": 48, "ftn_image": 24, "ftn_material_textures": 32,
-    "ftn_gbuffer_pixel": 48, "ftn_idmatte_pixel": 80, "ftn_ao_options": 16, "ftn_ao_pixel": 32, "ftn_motion_pixel": 32, "ftn_denoise_params": 32, "ftn_denoise_guided_params": 32, "ftn_moment_pixel": 16, "ftn_adaptive_params": 16, "ftn_adaptive_info": 24,
+    "ftn_gbuffer_pixel": 48, "ftn_idmatte_pixel": 80, "ftn_ao_options": 16, "ftn_ao_pixel": 32, "ftn_lightpass_pixel": 32, "ftn_motion_pixel": 32, "ftn_denoise_params": 32, "ftn_denoise_guided_params": 32, "ftn_moment_pixel": 16, "ftn_adaptive_params": 16, "ftn_adaptive_info": 24,
     "ftn_temporal_pixel": 32, "ftn_temporal_params": 32, "ftn_filter_desc": 32, "ftn_display_params": 48, "ftn_display_info": 32,
     "ftn_bloom_params": 32, "ftn_subdiv_info": 184,
     "ftn_metrics_params": 16, "ftn_metrics_totals": 112, "ftn_metrics_result": 136,
@@ -506,6 +515,20 @@ AO_PROTOTYPES = {
     "ftn_ao_abi_version": ([], C.c_int),
 }
 AO_FUNCTIONS = sorted(AO_PROTOTYPES)
+
+# Every function the extension header include/fountain_hip_lightpass.h declares (kept apart from the lists above: the reference has no
+# light AOVs, so these have no orc_* twin either), with its prototype: name -> (argument types, result type).
+LIGHTPASS_PROTOTYPES = {
+    "ftn_render_lightpass": ([C.c_void_p] * 7 + [c_u32] + [C.c_void_p] * 2, C.c_int),
+    "ftn_render_lightpass_device": ([C.c_void_p] * 7 + [c_u32] + [C.c_void_p] * 3, C.c_int),
+    "ftn_lightpass_resolve": ([C.c_void_p, C.c_size_t, C.c_void_p], C.c_int),
+    "ftn_lightpass_resolve_device": ([C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p], C.c_int),
+    "ftn_lightpass_compose": ([C.c_void_p, C.c_void_p, c_u32, C.c_void_p, C.c_size_t, C.c_void_p], C.c_int),
+    "ftn_lightpass_compose_device": ([C.c_void_p, C.c_void_p, c_u32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p], C.c_int),
+    "ftn_lightpass_terms": ([C.c_void_p, C.c_void_p, C.c_size_t, c_u32, C.c_void_p, C.c_void_p], C.c_int),
+    "ftn_lightpass_abi_version": ([], C.c_int),
+}
+LIGHTPASS_FUNCTIONS = sorted(LIGHTPASS_PROTOTYPES)
 
 # Every function the extension header include/fountain_hip_motion.h declares (kept apart from the lists above: the reference renders
 # single frames, so these have no orc_* twin either), with its prototype: name -> (argument types, result type).

@@ -1,5 +1,5 @@
-"""Helpers shared by the bindings of the calls the CPU oracle has no twin of: the render passes (gbuffer.py, moments.py, adaptive.py) and
-the image-space stages (denoise.py, temporal.py, display.py, bloom.py, metrics.py)."""
+"""Helpers shared by the bindings of the calls the CPU oracle has no twin of: the render passes (gbuffer.py, moments.py, adaptive.py,
+lightpass.py) and the image-space stages (denoise.py, temporal.py, display.py, bloom.py, metrics.py, lightpass.py's compose)."""
 import ctypes as C
 
 import numpy as np
@@ -27,6 +27,15 @@ def call_args(cam, film, integrator, sampler, tiles, pipeline, device, count_tra
     opt.pipeline, opt.device, opt.count_traffic = pipeline, device, int(count_traffic)
     args = [C.byref(cam.desc), C.byref(film.desc), C.byref(sampler.desc)] + ([C.byref(integrator.desc)] if integrator is not None else [])
     return args + [C.byref(tr), C.byref(opt)], (tr, opt)
+
+
+def index_list(indices):
+    """An optional list of indices as the (uint32 array pointer or None, length) pair of a C call, and the array to keep alive: None
+    stays None with length 0 (lightpass.py: all lights)."""
+    if indices is None:
+        return None, 0, None
+    a = np.ascontiguousarray(indices, dtype=np.uint32).reshape(-1)
+    return a.ctypes.data_as(C.c_void_p), len(a), a
 
 
 def check_tensor(t, shape):

@@ -13,7 +13,12 @@ writes <name>_crypto.exr: the ID mattes of the same camera samples (fountain_amd
 CryptoObject and CryptoPrimitive, one per kind; it has the same needs as --gbuffer.  --ao [RAYS] (default 4, at most 64) also writes the
 ambient occlusion of the same camera samples (fountain_amd/ao.py), RAYS cosine-distributed occlusion rays per sample of at most
 --ao-radius R (default: unbounded): <name>_ao.exr (the open fraction in R, G and B, 1 where no surface was hit) and <name>_bent.exr (the
-bent normal); it has the same needs as --gbuffer.  --denoise then renders that G-buffer (also without
+bent normal); it has the same needs as --gbuffer.  --light-groups [kind|each] (default kind) also writes the light-group AOVs of the same
+camera samples (fountain_amd/lightpass.py), one light sample and one shadow ray per sample and group: <name>_light_<group>.exr (the
+direct irradiance the group's lights leave on the first surface, shadows included) and <name>_lightvis_<group>.exr (the fraction of that
+light the scene lets through, in R, G and B); `kind` makes one group per kind of light the scene has (point, distant, infinite, area),
+`each` one per explicit light (light<i>) and one for the area lights.  `python -m fountain_amd.lightpass relight` sums such files over the
+albedo with a gain per group.  It has the same needs as --gbuffer.  --denoise then renders that G-buffer (also without
 --gbuffer) and writes <name>_denoised.exr: the image filtered by the edge-avoiding a-trous denoiser (fountain_amd/denoise.py, default
 parameters); the image itself is written unchanged.  It has the same needs as --gbuffer.  --variance renders the image together with
 the second moments of its camera samples (fountain_amd/moments.py), the same pixels bit for bit, and writes <name>_variance.exr: the
@@ -70,6 +75,8 @@ def main(argv=None):
     ap.add_argument("--ao", type=int, nargs="?", const=4, default=None, metavar="RAYS",
                     help="also write <name>_ao.exr and <name>_bent.exr: ambient occlusion and bent normals of the image's camera samples, RAYS (default 4) rays each")
     ap.add_argument("--ao-radius", type=float, default=None, metavar="R", help="with --ao: the length of the occlusion rays (default: unbounded)")
+    ap.add_argument("--light-groups", nargs="?", const="kind", default=None, choices=["kind", "each"], metavar="kind|each",
+                    help="also write <name>_light_<group>.exr and <name>_lightvis_<group>.exr per group of lights: direct irradiance and visibility of the image's camera samples")
     ap.add_argument("--denoise", action="store_true", help="also write <name>_denoised.exr, the image denoised with the first-hit G-buffer of its camera samples")
     ap.add_argument("--variance", action="store_true", help="also write <name>_variance.exr, the estimated variance of each pixel's mean (r, g, b)")
     ap.add_argument("--denoise-guided", action="store_true",
@@ -130,7 +137,7 @@ def main(argv=None):
             print("error: --idmatte takes a list of different kinds out of %s" % ", ".join(LAYERS), file=sys.stderr)
             return 2
     if opts.pixel_filter is not None:
-        for flag, on in (("--gbuffer", opts.gbuffer), ("--idmatte", opts.idmatte is not None), ("--ao", opts.ao is not None), ("--denoise", opts.denoise), ("--denoise-guided", opts.denoise_guided), ("--variance", opts.variance),
+        for flag, on in (("--gbuffer", opts.gbuffer), ("--idmatte", opts.idmatte is not None), ("--ao", opts.ao is not None), ("--light-groups", opts.light_groups is not None), ("--denoise", opts.denoise), ("--denoise-guided", opts.denoise_guided), ("--variance", opts.variance),
                          ("--adaptive", opts.adaptive is not None), ("--exact-stream", opts.exact_stream),
                          ("more than one GPU (--gpus)", opts.gpus is not None and opts.gpus > 1)):
             if on:
@@ -141,7 +148,7 @@ def main(argv=None):
         print("error: --min-samples belongs to --adaptive", file=sys.stderr)
         return 2
     if opts.adaptive is not None:
-        for flag, on in (("--exact-stream", opts.exact_stream), ("--gbuffer", opts.gbuffer), ("--idmatte", opts.idmatte is not None), ("--ao", opts.ao is not None), ("--denoise", opts.denoise),
+        for flag, on in (("--exact-stream", opts.exact_stream), ("--gbuffer", opts.gbuffer), ("--idmatte", opts.idmatte is not None), ("--ao", opts.ao is not None), ("--light-groups", opts.light_groups is not None), ("--denoise", opts.denoise),
                          ("--denoise-guided", opts.denoise_guided), ("more than one GPU (--gpus)", opts.gpus is not None and opts.gpus > 1)):
             if on:
                 print("error: --adaptive does not work with %s: it renders each tile at its own sample count on one GPU with the default sampler"
@@ -150,7 +157,7 @@ def main(argv=None):
         if not opts.adaptive >= 0.0 or opts.adaptive == float("inf"):
             print("error: --adaptive takes a finite threshold >= 0", file=sys.stderr)
             return 2
-    for flag, on in (("--gbuffer", opts.gbuffer), ("--idmatte", opts.idmatte is not None), ("--ao", opts.ao is not None), ("--denoise", opts.denoise), ("--variance", opts.variance),
+    for flag, on in (("--gbuffer", opts.gbuffer), ("--idmatte", opts.idmatte is not None), ("--ao", opts.ao is not None), ("--light-groups", opts.light_groups is not None), ("--denoise", opts.denoise), ("--variance", opts.variance),
                      ("--denoise-guided", opts.denoise_guided)):
         if on and opts.exact_stream:
             print("error: %s needs the default sampler: with --exact-stream a sample's camera ray depends on everything its tile drew before it" % flag, file=sys.stderr)
@@ -165,9 +172,9 @@ def main(argv=None):
         # started plainly: start the N ranks as a child process (before anything here has touched HIP) and hand back its exit code
         return spawn_ranks(opts.gpus, sys.argv[1:] if argv is None else list(argv), module="fountain_amd.render")
     world, rank = (env_world[0], env_world[1]) if env_world is not None else (1, 0)
-    if (opts.gbuffer or opts.idmatte is not None or opts.ao is not None or opts.denoise or opts.variance or opts.denoise_guided or opts.adaptive is not None or opts.pixel_filter is not None
+    if (opts.gbuffer or opts.idmatte is not None or opts.ao is not None or opts.light_groups is not None or opts.denoise or opts.variance or opts.denoise_guided or opts.adaptive is not None or opts.pixel_filter is not None
             or opts.png) and world > 1:
-        flag = "--png" if opts.png else "--gbuffer" if opts.gbuffer else "--idmatte" if opts.idmatte is not None else "--ao" if opts.ao is not None else "--denoise" if opts.denoise else "--variance" if opts.variance else \
+        flag = "--png" if opts.png else "--gbuffer" if opts.gbuffer else "--idmatte" if opts.idmatte is not None else "--ao" if opts.ao is not None else "--light-groups" if opts.light_groups is not None else "--denoise" if opts.denoise else "--variance" if opts.variance else \
             "--denoise-guided" if opts.denoise_guided else "--adaptive" if opts.adaptive is not None else "--pixel-filter"
         print("error: %s renders on one GPU, not under a launcher of %d ranks" % (flag, world), file=sys.stderr)
         return 2
@@ -296,6 +303,8 @@ def main(argv=None):
         write_idmatte(be, scene, parsed, film, sampler, filename, opts.gpu, opts.idmatte)
     if opts.ao is not None:
         write_ao(be, scene, parsed.camera, film, sampler, filename, opts.gpu, opts.ao, opts.ao_radius)
+    if opts.light_groups is not None:
+        write_lightpass(be, scene, parsed.camera, film, sampler, filename, opts.gpu, opts.light_groups)
     if opts.adaptive is not None:
         import numpy as np
         path = spp_path(filename)
@@ -378,6 +387,31 @@ def write_idmatte(be, scene, parsed, film, sampler, filename, device, kinds):
     path = idmatte_path(filename)
     I.write_cryptomatte(path, layers, be)
     print("ID mattes: %s (%s; %.1f ms on the GPU)" % (path, ", ".join(layers), ms), file=sys.stderr)
+
+
+def lightpass_paths(filename, group):
+    """out.exr, key -> {"light": out_light_key.exr, "lightvis": out_lightvis_key.exr}"""
+    base = filename[:filename.rindex(".exr")]
+    return {k: "%s_%s_%s.exr" % (base, k, group) for k in ("light", "lightvis")}
+
+
+def write_lightpass(be, scene, camera, film, sampler, filename, device, by):
+    """Renders the light-group AOVs of the film's camera samples, one call per group (lightpass.groups), and writes each group's resolved
+    lit irradiance and its visibility (repeated in R, G and B).  Returns {group: resolved dict}."""
+    import numpy as np
+    from .lightpass import groups, render_lightpass
+    out = {}
+    for name, lights in groups(scene, by).items():
+        res, _, st = render_lightpass(be, None, camera, None, sampler, lights=lights, scene=scene, film=film, device=device)
+        paths = lightpass_paths(filename, name)
+        write_exr(paths["light"], res["lit"], be)
+        write_exr(paths["lightvis"], np.repeat(res["visibility"], 3, axis=-1), be)
+        print("light group %s (%d lights): %s, %s (%.1f ms, %d shadow rays)" % (name, len(lights), paths["light"], paths["lightvis"], st["kernel_ms"], st["rays_any"]),
+              file=sys.stderr)
+        out[name] = res
+    if not out:
+        print("light groups: the scene has no lights, nothing written", file=sys.stderr)
+    return out
 
 
 def ao_paths(filename):
