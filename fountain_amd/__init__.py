@@ -6,7 +6,7 @@ from .api import (Backend, DirectLightingIntegrator, Film, FountainError, PathIn
 from .filters import Filter, render_filtered
 from .subdiv import loop_subdivide, loop_subdivide_cpu
 
-__all__ = ["Backend", "DirectLightingIntegrator", "Film", "Filter", "render_filtered", "DisplayParams", "write_png", "BloomParams", "MetricsParams", "compare", "compare_cpu", "compare_device", "loop_subdivide", "loop_subdivide_cpu", "FountainError", "PathIntegrator", "PbrtScene", "PerspectiveCamera",
+__all__ = ["Backend", "DirectLightingIntegrator", "Film", "Filter", "render_filtered", "DisplayParams", "write_png", "BloomParams", "VectorBlurParams", "MetricsParams", "compare", "compare_cpu", "compare_device", "loop_subdivide", "loop_subdivide_cpu", "FountainError", "PathIntegrator", "PbrtScene", "PerspectiveCamera",
            "RandomSampler", "SamplerIntegrator", "Scene", "SceneBuilder", "Transform", "WhittedIntegrator", "default_backend",
            "film_resolve_device", "load_ply", "load_ply_ascii", "make_rays", "read_exr", "write_exr", "_abi"]
 
@@ -20,6 +20,9 @@ def __getattr__(name):
     if name == "BloomParams":                    # likewise (python -m fountain_amd.bloom)
         from . import bloom
         return bloom.BloomParams
+    if name == "VectorBlurParams":               # likewise (python -m fountain_amd.vectorblur)
+        from . import vectorblur
+        return vectorblur.VectorBlurParams
     if name in ("MetricsParams", "compare", "compare_cpu", "compare_device"):     # likewise (python -m fountain_amd.metrics)
         from . import metrics
         return getattr(metrics, name)

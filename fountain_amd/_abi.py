@@ -299,6 +299,16 @@ FTN_BLOOM_KARIS = 1
 FTN_BLOOM_MAX_LEVELS = 12
 FTN_BLOOM_ABI_VERSION = 1    # include/fountain_hip_bloom.h (an extension with a version of its own)
 
+class ftn_vectorblur_params(C.Structure):
+    """include/fountain_hip_vectorblur.h: parameters of the vector-blur stage (ftn_vectorblur_params_default fills the defaults)."""
+    _fields_ = [("taps", c_i32), ("flags", c_u32), ("shutter", c_f), ("max_radius", c_f), ("depth_extent", c_f), ("reserved", c_u32 * 3)]
+
+
+FTN_VECTORBLUR_MAX_TAPS = 64
+FTN_VECTORBLUR_MAX_RADIUS = 16
+FTN_VECTORBLUR_ABI_VERSION = 1    # include/fountain_hip_vectorblur.h (an extension with a version of its own)
+
+
 class ftn_metrics_params(C.Structure):
     """include/fountain_hip_metrics.h: parameters of the measuring stage (ftn_metrics_params_default fills the defaults)."""
     _fields_ = [("flags", c_u32), ("peak", c_f), ("rel_eps", c_f), ("reserved", c_u32)]
@@ -344,7 +354,7 @@ SIZES = {
     "ftn_render_options": 16, "ftn_stats": 152, "ftn_scene_memory": 96, "ftn_texture": 48, "ftn_image": 24, "ftn_material_textures": 32,
     "ftn_gbuffer_pixel": 48, "ftn_idmatte_pixel": 80, "ftn_ao_options": 16, "ftn_ao_pixel": 32, "ftn_lightpass_pixel": 32, "ftn_motion_pixel": 32, "ftn_denoise_params": 32, "ftn_denoise_guided_params": 32, "ftn_moment_pixel": 16, "ftn_adaptive_params": 16, "ftn_adaptive_info": 24,
     "ftn_temporal_pixel": 32, "ftn_temporal_params": 32, "ftn_filter_desc": 32, "ftn_display_params": 48, "ftn_display_info": 32,
-    "ftn_bloom_params": 32, "ftn_subdiv_info": 184,
+    "ftn_bloom_params": 32, "ftn_vectorblur_params": 32, "ftn_subdiv_info": 184,
     "ftn_metrics_params": 16, "ftn_metrics_totals": 112, "ftn_metrics_result": 136,
 }
 
@@ -462,6 +472,20 @@ BLOOM_PROTOTYPES = {
     "ftn_bloom_abi_version": ([], C.c_int),
 }
 BLOOM_FUNCTIONS = sorted(BLOOM_PROTOTYPES)
+
+# Every function the extension header include/fountain_hip_vectorblur.h declares (kept apart from the lists above: the reference renders
+# single frames without a shutter, so these have no orc_* twin either), with its prototype: name -> (argument types, result type).
+_BLUR = [C.c_void_p, C.c_void_p, C.c_void_p, c_i32, c_i32, C.c_void_p]      # rgb, motion2, gb12, w, h, params
+VECTORBLUR_PROTOTYPES = {
+    "ftn_vectorblur_params_default": ([C.c_void_p], None),
+    "ftn_vectorblur": (_BLUR + [C.c_void_p, c_i32], C.c_int),
+    "ftn_vectorblur_workspace_size": ([c_i32, c_i32, C.c_void_p], C.c_int),
+    "ftn_vectorblur_device": (_BLUR + [C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
+    "ftn_vectorblur_cpu": (_BLUR + [C.c_void_p], C.c_int),
+    "ftn_vectorblur_velocities_cpu": (_BLUR[1:] + [C.c_void_p], C.c_int),
+    "ftn_vectorblur_abi_version": ([], C.c_int),
+}
+VECTORBLUR_FUNCTIONS = sorted(VECTORBLUR_PROTOTYPES)
 
 # Every function the extension header include/fountain_hip_metrics.h declares (kept apart from the lists above: the reference compares
 # no images, so these have no orc_* twin either), with its prototype: name -> (argument types, result type).

@@ -1,5 +1,5 @@
 """Helpers shared by the bindings of the calls the CPU oracle has no twin of: the render passes (gbuffer.py, moments.py, adaptive.py,
-lightpass.py) and the image-space stages (denoise.py, temporal.py, display.py, bloom.py, metrics.py, lightpass.py's compose)."""
+lightpass.py) and the image-space stages (denoise.py, temporal.py, display.py, bloom.py, vectorblur.py, metrics.py, lightpass.py's compose)."""
 import ctypes as C
 
 import numpy as np

@@ -1,6 +1,6 @@
 /*
  * ftn_stage_host.h -- what the host files of the image-space stages share (ftn_denoise_host.cpp, ftn_temporal_host.cpp,
- * ftn_display_host.cpp, ftn_bloom_host.cpp, ftn_metrics_host.cpp): the refusals every stage makes in the same words, the overlap and alignment rules over byte
+ * ftn_display_host.cpp, ftn_bloom_host.cpp, ftn_vectorblur_host.cpp, ftn_metrics_host.cpp): the refusals every stage makes in the same words, the overlap and alignment rules over byte
  * ranges, the launch result, and the device buffers of a host-buffer entry.  need_device() also serves the other host files, and the sampler,
  * pipeline and sample-range refusals are those of the passes on the wavefront pipeline (ftn_gbuffer_host.cpp, ftn_idmatte_host.cpp,
  * ftn_moments_host.cpp).

@@ -25,6 +25,8 @@ over the accumulated image and variance.  It needs at least 2 samples per pixel 
 With --dynamic every file's own scene is rendered (two scenes are alive at a time): frame k >= 1 renders its previous positions against
 frame k - 1's scene, accumulates through them and also writes out_<k>_motion.exr, the screen-space motion in R and G (B = 0).  The files'
 scenes must correspond (fountain_amd/motion.py); files that do not end with exit code 2 before anything is rendered or written.
+With --dynamic --vector-blur [SHUTTER] frame k >= 1 also writes out_<k>_blurred.exr: the frame's own render blurred along its motion
+vectors, with its G-buffer's depths (fountain_amd/vectorblur.py; the shutter is the share of the frame interval it is open, default 0.5).
 """
 import ctypes as C
 import sys
@@ -195,6 +197,12 @@ def motion_path(filename, k):
     return "%s_%d_motion.exr" % (base, k)
 
 
+def blurred_path(filename, k):
+    """out.exr, k -> out_<k>_blurred.exr (--dynamic --vector-blur)"""
+    base = filename[:-4] if filename.endswith(".exr") else filename
+    return "%s_%d_blurred.exr" % (base, k)
+
+
 def frame_paths(filename, k):
     """out.exr, k -> (out_<k>.exr, out_<k>_accumulated.exr, out_<k>_denoised_guided.exr)"""
     base = filename[:-4] if filename.endswith(".exr") else filename
@@ -216,7 +224,16 @@ def main(argv=None):
     ap.add_argument("--dynamic", action="store_true",
                     help="every file's own scene: objects may move between frames (the files' scenes must correspond); frame k >= 1 follows "
                          "them through its previous positions and also writes <name>_<k>_motion.exr")
+    ap.add_argument("--vector-blur", type=float, nargs="?", const=True, default=None, metavar="SHUTTER",
+                    help="with --dynamic: also write <name>_<k>_blurred.exr, frame k >= 1 blurred along its motion vectors; the shutter is open "
+                         "for this share of the frame interval, 0..1 (default 0.5)")
     opts = ap.parse_args(argv)
+    if opts.vector_blur is not None and not opts.dynamic:
+        print("error: --vector-blur belongs to --dynamic: a static scene's frames carry no motion vectors", file=sys.stderr)
+        return 2
+    if opts.vector_blur is not None and opts.vector_blur is not True and not 0.0 <= opts.vector_blur <= 1.0:
+        print("error: --vector-blur takes a shutter in [0, 1]", file=sys.stderr)
+        return 2
     if opts.dynamic and len(opts.scene_files) < 2:
         print("error: --dynamic needs at least two frames: a frame's motion is against the frame before it", file=sys.stderr)
         return 2
@@ -274,6 +291,10 @@ def main(argv=None):
         if mv8 is not None:
             mv = motion_vectors(be, mv8, gb12, f.camera, prev_camera, film, device=opts.gpu)
             write_exr(motion_path(filename, k), np.concatenate([mv, np.zeros_like(mv[..., :1])], axis=-1), be)
+            if opts.vector_blur is not None:
+                from .vectorblur import vector_blur
+                shutter = {} if opts.vector_blur is True else dict(shutter=opts.vector_blur)
+                write_exr(blurred_path(filename, k), vector_blur(be, img, mv, gb12, shutter, device=opts.gpu), be)
         write_exr(plain, img, be)
         write_exr(accumulated, out, be)
         if opts.denoise_guided:
