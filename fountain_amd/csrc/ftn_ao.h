@@ -42,12 +42,12 @@ FTN_HD void ao_resolve_pixel(const float* in, uint32_t rays, float* out) {
     out[4] = h / w; out[5] = w;
 }
 
-struct AoTimes { double any_ms; unsigned long long any_launches; };
 /* ambient occlusion over the camera samples wavefront_render traces for the same parameters (indexed sampler): d_out = 8 floats per crop
- * pixel (ftn_ao_pixel), added into; spill_a / b = zero float4 per crop pixel (left non-zero where P.stats->bc_writes says so);
- * count_mode: launch_trace's, for the occlusion rays (0: the production any-hit kernels, 1: the reference-order walk) */
+ * pixel (ftn_ao_pixel), added into; P.accA / B = zero float4 per crop pixel (left non-zero where P.stats->bc_writes says so);
+ * count_mode: launch_trace's, for the occlusion rays (0: the production any-hit kernels, 1: the reference-order walk); times: any_ms and
+ * any_launches of the occlusion rays, the other fields untouched */
 int wavefront_ao(WavefrontState** state, const RenderParams& P, const std::vector<DTile>& tiles, uint32_t rays, float radius, int count_mode, float* d_out,
-                 float4* spill_a, float4* spill_b, hipStream_t stream, double* trace_ms, AoTimes* times);
-void launch_ao_resolve(const float* in, size_t n, uint32_t rays, float* out6, hipStream_t stream);
+                 hipStream_t stream, double* trace_ms, WavefrontTimes* times);
+hipError_t launch_ao_resolve(const float* in, size_t n, uint32_t rays, float* out6, hipStream_t stream);
 }  // namespace ftn
 #endif

@@ -38,16 +38,11 @@ int ftn_render_ao_device(const ftn_scene* cs, const ftn_camera_desc* cam, const 
     if (int rc = bind_scene_device(s, opt)) return rc;
     hipStream_t stream = (hipStream_t)stream_v;
     if (int no = sample_range_check(sd)) return no;
-    const int count_mode = opt ? (opt->count_traffic == 2 ? 2 : (opt->count_traffic ? 1 : 0)) : 0;
-    AoTimes at{0.0, 0};
+    WavefrontTimes wt{};
     const int rc = first_hit_render(s, cam, film, sd, tr, stream, st, [&](const RenderParams& P, double* trace_ms) {
-        return wavefront_ao(&s->wf, P, s->sel, ao->rays, ao->radius, count_mode, (float*)device_pixels, P.accA, P.accB, stream, trace_ms, &at);
+        return wavefront_ao(&s->wf, P, s->sel, ao->rays, ao->radius, count_mode(opt), (float*)device_pixels, stream, trace_ms, &wt);
     });
-    if (rc == FTN_OK && st) {             /* first_hit_render has waited for the call and filled the first-hit statistics */
-        DevStats ds; HIP_TRY(hipMemcpy(&ds, s->stats.p, sizeof(ds), hipMemcpyDeviceToHost));
-        st->rays_any = ds.rays_any; st->any_ms = at.any_ms; st->any_launches = at.any_launches;
-    }
-    return rc;
+    return rc ? rc : any_hit_stats_out(s, wt, st);
 }
 
 int ftn_render_ao(const ftn_scene* cs, const ftn_camera_desc* cam, const ftn_film_desc* film, const ftn_sampler_desc* sd,
@@ -58,8 +53,7 @@ int ftn_render_ao(const ftn_scene* cs, const ftn_camera_desc* cam, const ftn_fil
     if (int no = wavefront_pipeline_check(opt, "ambient-occlusion")) return no;
     if (int no = need_device()) return no;
     if (int rc = bind_scene_device(cs, opt)) return rc;
-    const size_t npix = (size_t)std::max(0, film->crop[2] - film->crop[0]) * (size_t)std::max(0, film->crop[3] - film->crop[1]);
-    return continue_on_device(out_pixels, npix, [&](void* d) { return ftn_render_ao_device(cs, cam, film, sd, tr, opt, ao, d, nullptr, st); });
+    return continue_on_device(out_pixels, crop_pixels(film), [&](void* d) { return ftn_render_ao_device(cs, cam, film, sd, tr, opt, ao, d, nullptr, st); });
 }
 
 int ftn_ao_resolve(const ftn_ao_pixel* in, size_t n, uint32_t rays, float* out6) {
@@ -73,10 +67,7 @@ int ftn_ao_resolve_device(const void* in, size_t n, uint32_t rays, void* out6, v
     if (n && (!in || !out6)) return fail(FTN_ERR_INVALID_ARGUMENT, "null argument");
     if (int no = ao_rays_check(rays)) return no;
     if (int no = need_device()) return no;
-    launch_ao_resolve((const float*)in, n, rays, (float*)out6, (hipStream_t)stream);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(FTN_ERR_INTERNAL, hipGetErrorString(e));
-    return FTN_OK;
+    return launched(launch_ao_resolve((const float*)in, n, rays, (float*)out6, (hipStream_t)stream), "ambient-occlusion resolve");
 }
 
 int ftn_ao_rays(const float* hit24, const float* u2, size_t n, float radius, float* rays8) {

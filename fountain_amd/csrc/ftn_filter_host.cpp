@@ -66,8 +66,6 @@ int radius_refusal(const ftn_film_desc* film, const ftn_filter_desc* f) {
     return FTN_OK;
 }
 
-size_t crop_pixels(const ftn_film_desc* film) { return (size_t)std::max(0, film->crop[2] - film->crop[0]) * (size_t)std::max(0, film->crop[3] - film->crop[1]); }
-
 /* f(begin, end) over [0, n) in contiguous blocks on the host's threads (each element is written from its own inputs alone) */
 template <class F> void filter_parallel_for(size_t n, F f) {
     const int nt = (int)std::min<size_t>((size_t)host_threads(), n / 64 + 1);

@@ -28,7 +28,7 @@ int ftn_render_gbuffer_device(const ftn_scene* cs, const ftn_camera_desc* cam, c
     hipStream_t stream = (hipStream_t)stream_v;
     if (int no = sample_range_check(sd)) return no;
     return first_hit_render(s, cam, film, sd, tr, stream, st, [&](const RenderParams& P, double* trace_ms) {
-        return wavefront_gbuffer(&s->wf, P, s->sel, cam->camera_to_world.inv, (float*)device_pixels, P.accA, P.accB, P.accC, stream, trace_ms);
+        return wavefront_gbuffer(&s->wf, P, s->sel, cam->camera_to_world.inv, (float*)device_pixels, stream, trace_ms);
     });
 }
 
@@ -39,8 +39,7 @@ int ftn_render_gbuffer(const ftn_scene* cs, const ftn_camera_desc* cam, const ft
         return ftn_render_gbuffer_device(cs, cam, film, sd, tr, opt, out_pixels, nullptr, st);
     if (int no = need_device()) return no;
     if (int rc = bind_scene_device(cs, opt)) return rc;
-    const size_t npix = (size_t)std::max(0, film->crop[2] - film->crop[0]) * (size_t)std::max(0, film->crop[3] - film->crop[1]);
-    return continue_on_device(out_pixels, npix, [&](void* d) { return ftn_render_gbuffer_device(cs, cam, film, sd, tr, opt, d, nullptr, st); });
+    return continue_on_device(out_pixels, crop_pixels(film), [&](void* d) { return ftn_render_gbuffer_device(cs, cam, film, sd, tr, opt, d, nullptr, st); });
 }
 
 int ftn_gbuffer_resolve(const ftn_gbuffer_pixel* in, size_t n, float* out12) {
@@ -51,11 +50,8 @@ int ftn_gbuffer_resolve(const ftn_gbuffer_pixel* in, size_t n, float* out12) {
 
 int ftn_gbuffer_resolve_device(const void* in, size_t n, void* out12, void* stream) {
     if (n && (!in || !out12)) return fail(FTN_ERR_INVALID_ARGUMENT, "null argument");
-    if (ftn_device_count() <= 0) return fail(FTN_ERR_NO_DEVICE, "no HIP device");
-    launch_gbuffer_resolve((const float*)in, n, (float*)out12, (hipStream_t)stream);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(FTN_ERR_INTERNAL, hipGetErrorString(e));
-    return FTN_OK;
+    if (ftn_device_count() <= 0) return fail(FTN_ERR_NO_DEVICE, "no HIP device");          /* (not need_device(): this entry's refusal has words of its own) */
+    return launched(launch_gbuffer_resolve((const float*)in, n, (float*)out12, (hipStream_t)stream), "G-buffer resolve");
 }
 
 }  /* extern "C" */

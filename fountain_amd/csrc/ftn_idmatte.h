@@ -16,7 +16,7 @@ namespace ftn {
  * primitive in BVH order; d_out = 20 words per crop pixel (ftn_idmatte_pixel), continued */
 int wavefront_idmatte(WavefrontState** state, const RenderParams& P, const std::vector<DTile>& tiles, const uint32_t* d_ids, uint32_t* d_out,
                       hipStream_t stream, double* trace_ms);
-void launch_idmatte_resolve(const uint32_t* in, size_t n, uint32_t* out20, hipStream_t stream);
+hipError_t launch_idmatte_resolve(const uint32_t* in, size_t n, uint32_t* out20, hipStream_t stream);
 /* ids: n_ids sorted ids on the device */
 void launch_idmatte_select(const uint32_t* resolved, size_t n, const uint32_t* ids, size_t n_ids, uint32_t flags, float* mask, hipStream_t stream);
 

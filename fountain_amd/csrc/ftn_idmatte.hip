@@ -6,10 +6,9 @@
  * launches of k_im_shade and k_im_accumulate.  The foreign list -- its allocation before the first pass, its sort and k_im_apply after the
  * last -- is this unit's.
  */
-#include "ftn_wf_internal.h"
+#include "ftn_firsthit.h"
 #include "ftn_idmatte.h"
 #include <hipcub/hipcub.hpp>
-#include <algorithm>
 #include <cstring>
 
 namespace ftn {
@@ -40,19 +39,10 @@ __global__ void __launch_bounds__(256) k_im_shade(RenderParams P, WfBuffers W, I
     uint32_t p = 0;
     if (qi < *count_in) {
         p = q_in[qi];
-        const DHit h = load_hit(W, p);
-        uint2 r = make_uint2(0u, 0u);                                              /* a miss */
-        if (h.prim >= 0) {
-            const float4 ro = W.ray[2 * (size_t)p], rdv = W.ray[2 * (size_t)p + 1];
-            DRay ray0; ray0.o = V3(ro.x, ro.y, ro.z); ray0.d = V3(rdv.x, rdv.y, rdv.z); ray0.t_max = rdv.w; ray0.time = 0.0f;
-            DSI si; make_interaction(S, h, ray0, &si);
-            if (si.mat < 0) {
-                const DRay nr = spawn_ray(si.hit, ray0.d);
-                W.ray[2 * (size_t)p] = make_float4(nr.o.x, nr.o.y, nr.o.z, 0.0f); W.ray[2 * (size_t)p + 1] = make_float4(nr.d.x, nr.d.y, nr.d.z, nr.t_max);
-                push = true;
-            } else r = make_uint2(G.ids[h.prim], 1u);
-        }
-        if (!push) G.rec[p] = r;
+        DRay ray0; DHit h; DSI si;
+        const FhHit found = fh_first_hit(S, W, p, &ray0, &h, &si);
+        push = found == FH_THROUGH;
+        if (!push) G.rec[p] = found == FH_SURFACE ? make_uint2(G.ids[h.prim], 1u) : make_uint2(0u, 0u);          /* (a miss: zeros) */
     }
     const bool pred[1] = {push};
     const uint32_t val[1] = {p};
@@ -86,7 +76,7 @@ __device__ inline void im_film_add(const ImParams& G, const FilmCtx& F, V2 p_fil
 
 /* One thread per pixel slot takes its samples in sample order into the pixel's table, which stays in registers from the load to the
  * store; the workgroup stages IM_ACC_CHUNK samples of its 256 slots (8 bytes each, neighbours in memory) through LDS with coalesced
- * loads, as k_gb_accumulate does. */
+ * loads, as k_fh_accumulate (ftn_firsthit.h) does for the passes whose film is float sums. */
 #define IM_ACC_CHUNK 8u
 __global__ void __launch_bounds__(256) k_im_accumulate(RenderParams P, WfBuffers W, ImParams G, uint32_t first_of_call) {
     __shared__ uint2 s_rec[IM_ACC_CHUNK * 256];
@@ -140,14 +130,11 @@ __global__ void __launch_bounds__(256) k_im_apply(ImParams G, const unsigned lon
     im_store(t, px);
 }
 
-__global__ void __launch_bounds__(256) k_im_resolve(const uint32_t* __restrict__ in, size_t n, uint32_t* __restrict__ out20) {
-    for (size_t i = (size_t)blockIdx.x * 256u + threadIdx.x; i < n; i += (size_t)gridDim.x * 256u) idmatte_resolve_pixel(in + IM_WORDS * i, out20 + IM_WORDS * i);
-}
-void launch_idmatte_resolve(const uint32_t* in, size_t n, uint32_t* out20, hipStream_t stream) {
-    if (n == 0) return;
-    const unsigned grid = (unsigned)std::min<size_t>((n + 255) / 256, 4096);
-    hipLaunchKernelGGL(k_im_resolve, dim3(grid), dim3(256), 0, stream, in, n, out20);
-}
+struct ImResolve {
+    const uint32_t* in; uint32_t* out20;
+    __device__ void operator()(size_t i) const { idmatte_resolve_pixel(in + IM_WORDS * i, out20 + IM_WORDS * i); }
+};
+hipError_t launch_idmatte_resolve(const uint32_t* in, size_t n, uint32_t* out20, hipStream_t stream) { return fh_per_pixel(n, stream, ImResolve{in, out20}); }
 
 __global__ void __launch_bounds__(256) k_im_select(const uint32_t* __restrict__ resolved, size_t n, const uint32_t* __restrict__ ids, size_t n_ids, uint32_t flags, float* __restrict__ mask) {
     for (size_t i = (size_t)blockIdx.x * 256u + threadIdx.x; i < n; i += (size_t)gridDim.x * 256u) mask[i] = idmatte_select_pixel(resolved + IM_WORDS * i, ids, n_ids, flags);
@@ -217,7 +204,7 @@ int wavefront_idmatte(WavefrontState** state, const RenderParams& P, const std::
         return FTN_ERR_OUT_OF_MEMORY;
     }
     if (ctr[0]) {
-        const size_t npix = (size_t)std::max(0, P.crop[2] - P.crop[0]) * (size_t)std::max(0, P.crop[3] - P.crop[1]);
+        const size_t npix = fh_crop_pixels(P);
         int end_bit = 33; while (end_bit < 64 && ((unsigned long long)npix >> (end_bit - 32)) != 0ull) end_bit++;
         hipcub::DoubleBuffer<unsigned long long> keys(sp.key[0], sp.key[1]), vals(sp.val[0], sp.val[1]);
         size_t need = 0;

@@ -27,8 +27,7 @@ static int idmatte_refusals(const ftn_scene* cs, const ftn_camera_desc* cam, con
         return fail(FTN_ERR_UNSUPPORTED, "the ID-matte pass takes footprints of up to 3 x 3 pixels: a filter radius of at most 1 in each axis");
     if (int no = sample_range_check(sd)) return no;
     if (sd->samples_per_pixel >= (1u << IM_SAMPLE_BITS)) return fail(FTN_ERR_UNSUPPORTED, "the ID-matte pass takes fewer than 2^28 samples per pixel");
-    const int64_t npix = (int64_t)std::max(0, film->crop[2] - film->crop[0]) * (int64_t)std::max(0, film->crop[3] - film->crop[1]);
-    if (npix >= ((int64_t)1 << 31)) return fail(FTN_ERR_INVALID_ARGUMENT, "the crop window must be below 2^31 pixels");
+    if (crop_pixels(film) >= ((size_t)1 << 31)) return fail(FTN_ERR_INVALID_ARGUMENT, "the crop window must be below 2^31 pixels");
     return FTN_OK;
 }
 
@@ -64,9 +63,8 @@ int ftn_render_idmatte(const ftn_scene* cs, const ftn_camera_desc* cam, const ft
     if (int no = need_device()) return no;
     if (n_prim_ids != cs->host.order.size()) return fail(FTN_ERR_INVALID_ARGUMENT, "n_prim_ids must be the scene's primitive count (" + std::to_string(cs->host.order.size()) + ")");
     if (int rc = bind_scene_device(cs, opt)) return rc;
-    const size_t npix = (size_t)std::max(0, film->crop[2] - film->crop[0]) * (size_t)std::max(0, film->crop[3] - film->crop[1]);
     /* the caller's tables go to the device and come back: the call continues them */
-    return continue_on_device(out_pixels, npix, [&](void* d) { return ftn_render_idmatte_device(cs, cam, film, sd, tr, opt, prim_ids, n_prim_ids, d, nullptr, st); });
+    return continue_on_device(out_pixels, crop_pixels(film), [&](void* d) { return ftn_render_idmatte_device(cs, cam, film, sd, tr, opt, prim_ids, n_prim_ids, d, nullptr, st); });
 }
 
 int ftn_idmatte_resolve(const ftn_idmatte_pixel* in, size_t n, void* out20) {
@@ -78,8 +76,7 @@ int ftn_idmatte_resolve(const ftn_idmatte_pixel* in, size_t n, void* out20) {
 int ftn_idmatte_resolve_device(const void* in, size_t n, void* out20, void* stream) {
     if (n && (!in || !out20)) return fail(FTN_ERR_INVALID_ARGUMENT, "null argument");
     if (int no = need_device()) return no;
-    launch_idmatte_resolve((const uint32_t*)in, n, (uint32_t*)out20, (hipStream_t)stream);
-    return launched(hipGetLastError(), "ID-matte resolve");
+    return launched(launch_idmatte_resolve((const uint32_t*)in, n, (uint32_t*)out20, (hipStream_t)stream), "ID-matte resolve");
 }
 
 static int select_refusals(const void* resolved, size_t n, const uint32_t* ids, size_t n_ids, uint32_t flags, const void* mask) {

@@ -63,13 +63,13 @@ FTN_HD void lp_compose_pixel(const float* gb, const float* res8, size_t i, size_
     rgb[0] = acc[0]; rgb[1] = acc[1]; rgb[2] = acc[2];
 }
 
-struct LpTimes { double any_ms; unsigned long long any_launches; };
 /* the light-group pass over the camera samples wavefront_render traces for the same parameters (indexed sampler): d_lights = the group's
  * n_lights indices into S.lights in device memory, or NULL for all n_lights = S.n_lights of them; d_out = 8 floats per crop pixel
- * (ftn_lightpass_pixel), added into; spill_a / b = zero float4 per crop pixel (left non-zero where P.stats->bc_writes says so);
- * count_mode: launch_trace's, for the shadow rays (0: the production any-hit kernels, 1: the reference-order walk) */
+ * (ftn_lightpass_pixel), added into; P.accA / B = zero float4 per crop pixel (left non-zero where P.stats->bc_writes says so);
+ * count_mode: launch_trace's, for the shadow rays (0: the production any-hit kernels, 1: the reference-order walk); times: any_ms and
+ * any_launches of the shadow rays, the other fields untouched */
 int wavefront_lightpass(WavefrontState** state, const RenderParams& P, const std::vector<DTile>& tiles, const uint32_t* d_lights, uint32_t n_lights, int count_mode,
-                        float* d_out, float4* spill_a, float4* spill_b, hipStream_t stream, double* trace_ms, LpTimes* times);
+                        float* d_out, hipStream_t stream, double* trace_ms, WavefrontTimes* times);
 hipError_t launch_lp_resolve(const float* in, size_t n, float* out8, hipStream_t stream);
 hipError_t launch_lp_compose(const float* gb12, const float* res8, uint32_t groups, const LpGains& gains, size_t n, float* rgb, hipStream_t stream);
 }  // namespace ftn

@@ -71,29 +71,23 @@ int ftn_render_lightpass_device(const ftn_scene* cs, const ftn_camera_desc* cam,
     if (int rc = bind_scene_device(s, opt)) return rc;
     hipStream_t stream = (hipStream_t)stream_v;
     if (int no = sample_range_check(sd)) return no;
-    const int count_mode = opt ? (opt->count_traffic == 2 ? 2 : (opt->count_traffic ? 1 : 0)) : 0;
     /* the group's list, uploaded for this call and freed on every way out (first_hit_render has drained the stream when it returns) */
     DevBuf<uint32_t> d_lights;
     struct Release { DevBuf<uint32_t>& b; ~Release() { b.release(); } } keep{d_lights};
     if (int rc = d_lights.upload(lights, n_lights)) return rc;
     const uint32_t n = lights ? n_lights : s->d.n_lights;
-    LpTimes lt{0.0, 0};
+    WavefrontTimes wt{};
     const int rc = first_hit_render(s, cam, film, sd, tr, stream, st, [&](const RenderParams& P, double* trace_ms) {
-        return wavefront_lightpass(&s->wf, P, s->sel, d_lights.p, n, count_mode, (float*)device_pixels, P.accA, P.accB, stream, trace_ms, &lt);
+        return wavefront_lightpass(&s->wf, P, s->sel, d_lights.p, n, count_mode(opt), (float*)device_pixels, stream, trace_ms, &wt);
     });
-    if (rc == FTN_OK && st) {             /* first_hit_render has waited for the call and filled the first-hit statistics */
-        DevStats ds; HIP_TRY(hipMemcpy(&ds, s->stats.p, sizeof(ds), hipMemcpyDeviceToHost));
-        st->rays_any = ds.rays_any; st->any_ms = lt.any_ms; st->any_launches = lt.any_launches;
-    }
-    return rc;
+    return rc ? rc : any_hit_stats_out(s, wt, st);
 }
 
 int ftn_render_lightpass(const ftn_scene* cs, const ftn_camera_desc* cam, const ftn_film_desc* film, const ftn_sampler_desc* sd, const ftn_tile_range* tr,
                          const ftn_render_options* opt, const uint32_t* lights, uint32_t n_lights, ftn_lightpass_pixel* out_pixels, ftn_stats* st) {
     if (int no = render_refusals(cs, cam, film, sd, opt, lights, n_lights, out_pixels)) return no;          /* (before any device work) */
     if (int rc = bind_scene_device(cs, opt)) return rc;
-    const size_t npix = (size_t)std::max(0, film->crop[2] - film->crop[0]) * (size_t)std::max(0, film->crop[3] - film->crop[1]);
-    return continue_on_device(out_pixels, npix, [&](void* d) { return ftn_render_lightpass_device(cs, cam, film, sd, tr, opt, lights, n_lights, d, nullptr, st); });
+    return continue_on_device(out_pixels, crop_pixels(film), [&](void* d) { return ftn_render_lightpass_device(cs, cam, film, sd, tr, opt, lights, n_lights, d, nullptr, st); });
 }
 
 int ftn_lightpass_resolve(const ftn_lightpass_pixel* in, size_t n, float* out8) {

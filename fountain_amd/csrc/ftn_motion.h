@@ -15,11 +15,11 @@ namespace ftn {
 #define MV_REMAP_COPY 0x80000000u
 
 /* previous-position pass over the camera samples wavefront_gbuffer records for the same parameters: d_out = 8 floats per crop pixel
- * (ftn_motion_pixel), added into; spill_a / b = zero float4 per crop pixel (left non-zero where P.stats->bc_writes says so).  prev: the
+ * (ftn_motion_pixel), added into; P.accA / B = zero float4 per crop pixel (left non-zero where P.stats->bc_writes says so).  prev: the
  * previous scene's arrays; remap: per primitive of the current scene in BVH order, the previous scene's BVH index of the same primitive
  * (every entry validated by the caller against prev.n_prims and the primitive's kind), MV_REMAP_COPY or-ed in */
 int wavefront_motion(WavefrontState** state, const RenderParams& P, const std::vector<DTile>& tiles, const DScene& prev, const uint32_t* remap,
-                     float* d_out, float4* spill_a, float4* spill_b, hipStream_t stream, double* trace_ms);
+                     float* d_out, hipStream_t stream, double* trace_ms);
 
 /* ftn_motion_resolve for one pixel: sums {position 3, normal 3, H, W} -> {position / H, normal / W, H / W, W} */
 FTN_HD void motion_resolve_pixel(const float* in, float* out) {
@@ -30,7 +30,7 @@ FTN_HD void motion_resolve_pixel(const float* in, float* out) {
     for (int k = 3; k < 6; k++) out[k] = in[k] / w;
     out[6] = h / w; out[7] = w;
 }
-void launch_motion_resolve(const float* in, size_t n, float* mv8, hipStream_t stream);
+hipError_t launch_motion_resolve(const float* in, size_t n, float* mv8, hipStream_t stream);
 
 /* what the motion vectors need beside the buffers */
 struct MvFrame { TpCamera cur, prev; int w, h, x0, y0; };

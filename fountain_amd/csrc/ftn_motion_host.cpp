@@ -110,7 +110,7 @@ static int render_motion_device(const ftn_scene* cs, const ftn_scene* prev, cons
     uint32_t* d_remap = nullptr;
     if ((rc = bufs.upload(remap.data(), remap.size(), &d_remap))) return rc;
     return first_hit_render(s, cam, film, sd, tr, stream, st, [&](const RenderParams& P, double* trace_ms) {        /* (it drains the stream before a failing return: d_remap is freed here) */
-        return wavefront_motion(&s->wf, P, s->sel, prev->d, d_remap, (float*)device_pixels, P.accA, P.accB, stream, trace_ms);
+        return wavefront_motion(&s->wf, P, s->sel, prev->d, d_remap, (float*)device_pixels, stream, trace_ms);
     });
 }
 
@@ -144,8 +144,7 @@ int ftn_render_motion(const ftn_scene* cs, const ftn_scene* prev, const ftn_came
     std::vector<uint32_t> remap;
     if (int no = motion_refusals(cs, prev, cam, film, sd, opt, out_pixels, &remap)) return no;
     if (int rc = bind_scene_device(cs, opt)) return rc;
-    const size_t npix = (size_t)std::max(0, film->crop[2] - film->crop[0]) * (size_t)std::max(0, film->crop[3] - film->crop[1]);
-    return continue_on_device(out_pixels, npix, [&](void* d) { return render_motion_device(cs, prev, remap, cam, film, sd, tr, opt, d, nullptr, st); });
+    return continue_on_device(out_pixels, crop_pixels(film), [&](void* d) { return render_motion_device(cs, prev, remap, cam, film, sd, tr, opt, d, nullptr, st); });
 }
 
 int ftn_motion_resolve(const ftn_motion_pixel* in, size_t n, float* mv8) {
@@ -157,8 +156,7 @@ int ftn_motion_resolve(const ftn_motion_pixel* in, size_t n, float* mv8) {
 int ftn_motion_resolve_device(const void* in, size_t n, void* mv8, void* stream) {
     if (n && (!in || !mv8)) return fail(FTN_ERR_INVALID_ARGUMENT, "null argument");
     if (int no = need_device()) return no;
-    launch_motion_resolve((const float*)in, n, (float*)mv8, (hipStream_t)stream);
-    return launched(hipGetLastError(), "motion resolve");
+    return launched(launch_motion_resolve((const float*)in, n, (float*)mv8, (hipStream_t)stream), "motion resolve");
 }
 
 int ftn_motion_vectors_device(const void* mv8, const void* gb12, const ftn_camera_desc* cur, const ftn_camera_desc* prev, const ftn_film_desc* film,

@@ -3,7 +3,7 @@
  * ftn_display_host.cpp, ftn_bloom_host.cpp, ftn_vectorblur_host.cpp, ftn_metrics_host.cpp): the refusals every stage makes in the same words, the overlap and alignment rules over byte
  * ranges, the launch result, and the device buffers of a host-buffer entry.  need_device() also serves the other host files, and the sampler,
  * pipeline and sample-range refusals are those of the passes on the wavefront pipeline (ftn_gbuffer_host.cpp, ftn_idmatte_host.cpp,
- * ftn_moments_host.cpp).
+ * ftn_moments_host.cpp), as are the crop's pixel count, count_mode and the any-hit statistics of the first-hit passes.
  *
  * Like ftn_host_internal.h, which it builds on, everything here has hidden visibility and exports nothing.
  */
@@ -33,6 +33,20 @@ inline int wavefront_pipeline_check(const ftn_render_options* opt, const char* p
 inline int sample_range_check(const ftn_sampler_desc* sd) {
     if ((uint64_t)sd->first_sample > (uint64_t)sd->samples_per_pixel || (uint64_t)sd->first_sample + (uint64_t)sd->sample_count > (uint64_t)sd->samples_per_pixel)
         return fail(FTN_ERR_INVALID_ARGUMENT, "sample range outside [0, samples_per_pixel]");
+    return FTN_OK;
+}
+
+/* the crop window's pixel count (ftn_firsthit.h has the pass units' twin over RenderParams) */
+inline size_t crop_pixels(const ftn_film_desc* film) { return (size_t)std::max(0, film->crop[2] - film->crop[0]) * (size_t)std::max(0, film->crop[3] - film->crop[1]); }
+/* launch_trace's count argument for the options' count_traffic: 0 the production kernels, 1 the reference-order walk, 2 the counting build
+ * of the production kernels */
+inline int count_mode(const ftn_render_options* opt) { return opt ? (opt->count_traffic == 2 ? 2 : (opt->count_traffic ? 1 : 0)) : 0; }
+/* The any-hit statistics of a first-hit pass that traces rays of its own (ambient occlusion, light groups), behind a first_hit_render that
+ * returned FTN_OK: it has waited for the call and filled the first-hit statistics */
+inline int any_hit_stats_out(const ftn_scene* s, const ftn::WavefrontTimes& wt, ftn_stats* st) {
+    if (!st) return FTN_OK;
+    ftn::DevStats ds; HIP_TRY(hipMemcpy(&ds, s->stats.p, sizeof(ds), hipMemcpyDeviceToHost));
+    st->rays_any = ds.rays_any; st->any_ms = wt.any_ms; st->any_launches = wt.any_launches;
     return FTN_OK;
 }
 

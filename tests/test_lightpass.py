@@ -67,6 +67,27 @@ def test_replay(gpu, orc_det, name, lights):
         assert ref["rays_any"] < ref["hits"], "no light sample was refused"
 
 
+def test_replay_with_a_wide_filter(gpu, orc_det):
+    """cornell under a box filter of radius (0.75, 0.5): half the samples reach a neighbour in x, so most pixels' sums come through the
+    spill sums and their merge.  A pixel that one foreign sample reached is held to bits, and among those pixels are shadowed ones: a
+    lit that the spill path added for an occluded sample (or added as + 0.0 onto a -0.0) would show there"""
+    radius = (0.75, 0.5)
+    ref = LR.replay(orc_det, gpu, AR.cornell, SPP, SEED, None, radius=radius)
+    scene, cam, res = _scene(gpu, "cornell")
+    _, raw, st = LP.render_lightpass(gpu, None, cam, res, _smp(), scene=scene, film=GR.film(gpu, res, (0.0, 0.0, 1.0, 1.0), radius))
+    one, many = ref["foreign"] == 1, ref["foreign"] > 1
+    shadowed = (ref["acc"][..., 0:3] < ref["acc"][..., 3:6]).any(-1)
+    print("radius %r: %d samples, %d spilled, %d shadow rays, %d occluded; pixels with 0 / 1 / more foreign samples %d / %d / %d, shadowed among the last two %d / %d" % (
+        radius, ref["n"], ref["n_spill"], ref["rays_any"], ref["occluded"], int((ref["foreign"] == 0).sum()), int(one.sum()), int(many.sum()),
+        int((one & shadowed).sum()), int((many & shadowed).sum())))
+    assert (st["camera_samples"], st["rays_closest"], st["rays_any"], st["spill_samples"]) == (ref["n"], ref["rays_closest"], ref["rays_any"], ref["n_spill"])
+    assert st["any_launches"] == 1 and st["any_ms"] > 0
+    LR.assert_matches(raw, ref, "cornell, radius %r" % (radius,))
+    # the reference reaches what the test is here for
+    assert ref["n_spill"] > 0.4 * ref["n"] and one.sum() >= 100 and many.sum() >= 100
+    assert (one & shadowed).sum() >= 5 and (many & shadowed).sum() >= 5
+
+
 # ------------------------------------------------------------------ 2. exact properties
 def test_open_and_covered(gpu):
     """nothing between surface and lights: lit == unshadowed bit for bit.  A plate that covers the light: lit == 0 while unshadowed > 0"""

@@ -166,6 +166,19 @@ def test_replay(gpu, orc_det, name):
         assert scene.info()["n_prims"] == 130 <= 640
 
 
+def test_replay_with_a_wide_filter(gpu, orc_det):
+    """cornell under a box filter of radius (0.75, 0.5): half the samples reach a neighbour in x, so the spill sums and their merge carry
+    a large part of the film; pixels no foreign sample reached stay bit-equal, the others within the reordering bound"""
+    radius = (0.75, 0.5)
+    ref = MR.replay(gpu, orc_det, SCENES["cornell"], SPP, SEED, radius=radius)
+    scene, prev, cam, res = _pair(gpu, "cornell")
+    _, raw, st = M.render_motion(gpu, None, cam, res, _smp(), scene=scene, prev_scene=prev, film=GR.film(gpu, res, (0.0, 0.0, 1.0, 1.0), radius))
+    print("radius %r: %d samples, %d spilled, %.3f of the pixels with a foreign sample" % (radius, ref["n"], ref["n_spill"], ref["foreign"].mean()))
+    assert (st["camera_samples"], st["rays_closest"], st["spill_samples"]) == (ref["n"], ref["rays_closest"], ref["n_spill"])
+    MR.assert_replayed(raw, ref, "cornell, radius %r" % (radius,))
+    assert 0.05 < ref["foreign"].mean() < 0.95, "one of the two pixel classes is all but empty"
+
+
 @pytest.mark.parametrize("name", sorted(SCENES))
 def test_equal_scenes_give_the_gbuffer(gpu, name):
     """a previous scene built like the current one (another scene object): the position and normal sums are the G-buffer's bit for bit,

@@ -26,7 +26,7 @@ int first_hit_render(ftn_scene*, const ftn_camera_desc*, const ftn_film_desc*, c
                      const std::function<int(const ftn::RenderParams&, double*)>&) { abort(); }
 namespace ftn {
 int wavefront_idmatte(WavefrontState**, const RenderParams&, const std::vector<DTile>&, const uint32_t*, uint32_t*, hipStream_t, double*) { abort(); }
-void launch_idmatte_resolve(const uint32_t*, size_t, uint32_t*, hipStream_t) { abort(); }
+hipError_t launch_idmatte_resolve(const uint32_t*, size_t, uint32_t*, hipStream_t) { abort(); }
 void launch_idmatte_select(const uint32_t*, size_t, const uint32_t*, size_t, uint32_t, float*, hipStream_t) { abort(); }
 void wavefront_destroy(WavefrontState*) {}
 }  // namespace ftn
