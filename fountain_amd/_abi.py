@@ -4,6 +4,7 @@ Only layout lives here: every struct below must match the header field for field
 (tests/test_abi.py checks sizes and that the shared library exports each declared symbol).
 """
 import ctypes as C
+from collections import namedtuple
 
 c_f = C.c_float
 c_u32 = C.c_uint32
@@ -390,61 +391,116 @@ TEST_CAMERA_ARGTYPES = [C.c_void_p, c_u32, C.c_void_p, C.c_size_t, C.c_void_p]
 FTN_TEST_MATERIAL_IN, FTN_TEST_MATERIAL_OUT = 6, 16
 TEST_MATERIAL_ARGTYPES = [C.c_void_p, c_i32, C.c_void_p, C.c_size_t, C.c_void_p]
 
-# Every function the extension header include/fountain_hip_gbuffer.h declares (kept apart from DECLARED_FUNCTIONS, which mirrors
-# fountain_hip.h alone: the reference has no G-buffer, so these have no orc_* twin).
-GBUFFER_FUNCTIONS = [
-    "ftn_render_gbuffer", "ftn_render_gbuffer_device", "ftn_gbuffer_resolve", "ftn_gbuffer_resolve_device", "ftn_gbuffer_abi_version",
-]
+# The functions of fountain_hip.h that api.py calls with declared types, name without the backend's prefix -> (argument types, result
+# type); Backend() applies them once.  CORE_TWINS are the ones the oracle's orc_* twins get as well; the rest exist in the product
+# library alone.  Every other function of the header is called with ctypes' default conversions (some, such as scene_create, intersect*
+# and render, differ between the backends).
+CORE_PROTOTYPES = {
+    "last_error": (None, C.c_char_p),
+    "transform_scale": ([c_f, c_f, c_f, C.c_void_p], C.c_int),
+    "transform_rotate": ([c_f, C.c_void_p, C.c_void_p], C.c_int),
+    "transform_perspective": ([c_f, c_f, c_f, C.c_void_p], C.c_int),
+    "sphere_init": ([C.c_void_p, C.c_void_p, C.c_int, c_f, c_f, c_f, c_f, C.c_void_p], C.c_int),
+    "camera_perspective": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, c_f, c_f, c_f, C.c_void_p], C.c_int),
+    "test_interaction": (TEST_INTERACTION_ARGTYPES, C.c_int),
+    "test_camera": (TEST_CAMERA_ARGTYPES, C.c_int),
+    "pbrt_load": ([C.c_char_p, C.POINTER(C.c_void_p)], C.c_int),
+    "pbrt_destroy": ([C.c_void_p], None),
+    "pbrt_scene": ([C.c_void_p], C.POINTER(ftn_scene_desc)),
+    "pbrt_camera": ([C.c_void_p], C.POINTER(ftn_camera_desc)),
+    "pbrt_film": ([C.c_void_p], C.POINTER(ftn_film_desc)),
+    "pbrt_samples_per_pixel": ([C.c_void_p], C.c_int),
+    "pbrt_film_name": ([C.c_void_p], C.c_char_p),
+    "pbrt_last_error": (None, C.c_char_p),
+    "ply_load": ([C.c_char_p] + [C.c_void_p] * 8, C.c_int),
+    "film_resolve_device": ([C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p], C.c_int),
+    "exr_write": ([C.c_char_p, C.c_void_p, c_u32, c_u32], C.c_int),
+    "exr_read": ([C.c_char_p, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
+    "imageio_last_error": (None, C.c_char_p),
+}
+CORE_TWINS = ("last_error", "transform_scale", "transform_rotate", "transform_perspective", "sphere_init", "camera_perspective",
+              "test_interaction", "test_camera")
 
-# Every function the extension header include/fountain_hip_denoise.h declares (kept apart from the two lists above: the reference has
-# no denoiser, so these have no orc_* twin either).
-DENOISE_FUNCTIONS = [
-    "ftn_denoise_params_default", "ftn_denoise", "ftn_denoise_workspace_size", "ftn_denoise_device", "ftn_denoise_cpu",
-    "ftn_denoise_abi_version",
-]
+# The extension headers, one table each: every function the header declares, name -> (argument types, result type).  They are kept
+# apart from DECLARED_FUNCTIONS, which mirrors fountain_hip.h alone: the reference has none of these calls, so none has an orc_* twin.
+# X_FUNCTIONS is the sorted list of a table's names; EXTENSIONS at the end of this file is the registry _nontwin.bind works from.
+_VP = C.c_void_p
+_RENDER_ARGS = [_VP] * 8                                    # scene, camera, film, filter, sampler, integrator, tiles, options
 
-# Every function the extension header include/fountain_hip_denoise_guided.h declares (kept apart from the lists above: the reference has
-# no denoiser, so these have no orc_* twin either).
-DENOISE_GUIDED_FUNCTIONS = [
-    "ftn_denoise_guided_params_default", "ftn_denoise_guided", "ftn_denoise_guided_workspace_size", "ftn_denoise_guided_device",
-    "ftn_denoise_guided_cpu", "ftn_denoise_guided_abi_version",
-]
+# include/fountain_hip_gbuffer.h
+GBUFFER_PROTOTYPES = {
+    "ftn_render_gbuffer": ([_VP] * 8, C.c_int),
+    "ftn_render_gbuffer_device": ([_VP] * 9, C.c_int),
+    "ftn_gbuffer_resolve": ([_VP, C.c_size_t, _VP], C.c_int),
+    "ftn_gbuffer_resolve_device": ([_VP, C.c_size_t, _VP, _VP], C.c_int),
+    "ftn_gbuffer_abi_version": ([], C.c_int),
+}
+GBUFFER_FUNCTIONS = sorted(GBUFFER_PROTOTYPES)
 
-# Every function the extension header include/fountain_hip_moments.h declares (kept apart from the lists above: the reference keeps no
-# second moments, so these have no orc_* twin either).
-MOMENTS_FUNCTIONS = [
-    "ftn_render_moments", "ftn_render_moments_device", "ftn_moments_resolve", "ftn_moments_resolve_device", "ftn_moments_abi_version",
-]
+# include/fountain_hip_denoise.h and include/fountain_hip_denoise_guided.h (whose calls take var4 after gb12)
+DENOISE_PROTOTYPES = {
+    "ftn_denoise_params_default": ([_VP], None),
+    "ftn_denoise": ([_VP, _VP, c_i32, c_i32, _VP, _VP, c_i32], C.c_int),
+    "ftn_denoise_workspace_size": ([c_i32, c_i32, _VP], C.c_int),
+    "ftn_denoise_device": ([_VP, _VP, c_i32, c_i32, _VP, _VP, _VP, _VP], C.c_int),
+    "ftn_denoise_cpu": ([_VP, _VP, c_i32, c_i32, _VP, _VP], C.c_int),
+    "ftn_denoise_abi_version": ([], C.c_int),
+}
+DENOISE_FUNCTIONS = sorted(DENOISE_PROTOTYPES)
+DENOISE_GUIDED_PROTOTYPES = {
+    "ftn_denoise_guided_params_default": ([_VP], None),
+    "ftn_denoise_guided": ([_VP] * 3 + [c_i32, c_i32, _VP, _VP, c_i32], C.c_int),
+    "ftn_denoise_guided_workspace_size": ([c_i32, c_i32, _VP], C.c_int),
+    "ftn_denoise_guided_device": ([_VP] * 3 + [c_i32, c_i32, _VP, _VP, _VP, _VP], C.c_int),
+    "ftn_denoise_guided_cpu": ([_VP] * 3 + [c_i32, c_i32, _VP, _VP], C.c_int),
+    "ftn_denoise_guided_abi_version": ([], C.c_int),
+}
+DENOISE_GUIDED_FUNCTIONS = sorted(DENOISE_GUIDED_PROTOTYPES)
 
-# Every function the extension header include/fountain_hip_adaptive.h declares (kept apart from the lists above: the reference has no
-# adaptive sampling, so these have no orc_* twin either).
-ADAPTIVE_FUNCTIONS = [
-    "ftn_adaptive_params_default", "ftn_render_adaptive", "ftn_render_adaptive_device", "ftn_adaptive_converged", "ftn_adaptive_abi_version",
-]
+# include/fountain_hip_moments.h
+MOMENTS_PROTOTYPES = {
+    "ftn_render_moments": ([_VP] * 10, C.c_int),
+    "ftn_render_moments_device": ([_VP] * 11, C.c_int),
+    "ftn_moments_resolve": ([_VP, _VP, C.c_size_t, _VP], C.c_int),
+    "ftn_moments_resolve_device": ([_VP, _VP, C.c_size_t, _VP, _VP], C.c_int),
+    "ftn_moments_abi_version": ([], C.c_int),
+}
+MOMENTS_FUNCTIONS = sorted(MOMENTS_PROTOTYPES)
 
-# Every function the extension header include/fountain_hip_temporal.h declares (kept apart from the lists above: the reference renders
-# single frames, so these have no orc_* twin either).
-TEMPORAL_FUNCTIONS = [
-    "ftn_temporal_params_default", "ftn_temporal_accumulate", "ftn_temporal_accumulate_device", "ftn_temporal_accumulate_cpu",
-    "ftn_temporal_abi_version",
-]
+# include/fountain_hip_adaptive.h
+ADAPTIVE_PROTOTYPES = {
+    "ftn_adaptive_params_default": ([_VP], None),
+    "ftn_render_adaptive": ([_VP] * 13, C.c_int),
+    "ftn_render_adaptive_device": ([_VP] * 14, C.c_int),
+    "ftn_adaptive_converged": ([_VP, _VP, C.c_size_t, _VP, _VP], C.c_int),
+    "ftn_adaptive_abi_version": ([], C.c_int),
+}
+ADAPTIVE_FUNCTIONS = sorted(ADAPTIVE_PROTOTYPES)
 
-# Every function the extension header include/fountain_hip_filter.h declares (kept apart from the lists above: the reference's only
-# filter is the box, so these have no orc_* twin either), with its prototype: name -> argument types (every one returns int).
-_RENDER_ARGS = [C.c_void_p] * 8
+# include/fountain_hip_temporal.h
+_TEMPORAL = [_VP] * 5 + [c_i32, c_i32] + [_VP] * 7     # rgb, gb12, var4, camera, film, w, h, the previous three, params, the outputs
+TEMPORAL_PROTOTYPES = {
+    "ftn_temporal_params_default": ([_VP], None),
+    "ftn_temporal_accumulate": (_TEMPORAL + [c_i32], C.c_int),
+    "ftn_temporal_accumulate_device": (_TEMPORAL + [_VP], C.c_int),
+    "ftn_temporal_accumulate_cpu": (_TEMPORAL, C.c_int),
+    "ftn_temporal_abi_version": ([], C.c_int),
+}
+TEMPORAL_FUNCTIONS = sorted(TEMPORAL_PROTOTYPES)
+
+# include/fountain_hip_filter.h
 FILTER_PROTOTYPES = {
-    "ftn_filter_init": [c_u32, C.c_void_p],
-    "ftn_filter_table": [C.c_void_p, C.c_void_p],
-    "ftn_render_filtered": _RENDER_ARGS + [C.c_void_p, C.c_void_p],
-    "ftn_render_filtered_device": _RENDER_ARGS + [C.c_void_p, C.c_void_p, C.c_void_p],
-    "ftn_filter_accumulate_samples": [C.c_void_p, C.c_void_p, C.c_size_t] + [C.c_void_p] * 6,
-    "ftn_pbrt_filter": [C.c_void_p, C.c_void_p],
-    "ftn_filter_abi_version": [],
+    "ftn_filter_init": ([c_u32, C.c_void_p], C.c_int),
+    "ftn_filter_table": ([C.c_void_p, C.c_void_p], C.c_int),
+    "ftn_render_filtered": (_RENDER_ARGS + [C.c_void_p, C.c_void_p], C.c_int),
+    "ftn_render_filtered_device": (_RENDER_ARGS + [C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
+    "ftn_filter_accumulate_samples": ([C.c_void_p, C.c_void_p, C.c_size_t] + [C.c_void_p] * 6, C.c_int),
+    "ftn_pbrt_filter": ([C.c_void_p, C.c_void_p], C.c_int),
+    "ftn_filter_abi_version": ([], C.c_int),
 }
 FILTER_FUNCTIONS = sorted(FILTER_PROTOTYPES)
 
-# Every function the extension header include/fountain_hip_display.h declares (kept apart from the lists above: the reference writes
-# linear OpenEXR files only, so these have no orc_* twin either), with its prototype: name -> (argument types, result type).
+# include/fountain_hip_display.h
 _IMG = [C.c_void_p, c_i32, c_i32]
 DISPLAY_PROTOTYPES = {
     "ftn_display_params_default": ([C.c_void_p], None),
@@ -461,8 +517,7 @@ DISPLAY_PROTOTYPES = {
 }
 DISPLAY_FUNCTIONS = sorted(DISPLAY_PROTOTYPES)
 
-# Every function the extension header include/fountain_hip_bloom.h declares (kept apart from the lists above: the reference writes
-# linear OpenEXR files only, so these have no orc_* twin either), with its prototype: name -> (argument types, result type).
+# include/fountain_hip_bloom.h
 BLOOM_PROTOTYPES = {
     "ftn_bloom_params_default": ([C.c_void_p], None),
     "ftn_bloom": (_IMG + [C.c_void_p, C.c_void_p, c_i32], C.c_int),
@@ -473,8 +528,7 @@ BLOOM_PROTOTYPES = {
 }
 BLOOM_FUNCTIONS = sorted(BLOOM_PROTOTYPES)
 
-# Every function the extension header include/fountain_hip_vectorblur.h declares (kept apart from the lists above: the reference renders
-# single frames without a shutter, so these have no orc_* twin either), with its prototype: name -> (argument types, result type).
+# include/fountain_hip_vectorblur.h
 _BLUR = [C.c_void_p, C.c_void_p, C.c_void_p, c_i32, c_i32, C.c_void_p]      # rgb, motion2, gb12, w, h, params
 VECTORBLUR_PROTOTYPES = {
     "ftn_vectorblur_params_default": ([C.c_void_p], None),
@@ -487,8 +541,7 @@ VECTORBLUR_PROTOTYPES = {
 }
 VECTORBLUR_FUNCTIONS = sorted(VECTORBLUR_PROTOTYPES)
 
-# Every function the extension header include/fountain_hip_metrics.h declares (kept apart from the lists above: the reference compares
-# no images, so these have no orc_* twin either), with its prototype: name -> (argument types, result type).
+# include/fountain_hip_metrics.h
 _PAIR = [C.c_void_p, C.c_void_p, c_i32, c_i32, C.c_void_p]      # test, ref, w, h, params
 METRICS_PROTOTYPES = {
     "ftn_metrics_params_default": ([C.c_void_p], None),
@@ -502,8 +555,7 @@ METRICS_PROTOTYPES = {
 }
 METRICS_FUNCTIONS = sorted(METRICS_PROTOTYPES)
 
-# Every function the extension header include/fountain_hip_subdiv.h declares (kept apart from the lists above: the reference's
-# loop_subdiv.rs ends in unimplemented!(), so these have no orc_* twin either), with its prototype: name -> (argument types, result type).
+# include/fountain_hip_subdiv.h
 _CAGE = [C.c_void_p, c_i32, C.c_void_p, c_i32, c_i32]      # P, n_vertices, indices, n_faces, levels
 SUBDIV_PROTOTYPES = {
     "ftn_loop_subdivide_info": ([C.c_void_p, c_i32, c_i32, c_i32, C.c_void_p], C.c_int),
@@ -513,8 +565,7 @@ SUBDIV_PROTOTYPES = {
 }
 SUBDIV_FUNCTIONS = sorted(SUBDIV_PROTOTYPES)
 
-# Every function the extension header include/fountain_hip_idmatte.h declares (kept apart from the lists above: the reference renders
-# no mattes, so these have no orc_* twin either), with its prototype: name -> (argument types, result type).
+# include/fountain_hip_idmatte.h
 _STRINGS = C.POINTER(C.c_char_p)
 IDMATTE_PROTOTYPES = {
     "ftn_render_idmatte": ([C.c_void_p] * 7 + [C.c_size_t, C.c_void_p, C.c_void_p], C.c_int),
@@ -528,8 +579,7 @@ IDMATTE_PROTOTYPES = {
 }
 IDMATTE_FUNCTIONS = sorted(IDMATTE_PROTOTYPES)
 
-# Every function the extension header include/fountain_hip_ao.h declares (kept apart from the lists above: the reference has no
-# ambient-occlusion integrator, so these have no orc_* twin either), with its prototype: name -> (argument types, result type).
+# include/fountain_hip_ao.h
 AO_PROTOTYPES = {
     "ftn_render_ao": ([C.c_void_p] * 9, C.c_int),
     "ftn_render_ao_device": ([C.c_void_p] * 10, C.c_int),
@@ -540,8 +590,7 @@ AO_PROTOTYPES = {
 }
 AO_FUNCTIONS = sorted(AO_PROTOTYPES)
 
-# Every function the extension header include/fountain_hip_lightpass.h declares (kept apart from the lists above: the reference has no
-# light AOVs, so these have no orc_* twin either), with its prototype: name -> (argument types, result type).
+# include/fountain_hip_lightpass.h
 LIGHTPASS_PROTOTYPES = {
     "ftn_render_lightpass": ([C.c_void_p] * 7 + [c_u32] + [C.c_void_p] * 2, C.c_int),
     "ftn_render_lightpass_device": ([C.c_void_p] * 7 + [c_u32] + [C.c_void_p] * 3, C.c_int),
@@ -554,8 +603,7 @@ LIGHTPASS_PROTOTYPES = {
 }
 LIGHTPASS_FUNCTIONS = sorted(LIGHTPASS_PROTOTYPES)
 
-# Every function the extension header include/fountain_hip_motion.h declares (kept apart from the lists above: the reference renders
-# single frames, so these have no orc_* twin either), with its prototype: name -> (argument types, result type).
+# include/fountain_hip_motion.h
 _TEMPORAL_MOTION = [C.c_void_p] * 6 + [c_i32, c_i32] + [C.c_void_p] * 7
 MOTION_PROTOTYPES = {
     "ftn_render_motion": ([C.c_void_p] * 9, C.c_int),
@@ -571,3 +619,44 @@ MOTION_PROTOTYPES = {
     "ftn_motion_abi_version": ([], C.c_int),
 }
 MOTION_FUNCTIONS = sorted(MOTION_PROTOTYPES)
+
+
+# One extension header as _nontwin.bind needs it: the header's file, its ABI-version function and the version this binding was written
+# for, its prototypes, and the words of the two refusals -- `what` names the extension where the library reports another version,
+# `no_twin` is the sentence the oracle backend is refused with.
+Extension = namedtuple("Extension", "header abi_version_fn abi_version prototypes what no_twin")
+
+EXTENSIONS = {
+    "gbuffer": Extension("fountain_hip_gbuffer.h", "ftn_gbuffer_abi_version", FTN_GBUFFER_ABI_VERSION, GBUFFER_PROTOTYPES, "G-buffer",
+                          "the G-buffer pass has no oracle twin: the reference renders no G-buffer"),
+    "denoise": Extension("fountain_hip_denoise.h", "ftn_denoise_abi_version", FTN_DENOISE_ABI_VERSION, DENOISE_PROTOTYPES, "denoise",
+                          "the denoiser has no oracle twin: the reference has no denoiser"),
+    "denoise_guided": Extension("fountain_hip_denoise_guided.h", "ftn_denoise_guided_abi_version", FTN_DENOISE_GUIDED_ABI_VERSION, DENOISE_GUIDED_PROTOTYPES, "guided denoise",
+                                 "the denoiser has no oracle twin: the reference has no denoiser"),
+    "moments": Extension("fountain_hip_moments.h", "ftn_moments_abi_version", FTN_MOMENTS_ABI_VERSION, MOMENTS_PROTOTYPES, "moments",
+                          "the moments pass has no oracle twin: the reference keeps no second moments"),
+    "adaptive": Extension("fountain_hip_adaptive.h", "ftn_adaptive_abi_version", FTN_ADAPTIVE_ABI_VERSION, ADAPTIVE_PROTOTYPES, "adaptive",
+                           "adaptive sampling has no oracle twin: the reference has no adaptive sampling"),
+    "temporal": Extension("fountain_hip_temporal.h", "ftn_temporal_abi_version", FTN_TEMPORAL_ABI_VERSION, TEMPORAL_PROTOTYPES, "temporal",
+                           "temporal accumulation has no oracle twin: the reference renders single frames"),
+    "filter": Extension("fountain_hip_filter.h", "ftn_filter_abi_version", FTN_FILTER_ABI_VERSION, FILTER_PROTOTYPES, "filter",
+                         "the filtered film has no oracle twin: the reference's only filter is the box"),
+    "display": Extension("fountain_hip_display.h", "ftn_display_abi_version", FTN_DISPLAY_ABI_VERSION, DISPLAY_PROTOTYPES, "display",
+                          "the display stage has no oracle twin: the reference writes linear OpenEXR files only"),
+    "bloom": Extension("fountain_hip_bloom.h", "ftn_bloom_abi_version", FTN_BLOOM_ABI_VERSION, BLOOM_PROTOTYPES, "bloom",
+                        "the bloom stage has no oracle twin: the reference writes linear OpenEXR files only"),
+    "vectorblur": Extension("fountain_hip_vectorblur.h", "ftn_vectorblur_abi_version", FTN_VECTORBLUR_ABI_VERSION, VECTORBLUR_PROTOTYPES, "vector-blur",
+                             "the vector-blur stage has no oracle twin: the reference renders single frames without a shutter"),
+    "metrics": Extension("fountain_hip_metrics.h", "ftn_metrics_abi_version", FTN_METRICS_ABI_VERSION, METRICS_PROTOTYPES, "metrics",
+                          "the measuring stage has no oracle twin: the reference compares no images"),
+    "subdiv": Extension("fountain_hip_subdiv.h", "ftn_subdiv_abi_version", FTN_SUBDIV_ABI_VERSION, SUBDIV_PROTOTYPES, "subdivision",
+                         ""),
+    "idmatte": Extension("fountain_hip_idmatte.h", "ftn_idmatte_abi_version", FTN_IDMATTE_ABI_VERSION, IDMATTE_PROTOTYPES, "ID-matte",
+                          "the ID-matte pass has no oracle twin: the reference renders no mattes"),
+    "ao": Extension("fountain_hip_ao.h", "ftn_ao_abi_version", FTN_AO_ABI_VERSION, AO_PROTOTYPES, "ambient-occlusion",
+                     "the ambient-occlusion pass has no oracle twin: the reference has no such integrator"),
+    "lightpass": Extension("fountain_hip_lightpass.h", "ftn_lightpass_abi_version", FTN_LIGHTPASS_ABI_VERSION, LIGHTPASS_PROTOTYPES, "light-pass",
+                            "the light-group pass has no oracle twin: the reference has no light AOVs"),
+    "motion": Extension("fountain_hip_motion.h", "ftn_motion_abi_version", FTN_MOTION_ABI_VERSION, MOTION_PROTOTYPES, "motion",
+                         "the previous-position pass has no oracle twin: the reference renders single frames"),
+}

@@ -1,5 +1,7 @@
-"""Helpers shared by the bindings of the calls the CPU oracle has no twin of: the render passes (gbuffer.py, moments.py, adaptive.py,
-lightpass.py) and the image-space stages (denoise.py, temporal.py, display.py, bloom.py, vectorblur.py, metrics.py, lightpass.py's compose)."""
+"""Helpers shared by the bindings of the calls the CPU oracle has no twin of: the render passes (gbuffer.py, ao.py, motion.py, lightpass.py
+-- through _firsthit.py -- and idmatte.py, moments.py, adaptive.py, filters.py), the image-space stages (denoise.py, temporal.py, display.py,
+bloom.py, vectorblur.py, metrics.py, motion.py's vectors, lightpass.py's compose) and subdiv.py.  bind() is the one place where the
+functions of an extension header get their argument and result types."""
 import ctypes as C
 
 import numpy as np
@@ -8,14 +10,21 @@ from . import _abi as A
 from .api import FountainError
 
 
-def checked_lib(be, no_twin, what, abi_version_fn, abi_version):
-    """be.lib, once it is the HIP library and reports the ABI version of `what` this binding was written for."""
+def bind(be, ext):
+    """be.lib, once it is the HIP library and reports the ABI version of the extension `ext` (an A.Extension) this binding was written
+    for.  The first call for a library that passes asks for the version and gives the extension's functions their prototypes; be.bound
+    remembers that (a loaded library does not change), so later calls only look the header up there."""
     if be.is_oracle:
-        raise FountainError(A.FTN_ERR_UNSUPPORTED, no_twin)
-    have = getattr(be.lib, abi_version_fn)()
-    if have != abi_version:
-        raise FountainError(A.FTN_ERR_INTERNAL, "%s reports %s ABI version %d, this binding was written for %d: rebuild the library"
-                            % (be.path, what, have, abi_version))
+        raise FountainError(A.FTN_ERR_UNSUPPORTED, ext.no_twin)
+    if ext.header not in be.bound:
+        have = getattr(be.lib, ext.abi_version_fn)()
+        if have != ext.abi_version:
+            raise FountainError(A.FTN_ERR_INTERNAL, "%s reports %s ABI version %d, this binding was written for %d: rebuild the library"
+                                % (be.path, ext.what, have, ext.abi_version))
+        for name, (argtypes, restype) in ext.prototypes.items():
+            fn = getattr(be.lib, name)
+            fn.argtypes, fn.restype = argtypes, restype
+        be.bound.add(ext.header)
     return be.lib
 
 
@@ -30,18 +39,37 @@ def call_args(cam, film, integrator, sampler, tiles, pipeline, device, count_tra
 
 
 def index_list(indices):
-    """An optional list of indices as the (uint32 array pointer or None, length) pair of a C call, and the array to keep alive: None
-    stays None with length 0 (lightpass.py: all lights)."""
+    """An optional list of indices as the (uint32 array pointer or None, length) pair of a C call (the pointer keeps its array alive):
+    None stays None with length 0 (lightpass.py: all lights)."""
     if indices is None:
-        return None, 0, None
+        return None, 0
     a = np.ascontiguousarray(indices, dtype=np.uint32).reshape(-1)
-    return a.ctypes.data_as(C.c_void_p), len(a), a
+    return ptr(a), len(a)
 
 
 def check_tensor(t, shape):
     import torch
     if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() or tuple(t.shape) != tuple(shape):
         raise ValueError("expected a contiguous float32 CUDA tensor of shape %r" % (tuple(shape),))
+
+
+def current_stream(t):
+    """The current stream of tensor t's device, as the integer a C call takes."""
+    import torch
+    return torch.cuda.current_stream(t.device).cuda_stream
+
+
+def check_array(a, shape, what):
+    if a.shape != shape or a.dtype != np.float32 or not a.flags.c_contiguous:
+        raise ValueError("%s must be a C-contiguous float32 array of shape %r" % (what, shape))
+
+
+def desc_of(obj, typ, what):
+    """`obj` as the descriptor struct `typ`: the struct itself, or what carries one as .desc (a camera, a film); TypeError otherwise."""
+    d = obj if isinstance(obj, typ) else getattr(obj, "desc", None)
+    if not isinstance(d, typ):
+        raise TypeError("%s must be a %s or carry one as .desc" % (what, typ.__name__))
+    return d
 
 
 def check_workspace(t, need, device):
@@ -89,3 +117,8 @@ def host_image(a, channels, hw=None):
 
 def ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def tptr(t):
+    """The device pointer of a tensor (None stays None)."""
+    return None if t is None else C.c_void_p(t.data_ptr())

@@ -14,25 +14,19 @@ import ctypes as C
 import numpy as np
 
 from . import _abi as A
-from ._nontwin import call_args as _call_args, check_tensor as _check_tensor, checked_lib
+from ._nontwin import bind, call_args as _call_args, check_array as _check_array, check_tensor as _check_tensor, ptr, set_fields, tptr
 from .api import Film
-from .moments import _check_array
 
 
 def _lib(be):
-    return checked_lib(be, "adaptive sampling has no oracle twin: the reference has no adaptive sampling", "adaptive", "ftn_adaptive_abi_version",
-                       A.FTN_ADAPTIVE_ABI_VERSION)
+    return bind(be, A.EXTENSIONS["adaptive"])
 
 
 def params(be, **overrides):
     """ftn_adaptive_params_default, then the given fields (min_samples, step_samples, threshold, abs_floor)."""
     p = A.ftn_adaptive_params()
     _lib(be).ftn_adaptive_params_default(C.byref(p))
-    for k, v in overrides.items():
-        if k not in dict(A.ftn_adaptive_params._fields_):
-            raise TypeError("ftn_adaptive_params has no field %r" % k)
-        setattr(p, k, v)
-    return p
+    return set_fields(p, overrides)
 
 
 def converged(be, pixels, moments, prm):
@@ -43,8 +37,7 @@ def converged(be, pixels, moments, prm):
     if pixels.shape != moments.shape or pixels.shape[-1] != 4:
         raise ValueError("pixels and moments must have the same shape [..., 4]")
     out = np.zeros(pixels.shape[:-1], np.uint8)
-    be.check(lib.ftn_adaptive_converged(pixels.ctypes.data_as(C.c_void_p), moments.ctypes.data_as(C.c_void_p), C.c_size_t(pixels.size // 4),
-                                        C.byref(prm), out.ctypes.data_as(C.c_void_p)))
+    be.check(lib.ftn_adaptive_converged(ptr(pixels), ptr(moments), pixels.size // 4, C.byref(prm), ptr(out)))
     return out
 
 
@@ -68,8 +61,7 @@ def render_adaptive(be, builder, cam, res, integrator, sampler, prm=None, tiles=
         raise ValueError("counts must be a C-contiguous uint32 array of shape %r" % (shape[:2],))
     args, keep = _call_args(cam, film, integrator, sampler, tiles, pipeline, device, count_traffic)
     st, info = A.ftn_stats(), A.ftn_adaptive_info()
-    be.check(lib.ftn_render_adaptive(scene.handle, *args, C.byref(prm), film.pixels.ctypes.data_as(C.c_void_p), moments.ctypes.data_as(C.c_void_p),
-                                     counts.ctypes.data_as(C.c_void_p), C.byref(info), C.byref(st)))
+    be.check(lib.ftn_render_adaptive(scene.handle, *args, C.byref(prm), ptr(film.pixels), ptr(moments), ptr(counts), C.byref(info), C.byref(st)))
     return film, moments, counts, info.as_dict(), st.as_dict()
 
 
@@ -92,6 +84,6 @@ def render_adaptive_torch(scene, cam, film, integrator, sampler, prm, pixels, mo
     args, keep = _call_args(cam, film, integrator, sampler, tiles, pipeline, pixels.device.index)
     st, info = A.ftn_stats(), A.ftn_adaptive_info()
     s = (stream or torch.cuda.current_stream(pixels.device)).cuda_stream
-    be.check(lib.ftn_render_adaptive_device(scene.handle, *args, C.byref(prm), C.c_void_p(pixels.data_ptr()), C.c_void_p(moments.data_ptr()),
-                                            C.c_void_p(counts.data_ptr()), C.c_void_p(s), C.byref(info), C.byref(st)))
+    be.check(lib.ftn_render_adaptive_device(scene.handle, *args, C.byref(prm), tptr(pixels), tptr(moments),
+                                            tptr(counts), C.c_void_p(s), C.byref(info), C.byref(st)))
     return info.as_dict(), st.as_dict()

@@ -13,22 +13,17 @@ import ctypes as C
 
 import numpy as np
 
-from . import _abi as A
-from ._nontwin import call_args, check_tensor as _check_tensor, checked_lib
-from .api import Film
+from . import _abi as A, _firsthit as F
+from ._nontwin import bind, ptr
 
 # resolved channels: name -> slice of the 6 floats ftn_ao_resolve writes per pixel
 CHANNELS = {"ao": slice(0, 1), "bent": slice(1, 4), "coverage": slice(4, 5), "weight": slice(5, 6)}
+PASS = F.FirstHitPass(A.EXTENSIONS["ao"], 8, 6, ("ftn_render_ao", "ftn_render_ao_device", "ftn_ao_resolve", "ftn_ao_resolve_device"), CHANNELS)
 INF = float("inf")
 
 
 def _lib(be):
-    lib = checked_lib(be, "the ambient-occlusion pass has no oracle twin: the reference has no such integrator", "ambient-occlusion",
-                      "ftn_ao_abi_version", A.FTN_AO_ABI_VERSION)
-    for name, (argtypes, restype) in A.AO_PROTOTYPES.items():
-        fn = getattr(lib, name)
-        fn.argtypes, fn.restype = argtypes, restype
-    return lib
+    return bind(be, PASS.ext)
 
 
 def options(rays=4, radius=INF):
@@ -39,13 +34,7 @@ def options(rays=4, radius=INF):
 
 def resolve(be, raw, rays):
     """ftn_ao_resolve: raw [H, W, 8] sums -> dict of resolved [H, W, k] arrays (CHANNELS)."""
-    lib = _lib(be)
-    raw = np.ascontiguousarray(raw, dtype=np.float32)
-    if raw.shape[-1] != 8:
-        raise ValueError("the last dimension holds the 8 floats of a pixel")
-    out = np.empty(raw.shape[:-1] + (6,), np.float32)
-    be.check(lib.ftn_ao_resolve(raw.ctypes.data_as(C.c_void_p), raw.size // 8, int(rays), out.ctypes.data_as(C.c_void_p)))
-    return {k: out[..., s] for k, s in CHANNELS.items()}
+    return F.channels(PASS, F.resolve_host(PASS, be, raw, lambda: (int(rays),)))
 
 
 def ao_rays(be, hit24, u2, radius=INF):
@@ -57,7 +46,7 @@ def ao_rays(be, hit24, u2, radius=INF):
     if len(hit24) != len(u2):
         raise ValueError("one pair of draws per interaction record")
     out = np.empty((len(hit24), 8), np.float32)
-    be.check(lib.ftn_ao_rays(hit24.ctypes.data_as(C.c_void_p), u2.ctypes.data_as(C.c_void_p), len(hit24), float(radius), out.ctypes.data_as(C.c_void_p)))
+    be.check(lib.ftn_ao_rays(ptr(hit24), ptr(u2), len(hit24), float(radius), ptr(out)))
     return out
 
 
@@ -66,40 +55,16 @@ def render_ao(be, builder, cam, res, sampler, rays=4, radius=INF, tiles=None, cr
     """Shaped like gbuffer.render_gbuffer: create_scene (unless `scene` is given) + Film (unless `film` is given) + ftn_render_ao.  `raw`
     ([H, W, 8] float32) is added into when given, else a zero buffer is.  count_traffic: the occlusion rays take the reference-order
     traversal instead of the production any-hit kernels.  Returns (resolved dict, raw sums, stats)."""
-    lib = _lib(be)
-    scene = scene or builder.create_scene()
-    film = film or Film(be, res, crop)
-    if raw is None:
-        raw = np.zeros((film.height, film.width, 8), np.float32)
-    if raw.shape != (film.height, film.width, 8) or raw.dtype != np.float32 or not raw.flags.c_contiguous:
-        raise ValueError("raw must be a C-contiguous float32 array of shape %r" % ((film.height, film.width, 8),))
-    args, keep = call_args(cam, film, None, sampler, tiles, pipeline, device, count_traffic)
-    st, opt = A.ftn_stats(), options(rays, radius)
-    be.check(lib.ftn_render_ao(scene.handle, *args, C.byref(opt), raw.ctypes.data_as(C.c_void_p), C.byref(st)))
-    return resolve(be, raw, rays), raw, st.as_dict()
+    raw, st = F.render_host(PASS, be, builder, cam, res, sampler, tiles=tiles, crop=crop, scene=scene, raw=raw, pipeline=pipeline, device=device, film=film,
+                            count_traffic=count_traffic, extra=lambda: (C.byref(options(rays, radius)),))
+    return resolve(be, raw, rays), raw, st
 
 
 def render_ao_torch(scene, cam, film, sampler, out, rays=4, radius=INF, tiles=None, pipeline=A.FTN_PIPELINE_AUTO):
     """ftn_render_ao_device into `out` (float32 CUDA tensor [H, W, 8], added into) on the current stream of its device."""
-    import torch
-    be = scene.be
-    lib = _lib(be)
-    _check_tensor(out, (film.height, film.width, 8))
-    args, keep = call_args(cam, film, None, sampler, tiles, pipeline, out.device.index)
-    st, opt = A.ftn_stats(), options(rays, radius)
-    stream = torch.cuda.current_stream(out.device).cuda_stream
-    be.check(lib.ftn_render_ao_device(scene.handle, *args, C.byref(opt), C.c_void_p(out.data_ptr()), C.c_void_p(stream), C.byref(st)))
-    return st.as_dict()
+    return F.render_torch(PASS, scene, cam, film, sampler, out, tiles=tiles, pipeline=pipeline, extra=lambda: (C.byref(options(rays, radius)),))
 
 
 def resolve_torch(be, raw, rays, out):
     """ftn_ao_resolve_device: raw [..., 8] sums -> out [..., 6] resolved floats, both float32 CUDA tensors, current stream."""
-    import torch
-    lib = _lib(be)
-    _check_tensor(raw, raw.shape)
-    if raw.shape[-1] != 8:
-        raise ValueError("the last dimension holds the 8 floats of a pixel")
-    _check_tensor(out, tuple(raw.shape[:-1]) + (6,))
-    stream = torch.cuda.current_stream(raw.device).cuda_stream
-    be.check(lib.ftn_ao_resolve_device(C.c_void_p(raw.data_ptr()), raw.numel() // 8, int(rays), C.c_void_p(out.data_ptr()), C.c_void_p(stream)))
-    return out
+    return F.resolve_torch(PASS, be, raw, out, lambda: (int(rays),))

@@ -46,24 +46,14 @@ class Backend:
         self.path = path
         self.prefix = prefix
         self.is_oracle = is_oracle
-        le = getattr(self.lib, prefix + "last_error")
-        le.restype = C.c_char_p
+        self.bound = set()                    # the extension headers whose prototypes _nontwin.bind has applied to self.lib
         if not is_oracle:                     # the structs below are read and written by the library: a build against another header is refused here
             have = self.lib.ftn_abi_version() if hasattr(self.lib, "ftn_abi_version") else 0
             if have != A.FTN_ABI_VERSION:
                 raise FountainError(A.FTN_ERR_INTERNAL, "%s reports ABI version %d, this binding was written for %d: rebuild the library" % (path, have, A.FTN_ABI_VERSION))
-        for name in ("transform_scale", "transform_rotate", "transform_perspective", "sphere_init", "camera_perspective"):
+        for name in (A.CORE_TWINS if is_oracle else A.CORE_PROTOTYPES):
             fn = getattr(self.lib, prefix + name)
-            if name == "transform_scale":
-                fn.argtypes = [C.c_float, C.c_float, C.c_float, C.c_void_p]
-            elif name == "transform_rotate":
-                fn.argtypes = [C.c_float, C.c_void_p, C.c_void_p]
-            elif name == "transform_perspective":
-                fn.argtypes = [C.c_float, C.c_float, C.c_float, C.c_void_p]
-            elif name == "sphere_init":
-                fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p]
-            elif name == "camera_perspective":
-                fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_void_p]
+            fn.argtypes, fn.restype = A.CORE_PROTOTYPES[name]
 
     def fn(self, name):
         return getattr(self.lib, self.prefix + name)
@@ -625,20 +615,9 @@ class PbrtScene:
         if be.is_oracle:
             raise ValueError("scene files are read by the product library only")
         self.handle = C.c_void_p()
-        load = be.lib.ftn_pbrt_load
-        load.argtypes = [C.c_char_p, C.POINTER(C.c_void_p)]
-        rc = load(os.fsencode(path), C.byref(self.handle))
+        rc = be.lib.ftn_pbrt_load(os.fsencode(path), C.byref(self.handle))
         if rc != 0:
-            err = be.lib.ftn_pbrt_last_error
-            err.restype = C.c_char_p
-            raise FountainError(rc, err().decode())
-        for name, typ in (("scene", A.ftn_scene_desc), ("camera", A.ftn_camera_desc), ("film", A.ftn_film_desc)):
-            f = getattr(be.lib, "ftn_pbrt_" + name)
-            f.restype = C.POINTER(typ)
-            f.argtypes = [C.c_void_p]
-        be.lib.ftn_pbrt_samples_per_pixel.argtypes = [C.c_void_p]
-        be.lib.ftn_pbrt_film_name.argtypes = [C.c_void_p]
-        be.lib.ftn_pbrt_film_name.restype = C.c_char_p
+            raise FountainError(rc, be.lib.ftn_pbrt_last_error().decode())
         self.desc = be.lib.ftn_pbrt_scene(self.handle).contents
         self.samples_per_pixel = be.lib.ftn_pbrt_samples_per_pixel(self.handle)
         self.film_name = be.lib.ftn_pbrt_film_name(self.handle).decode()
@@ -661,10 +640,7 @@ class PbrtScene:
     def __del__(self):
         try:
             if self.handle:
-                d = self.be.lib.ftn_pbrt_destroy
-                d.argtypes = [C.c_void_p]
-                d.restype = None
-                d(self.handle)
+                self.be.lib.ftn_pbrt_destroy(self.handle)
                 self.handle = None
         except Exception:
             pass
@@ -673,17 +649,12 @@ class PbrtScene:
 def load_ply(path, backend=None):
     """make_triangle_mesh_from_ply's reader (constructors.rs:94-190) -> (P [nv,3], N or None, UV or None, idx [nt,3])."""
     be = backend or default_backend()
-    f = be.lib.ftn_ply_load
-    f.argtypes = [C.c_char_p] + [C.c_void_p] * 8
     nv, nt, hn, huv = C.c_uint32(), C.c_uint32(), C.c_int(), C.c_int()
 
     def call(*arrs):
-        rc = f(os.fsencode(path), C.cast(C.byref(nv), C.c_void_p), C.cast(C.byref(nt), C.c_void_p), *arrs,
-               C.cast(C.byref(hn), C.c_void_p), C.cast(C.byref(huv), C.c_void_p))
+        rc = be.lib.ftn_ply_load(os.fsencode(path), C.byref(nv), C.byref(nt), *arrs, C.byref(hn), C.byref(huv))
         if rc != 0:
-            err = be.lib.ftn_pbrt_last_error
-            err.restype = C.c_char_p
-            raise FountainError(rc, err().decode())
+            raise FountainError(rc, be.lib.ftn_pbrt_last_error().decode())
     call(None, None, None, None)
     P = np.empty((nv.value, 3), np.float32)
     N = np.empty((nv.value, 3), np.float32)
@@ -781,9 +752,7 @@ class Scene:
         """the surface-interaction test hook (ftn_test_interaction / orc_test_interaction): rows [n, 32] -> [n, 68], layouts in fountain_hip.h"""
         rows = np.ascontiguousarray(rows, dtype=np.float32).reshape(-1, A.FTN_TEST_INTERACTION_IN)
         out = np.empty((rows.shape[0], A.FTN_TEST_INTERACTION_OUT), np.float32)
-        fn = self.be.fn("test_interaction")
-        fn.argtypes = A.TEST_INTERACTION_ARGTYPES
-        self.be.check(fn(self.handle, _fptr(rows), rows.shape[0], _fptr(out)))
+        self.be.call("test_interaction", self.handle, _fptr(rows), rows.shape[0], _fptr(out))
         return out
 
 
@@ -825,9 +794,7 @@ class PerspectiveCamera:
         """the camera test hook (ftn_test_camera / orc_test_camera): rows [n, 8] = p_film, p_lens, time -> [n, 20], layouts in fountain_hip.h"""
         rows = np.ascontiguousarray(rows, dtype=np.float32).reshape(-1, A.FTN_TEST_CAMERA_IN)
         out = np.empty((rows.shape[0], A.FTN_TEST_CAMERA_OUT), np.float32)
-        fn = self.be.fn("test_camera")
-        fn.argtypes = A.TEST_CAMERA_ARGTYPES
-        self.be.check(fn(C.addressof(self.desc), int(spp), _fptr(rows), rows.shape[0], _fptr(out)))
+        self.be.call("test_camera", C.addressof(self.desc), int(spp), _fptr(rows), rows.shape[0], _fptr(out))
         return out
 
     @classmethod
@@ -876,9 +843,7 @@ class Film:
 
 
 def _io_error(be, rc):
-    err = be.lib.ftn_imageio_last_error
-    err.restype = C.c_char_p
-    return FountainError(rc, err().decode())
+    return FountainError(rc, be.lib.ftn_imageio_last_error().decode())
 
 
 def write_exr(path, rgb, backend=None):
@@ -886,9 +851,7 @@ def write_exr(path, rgb, backend=None):
     be = backend or default_backend()
     rgb = np.ascontiguousarray(rgb, dtype=np.float32)
     h, w = rgb.shape[0], rgb.shape[1]
-    f = be.lib.ftn_exr_write
-    f.argtypes = [C.c_char_p, C.c_void_p, C.c_uint32, C.c_uint32]
-    rc = f(os.fsencode(path), rgb.ctypes.data_as(C.c_void_p), w, h)
+    rc = be.lib.ftn_exr_write(os.fsencode(path), rgb.ctypes.data_as(C.c_void_p), w, h)
     if rc != 0:
         raise _io_error(be, rc)
 
@@ -897,13 +860,12 @@ def read_exr(path, backend=None):
     """read_exr (imageio/exr.rs:11-45) -> rgb [h, w, 3] float32."""
     be = backend or default_backend()
     f = be.lib.ftn_exr_read
-    f.argtypes = [C.c_char_p, C.c_void_p, C.c_void_p, C.c_void_p]
     w, h = C.c_uint32(), C.c_uint32()
-    rc = f(os.fsencode(path), C.cast(C.byref(w), C.c_void_p), C.cast(C.byref(h), C.c_void_p), None)
+    rc = f(os.fsencode(path), C.byref(w), C.byref(h), None)
     if rc != 0:
         raise _io_error(be, rc)
     rgb = np.empty((h.value, w.value, 3), np.float32)
-    rc = f(os.fsencode(path), C.cast(C.byref(w), C.c_void_p), C.cast(C.byref(h), C.c_void_p), rgb.ctypes.data_as(C.c_void_p))
+    rc = f(os.fsencode(path), C.byref(w), C.byref(h), rgb.ctypes.data_as(C.c_void_p))
     if rc != 0:
         raise _io_error(be, rc)
     return rgb
@@ -911,9 +873,7 @@ def read_exr(path, backend=None):
 
 def film_resolve_device(be, device_pixels_ptr, n_pixels, device_rgb_ptr, stream_ptr=0):
     """Film::into_spectrum_buffer (film.rs:195-210) with both buffers in HBM (device pointers)."""
-    f = be.lib.ftn_film_resolve_device
-    f.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
-    be.check(f(C.c_void_p(device_pixels_ptr), n_pixels, C.c_void_p(device_rgb_ptr), C.c_void_p(stream_ptr)))
+    be.check(be.lib.ftn_film_resolve_device(C.c_void_p(device_pixels_ptr), n_pixels, C.c_void_p(device_rgb_ptr), C.c_void_p(stream_ptr)))
 
 
 class RandomSampler:

@@ -22,17 +22,12 @@ import sys
 import numpy as np
 
 from . import _abi as A
-from ._nontwin import checked_lib, host_image, params_of, ptr, set_fields
+from ._nontwin import bind, host_image, params_of, ptr, set_fields
 from .api import default_backend
 
 
 def _lib(be):
-    lib = checked_lib(be, "the bloom stage has no oracle twin: the reference writes linear OpenEXR files only", "bloom",
-                      "ftn_bloom_abi_version", A.FTN_BLOOM_ABI_VERSION)
-    for name, (argtypes, restype) in A.BLOOM_PROTOTYPES.items():
-        fn = getattr(lib, name)
-        fn.argtypes, fn.restype = argtypes, restype
-    return lib
+    return bind(be, A.EXTENSIONS["bloom"])
 
 
 class BloomParams:

@@ -21,16 +21,15 @@ import ctypes as C
 import numpy as np
 
 from . import _abi as A
-from ._nontwin import check_tensor, check_workspace, checked_lib, host_image, params_of, ptr
+from ._nontwin import bind, check_tensor, check_workspace, current_stream, host_image, params_of, ptr, tptr
 
 
 def _lib(be):
-    return checked_lib(be, "the denoiser has no oracle twin: the reference has no denoiser", "denoise", "ftn_denoise_abi_version", A.FTN_DENOISE_ABI_VERSION)
+    return bind(be, A.EXTENSIONS["denoise"])
 
 
 def _guided_lib(be):
-    return checked_lib(be, "the denoiser has no oracle twin: the reference has no denoiser", "guided denoise", "ftn_denoise_guided_abi_version",
-                       A.FTN_DENOISE_GUIDED_ABI_VERSION)
+    return bind(be, A.EXTENSIONS["denoise_guided"])
 
 
 # the two filters: the params struct, the prefix of the C names, the library check.  The calls below are written once for both; the guided
@@ -69,13 +68,13 @@ def _host_call(be, kind, suffix, rgb, gb12, var4, params, tail):
             raise ValueError("expected var4 [H, W, 4] with the H and W of rgb %r, got %r" % (rgb.shape, np.shape(var4))) from None
     h, w = rgb.shape[:2]
     out = np.empty_like(rgb)
-    be.check(getattr(lib, kind[1] + suffix)(*map(ptr, images), C.c_int32(w), C.c_int32(h), C.byref(p), ptr(out), *tail))
+    be.check(getattr(lib, kind[1] + suffix)(*map(ptr, images), w, h, C.byref(p), ptr(out), *tail))
     return out
 
 
 def denoise(be, rgb, gb12, params=None, device=-1):
     """ftn_denoise: host arrays, filtered on GPU `device` (-1 = the current one); returns a new [H, W, 3] float32 array."""
-    return _host_call(be, _PLAIN, "", rgb, gb12, None, params, (C.c_int32(device),))
+    return _host_call(be, _PLAIN, "", rgb, gb12, None, params, (device,))
 
 
 def denoise_cpu(be, rgb, gb12, params=None):
@@ -85,7 +84,7 @@ def denoise_cpu(be, rgb, gb12, params=None):
 
 def denoise_guided(be, rgb, gb12, var4, params=None, device=-1):
     """ftn_denoise_guided: host arrays, filtered on GPU `device` (-1 = the current one); returns a new [H, W, 3] float32 array."""
-    return _host_call(be, _GUIDED, "", rgb, gb12, var4, params, (C.c_int32(device),))
+    return _host_call(be, _GUIDED, "", rgb, gb12, var4, params, (device,))
 
 
 def denoise_guided_cpu(be, rgb, gb12, var4, params=None):
@@ -95,7 +94,7 @@ def denoise_guided_cpu(be, rgb, gb12, var4, params=None):
 
 def _workspace_bytes(be, kind, w, h):
     n = C.c_size_t()
-    be.check(getattr(kind[2](be), kind[1] + "_workspace_size")(C.c_int32(w), C.c_int32(h), C.byref(n)))
+    be.check(getattr(kind[2](be), kind[1] + "_workspace_size")(w, h, C.byref(n)))
     return n.value
 
 
@@ -128,9 +127,8 @@ def _torch_call(be, kind, rgb, gb12, var4, out, workspace, params):
         workspace = torch.empty(need, dtype=torch.uint8, device=rgb.device)
     else:
         check_workspace(workspace, need, rgb.device)
-    stream = torch.cuda.current_stream(rgb.device).cuda_stream
-    be.check(getattr(lib, kind[1] + "_device")(*[C.c_void_p(t.data_ptr()) for _, t, _ in inputs], C.c_int32(w), C.c_int32(h), C.byref(p),
-                                               C.c_void_p(out.data_ptr()), C.c_void_p(workspace.data_ptr()), C.c_void_p(stream)))
+    be.check(getattr(lib, kind[1] + "_device")(*[tptr(t) for _, t, _ in inputs], w, h, C.byref(p),
+                                               tptr(out), tptr(workspace), C.c_void_p(current_stream(rgb))))
     return out
 
 

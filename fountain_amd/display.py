@@ -26,7 +26,7 @@ import sys
 import numpy as np
 
 from . import _abi as A
-from ._nontwin import checked_lib, host_image, params_of, ptr, set_fields
+from ._nontwin import bind, host_image, params_of, ptr, set_fields
 from .api import default_backend
 
 TONEMAPS = {"linear": A.FTN_DISPLAY_TONEMAP_LINEAR, "reinhard": A.FTN_DISPLAY_TONEMAP_REINHARD, "aces": A.FTN_DISPLAY_TONEMAP_ACES,
@@ -35,12 +35,7 @@ TRANSFERS = {"srgb": A.FTN_DISPLAY_TRANSFER_SRGB, "gamma": A.FTN_DISPLAY_TRANSFE
 
 
 def _lib(be):
-    lib = checked_lib(be, "the display stage has no oracle twin: the reference writes linear OpenEXR files only", "display",
-                      "ftn_display_abi_version", A.FTN_DISPLAY_ABI_VERSION)
-    for name, (argtypes, restype) in A.DISPLAY_PROTOTYPES.items():
-        fn = getattr(lib, name)
-        fn.argtypes, fn.restype = argtypes, restype
-    return lib
+    return bind(be, A.EXTENSIONS["display"])
 
 
 class DisplayParams:

@@ -16,7 +16,7 @@ import ctypes as C
 import numpy as np
 
 from . import _abi as A
-from ._nontwin import call_args as _call_args, check_tensor as _check_tensor, checked_lib
+from ._nontwin import bind, call_args as _call_args, check_array as _check_array, check_tensor as _check_tensor, current_stream, ptr, tptr
 from .api import Film, FountainError, default_backend
 
 KINDS = {"box": A.FTN_FILTER_BOX, "triangle": A.FTN_FILTER_TRIANGLE, "gaussian": A.FTN_FILTER_GAUSSIAN, "mitchell": A.FTN_FILTER_MITCHELL,
@@ -25,12 +25,7 @@ PARAMS = {"box": (), "triangle": (), "gaussian": ("alpha",), "mitchell": ("B", "
 
 
 def _lib(be):
-    lib = checked_lib(be, "the filtered film has no oracle twin: the reference's only filter is the box", "filter", "ftn_filter_abi_version",
-                      A.FTN_FILTER_ABI_VERSION)
-    for name, argtypes in A.FILTER_PROTOTYPES.items():
-        fn = getattr(lib, name)
-        fn.argtypes, fn.restype = argtypes, C.c_int
-    return lib
+    return bind(be, A.EXTENSIONS["filter"])
 
 
 class Filter:
@@ -67,9 +62,7 @@ class Filter:
         desc = A.ftn_filter_desc()
         rc = _lib(parsed.be).ftn_pbrt_filter(parsed.handle, C.byref(desc))
         if rc < 0:
-            err = parsed.be.lib.ftn_pbrt_last_error
-            err.restype = C.c_char_p
-            raise FountainError(rc, err().decode())
+            raise FountainError(rc, parsed.be.lib.ftn_pbrt_last_error().decode())
         return cls.from_desc(parsed.be, desc) if rc else None
 
     @property
@@ -79,7 +72,7 @@ class Filter:
     def table(self):
         """ftn_filter_table: Film::new's 16 x 16 table, [y, x]."""
         out = np.empty((16, 16), np.float32)
-        self.be.check(_lib(self.be).ftn_filter_table(C.byref(self.desc), out.ctypes.data_as(C.c_void_p)))
+        self.be.check(_lib(self.be).ftn_filter_table(C.byref(self.desc), ptr(out)))
         return out
 
 
@@ -88,11 +81,6 @@ def filtered_film(be, filt, res=None, crop=(0.0, 0.0, 1.0, 1.0), film=None):
     f = Film.from_desc(be, film.desc) if film is not None else Film(be, res, crop)
     f.desc.filter_radius[0], f.desc.filter_radius[1] = filt.desc.radius[0], filt.desc.radius[1]
     return f
-
-
-def _check_array(a, shape, what):
-    if a.shape != shape or a.dtype != np.float32 or not a.flags.c_contiguous:
-        raise ValueError("%s must be a C-contiguous float32 array of shape %r" % (what, shape))
 
 
 def render_filtered(be, builder, cam, res, integrator, sampler, filt, tiles=None, crop=(0.0, 0.0, 1.0, 1.0), scene=None, film=None,
@@ -105,22 +93,20 @@ def render_filtered(be, builder, cam, res, integrator, sampler, filt, tiles=None
     _check_array(film.pixels, (film.height, film.width, 4), "film.pixels")
     args, keep = _call_args(cam, film, integrator, sampler, tiles, pipeline, device, count_traffic)
     st = A.ftn_stats()
-    be.check(lib.ftn_render_filtered(scene.handle, args[0], args[1], C.byref(filt.desc), *args[2:], film.pixels.ctypes.data_as(C.c_void_p), C.byref(st)))
+    be.check(lib.ftn_render_filtered(scene.handle, args[0], args[1], C.byref(filt.desc), *args[2:], ptr(film.pixels), C.byref(st)))
     return film.into_spectrum_buffer()[0], film, st.as_dict()
 
 
 def render_filtered_torch(scene, cam, film, integrator, sampler, filt, pixels, tiles=None, pipeline=A.FTN_PIPELINE_AUTO):
     """ftn_render_filtered_device into `pixels` (ftn_pixel: a float32 CUDA tensor [H, W, 4], added into) on the current stream of its
     device."""
-    import torch
     be = scene.be
     lib = _lib(be)
     _check_tensor(pixels, (film.height, film.width, 4))
     args, keep = _call_args(cam, film, integrator, sampler, tiles, pipeline, pixels.device.index)
     st = A.ftn_stats()
-    stream = torch.cuda.current_stream(pixels.device).cuda_stream
-    be.check(lib.ftn_render_filtered_device(scene.handle, args[0], args[1], C.byref(filt.desc), *args[2:], C.c_void_p(pixels.data_ptr()),
-                                            C.c_void_p(stream), C.byref(st)))
+    be.check(lib.ftn_render_filtered_device(scene.handle, args[0], args[1], C.byref(filt.desc), *args[2:], tptr(pixels),
+                                            C.c_void_p(current_stream(pixels)), C.byref(st)))
     return st.as_dict()
 
 
@@ -138,5 +124,5 @@ def accumulate_samples(be, film, filt, px, py, sample, p_film, L, out=None):
     if out is None:
         out = np.zeros(shape, np.float32)
     _check_array(out, shape, "out")
-    be.check(lib.ftn_filter_accumulate_samples(C.byref(film.desc), C.byref(filt.desc), n, *(a.ctypes.data_as(C.c_void_p) for a in (px, py, sample, p_film, L, out))))
+    be.check(lib.ftn_filter_accumulate_samples(C.byref(film.desc), C.byref(filt.desc), n, *map(ptr, (px, py, sample, p_film, L, out))))
     return out

@@ -26,7 +26,7 @@ import sys
 import numpy as np
 
 from . import _abi as A
-from ._nontwin import call_args, check_tensor as _check_tensor, checked_lib
+from ._nontwin import bind, call_args, check_tensor as _check_tensor, current_stream, ptr, tptr
 from .api import Film, FountainError, default_backend
 
 WORDS = A.FTN_IDMATTE_RESOLVED_WORDS
@@ -37,12 +37,7 @@ LEVELS = SLOTS // 2
 
 
 def _lib(be):
-    lib = checked_lib(be, "the ID-matte pass has no oracle twin: the reference renders no mattes", "ID-matte", "ftn_idmatte_abi_version",
-                      A.FTN_IDMATTE_ABI_VERSION)
-    for name, (argtypes, restype) in A.IDMATTE_PROTOTYPES.items():
-        fn = getattr(lib, name)
-        fn.argtypes, fn.restype = argtypes, restype
-    return lib
+    return bind(be, A.EXTENSIONS["idmatte"])
 
 
 # ------------------------------------------------------------------ ids
@@ -98,7 +93,7 @@ def _words(a, what):
 
 def _id_list(ids):
     ids = np.ascontiguousarray(np.asarray(list(ids) if not isinstance(ids, np.ndarray) else ids, dtype=np.uint64).astype(np.uint32))
-    return ids, (ids.ctypes.data_as(C.c_void_p) if ids.size else None)
+    return ids, (ptr(ids) if ids.size else None)
 
 
 # ------------------------------------------------------------------ the calls
@@ -107,7 +102,7 @@ def resolve(be, raw):
     lib = _lib(be)
     raw = _words(raw, "raw")
     out = np.empty(raw.shape, np.uint32)
-    be.check(lib.ftn_idmatte_resolve(raw.ctypes.data_as(C.c_void_p), raw.size // WORDS, out.ctypes.data_as(C.c_void_p)))
+    be.check(lib.ftn_idmatte_resolve(ptr(raw), raw.size // WORDS, ptr(out)))
     return out
 
 
@@ -118,7 +113,7 @@ def select(be, resolved, ids, overflow=False, miss=False):
     ids, p = _id_list(ids)
     out = np.empty(r.shape[:-1], np.float32)
     flags = (A.FTN_IDMATTE_SELECT_OVERFLOW if overflow else 0) | (A.FTN_IDMATTE_SELECT_MISS if miss else 0)
-    be.check(lib.ftn_idmatte_select(r.ctypes.data_as(C.c_void_p), r.size // WORDS, p, ids.size, flags, out.ctypes.data_as(C.c_void_p)))
+    be.check(lib.ftn_idmatte_select(ptr(r), r.size // WORDS, p, ids.size, flags, ptr(out)))
     return out
 
 
@@ -137,41 +132,36 @@ def render_idmatte(be, builder, cam, res, sampler, ids, tiles=None, crop=(0.0, 0
     ids = np.ascontiguousarray(ids, np.uint32)
     args, keep = call_args(cam, film, None, sampler, tiles, pipeline, device)
     st = A.ftn_stats()
-    be.check(lib.ftn_render_idmatte(scene.handle, *args, ids.ctypes.data_as(C.c_void_p), ids.size, raw.ctypes.data_as(C.c_void_p), C.byref(st)))
+    be.check(lib.ftn_render_idmatte(scene.handle, *args, ptr(ids), ids.size, ptr(raw), C.byref(st)))
     return resolve(be, raw), raw, st.as_dict()
 
 
 def render_idmatte_torch(scene, cam, film, sampler, ids, out, tiles=None, pipeline=A.FTN_PIPELINE_AUTO):
     """ftn_render_idmatte_device into `out` (float32 CUDA tensor [H, W, 20] holding the tables' bit patterns, continued) on the current
     stream of its device."""
-    import torch
     be = scene.be
     lib = _lib(be)
     _check_tensor(out, (film.height, film.width, WORDS))
     ids = np.ascontiguousarray(ids, np.uint32)
     args, keep = call_args(cam, film, None, sampler, tiles, pipeline, out.device.index)
     st = A.ftn_stats()
-    stream = torch.cuda.current_stream(out.device).cuda_stream
-    be.check(lib.ftn_render_idmatte_device(scene.handle, *args, ids.ctypes.data_as(C.c_void_p), ids.size, C.c_void_p(out.data_ptr()), C.c_void_p(stream), C.byref(st)))
+    be.check(lib.ftn_render_idmatte_device(scene.handle, *args, ptr(ids), ids.size, tptr(out), C.c_void_p(current_stream(out)), C.byref(st)))
     return st.as_dict()
 
 
 def resolve_torch(be, raw, out):
     """ftn_idmatte_resolve_device: raw [..., 20] -> out [..., 20], both float32 CUDA tensors of bit patterns, current stream"""
-    import torch
     lib = _lib(be)
     _check_tensor(raw, raw.shape)
     _check_tensor(out, raw.shape)
     if raw.shape[-1] != WORDS:
         raise ValueError("the last dimension holds the 20 words of a pixel")
-    stream = torch.cuda.current_stream(raw.device).cuda_stream
-    be.check(lib.ftn_idmatte_resolve_device(C.c_void_p(raw.data_ptr()), raw.numel() // WORDS, C.c_void_p(out.data_ptr()), C.c_void_p(stream)))
+    be.check(lib.ftn_idmatte_resolve_device(tptr(raw), raw.numel() // WORDS, tptr(out), C.c_void_p(current_stream(raw))))
     return out
 
 
 def select_torch(be, resolved, ids, out, overflow=False, miss=False):
     """ftn_idmatte_select_device: resolved [..., 20] -> out [...], float32 CUDA tensors, current stream"""
-    import torch
     lib = _lib(be)
     _check_tensor(resolved, resolved.shape)
     _check_tensor(out, resolved.shape[:-1])
@@ -179,9 +169,8 @@ def select_torch(be, resolved, ids, out, overflow=False, miss=False):
         raise ValueError("the last dimension holds the 20 words of a pixel")
     ids, p = _id_list(ids)
     flags = (A.FTN_IDMATTE_SELECT_OVERFLOW if overflow else 0) | (A.FTN_IDMATTE_SELECT_MISS if miss else 0)
-    stream = torch.cuda.current_stream(resolved.device).cuda_stream
-    be.check(lib.ftn_idmatte_select_device(C.c_void_p(resolved.data_ptr()), resolved.numel() // WORDS, p, ids.size, flags, C.c_void_p(out.data_ptr()),
-                                           C.c_void_p(stream)))
+    be.check(lib.ftn_idmatte_select_device(tptr(resolved), resolved.numel() // WORDS, p, ids.size, flags, tptr(out),
+                                           C.c_void_p(current_stream(resolved))))
     return out
 
 
@@ -260,9 +249,7 @@ def write_channels(path, planes, attrs=None, be=None):
     h, w = arrs[0].shape
     rc = lib.ftn_exr_write_channels(path.encode(), w, h, len(arrs), strings(names), ptrs, len(attrs), strings(list(attrs)), strings(list(attrs.values())))
     if rc != 0:
-        err = be.lib.ftn_imageio_last_error
-        err.restype = C.c_char_p
-        raise FountainError(rc, err().decode())
+        raise FountainError(rc, be.lib.ftn_imageio_last_error().decode())
 
 
 def write_cryptomatte(path, layers, be=None):

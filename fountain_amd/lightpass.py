@@ -22,22 +22,18 @@ import sys
 
 import numpy as np
 
-from . import _abi as A
-from ._nontwin import call_args, check_tensor as _check_tensor, checked_lib, host_image, index_list
-from .api import Film
+from . import _abi as A, _firsthit as F
+from ._nontwin import bind, check_tensor as _check_tensor, current_stream, host_image, index_list, ptr, tptr
 
 # resolved channels: name -> slice of the 8 floats ftn_lightpass_resolve writes per pixel
 CHANNELS = {"lit": slice(0, 3), "unshadowed": slice(3, 6), "visibility": slice(6, 7), "coverage": slice(7, 8)}
+PASS = F.FirstHitPass(A.EXTENSIONS["lightpass"], 8, 8,
+                      ("ftn_render_lightpass", "ftn_render_lightpass_device", "ftn_lightpass_resolve", "ftn_lightpass_resolve_device"), CHANNELS)
 KINDS = ("point", "distant", "infinite", "area")          # ftn_scene_get_lights' kinds 0 .. 3
 
 
 def _lib(be):
-    lib = checked_lib(be, "the light-group pass has no oracle twin: the reference has no light AOVs", "light-pass",
-                      "ftn_lightpass_abi_version", A.FTN_LIGHTPASS_ABI_VERSION)
-    for name, (argtypes, restype) in A.LIGHTPASS_PROTOTYPES.items():
-        fn = getattr(lib, name)
-        fn.argtypes, fn.restype = argtypes, restype
-    return lib
+    return bind(be, PASS.ext)
 
 
 def groups(scene, by="kind"):
@@ -56,19 +52,12 @@ def groups(scene, by="kind"):
 
 def resolve(be, raw):
     """ftn_lightpass_resolve: raw [H, W, 8] sums -> dict of resolved [H, W, k] arrays (CHANNELS)."""
-    out = resolve8(be, raw)
-    return {k: out[..., s] for k, s in CHANNELS.items()}
+    return F.channels(PASS, resolve8(be, raw))
 
 
 def resolve8(be, raw):
     """ftn_lightpass_resolve: raw [..., 8] sums -> the resolved [..., 8] floats as one array (what compose takes)."""
-    lib = _lib(be)
-    raw = np.ascontiguousarray(raw, dtype=np.float32)
-    if raw.shape[-1] != 8:
-        raise ValueError("the last dimension holds the 8 floats of a pixel")
-    out = np.empty(raw.shape, np.float32)
-    be.check(lib.ftn_lightpass_resolve(raw.ctypes.data_as(C.c_void_p), raw.size // 8, out.ctypes.data_as(C.c_void_p)))
-    return out
+    return F.resolve_host(PASS, be, raw)
 
 
 def _gains(gains, n_groups):
@@ -88,23 +77,20 @@ def compose(be, gb12, res8, gains):
         raise ValueError("expected res8 [groups, H, W, 8] with the G-buffer's H and W, got %r" % (res8.shape,))
     g = _gains(gains, res8.shape[0])
     out = np.empty(gb12.shape[:2] + (3,), np.float32)
-    be.check(lib.ftn_lightpass_compose(gb12.ctypes.data_as(C.c_void_p), res8.ctypes.data_as(C.c_void_p), res8.shape[0], g.ctypes.data_as(C.c_void_p),
-                                       gb12.shape[0] * gb12.shape[1], out.ctypes.data_as(C.c_void_p)))
+    be.check(lib.ftn_lightpass_compose(ptr(gb12), ptr(res8), res8.shape[0], ptr(g), gb12.shape[0] * gb12.shape[1], ptr(out)))
     return out
 
 
 def compose_torch(be, gb12, res8, gains, out):
     """ftn_lightpass_compose_device: float32 CUDA tensors gb12 [H, W, 12], res8 [groups, H, W, 8] -> out [H, W, 3], current stream; gains
     is a host array [groups, 3]."""
-    import torch
     lib = _lib(be)
     _check_tensor(gb12, tuple(gb12.shape[:2]) + (12,))
     _check_tensor(res8, (res8.shape[0],) + tuple(gb12.shape[:2]) + (8,))
     _check_tensor(out, tuple(gb12.shape[:2]) + (3,))
     g = _gains(gains, res8.shape[0])
-    stream = torch.cuda.current_stream(gb12.device).cuda_stream
-    be.check(lib.ftn_lightpass_compose_device(C.c_void_p(gb12.data_ptr()), C.c_void_p(res8.data_ptr()), res8.shape[0], g.ctypes.data_as(C.c_void_p),
-                                              gb12.shape[0] * gb12.shape[1], C.c_void_p(out.data_ptr()), C.c_void_p(stream)))
+    be.check(lib.ftn_lightpass_compose_device(tptr(gb12), tptr(res8), res8.shape[0], ptr(g),
+                                              gb12.shape[0] * gb12.shape[1], tptr(out), C.c_void_p(current_stream(gb12))))
     return out
 
 
@@ -117,8 +103,7 @@ def terms(be, hit24, light24, group_size):
     if len(hit24) != len(light24):
         raise ValueError("one light sample per interaction record")
     e, rays = np.empty((len(hit24), 3), np.float32), np.empty((len(hit24), 8), np.float32)
-    be.check(lib.ftn_lightpass_terms(hit24.ctypes.data_as(C.c_void_p), light24.ctypes.data_as(C.c_void_p), len(hit24), int(group_size),
-                                     e.ctypes.data_as(C.c_void_p), rays.ctypes.data_as(C.c_void_p)))
+    be.check(lib.ftn_lightpass_terms(ptr(hit24), ptr(light24), len(hit24), int(group_size), ptr(e), ptr(rays)))
     return e, rays
 
 
@@ -127,45 +112,19 @@ def render_lightpass(be, builder, cam, res, sampler, lights=None, tiles=None, cr
     """Shaped like ao.render_ao: create_scene (unless `scene` is given) + Film (unless `film` is given) + ftn_render_lightpass.  `raw`
     ([H, W, 8] float32) is added into when given, else a zero buffer is.  count_traffic: the shadow rays take the reference-order
     traversal instead of the production any-hit kernels.  Returns (resolved dict, raw sums, stats)."""
-    lib = _lib(be)
-    scene = scene or builder.create_scene()
-    film = film or Film(be, res, crop)
-    if raw is None:
-        raw = np.zeros((film.height, film.width, 8), np.float32)
-    if raw.shape != (film.height, film.width, 8) or raw.dtype != np.float32 or not raw.flags.c_contiguous:
-        raise ValueError("raw must be a C-contiguous float32 array of shape %r" % ((film.height, film.width, 8),))
-    args, keep = call_args(cam, film, None, sampler, tiles, pipeline, device, count_traffic)
-    p_lights, n_lights, keep_lights = index_list(lights)
-    st = A.ftn_stats()
-    be.check(lib.ftn_render_lightpass(scene.handle, *args, p_lights, n_lights, raw.ctypes.data_as(C.c_void_p), C.byref(st)))
-    return resolve(be, raw), raw, st.as_dict()
+    raw, st = F.render_host(PASS, be, builder, cam, res, sampler, tiles=tiles, crop=crop, scene=scene, raw=raw, pipeline=pipeline, device=device, film=film,
+                            count_traffic=count_traffic, extra=lambda: index_list(lights))
+    return resolve(be, raw), raw, st
 
 
 def render_lightpass_torch(scene, cam, film, sampler, out, lights=None, tiles=None, pipeline=A.FTN_PIPELINE_AUTO):
     """ftn_render_lightpass_device into `out` (float32 CUDA tensor [H, W, 8], added into) on the current stream of its device."""
-    import torch
-    be = scene.be
-    lib = _lib(be)
-    _check_tensor(out, (film.height, film.width, 8))
-    args, keep = call_args(cam, film, None, sampler, tiles, pipeline, out.device.index)
-    p_lights, n_lights, keep_lights = index_list(lights)
-    st = A.ftn_stats()
-    stream = torch.cuda.current_stream(out.device).cuda_stream
-    be.check(lib.ftn_render_lightpass_device(scene.handle, *args, p_lights, n_lights, C.c_void_p(out.data_ptr()), C.c_void_p(stream), C.byref(st)))
-    return st.as_dict()
+    return F.render_torch(PASS, scene, cam, film, sampler, out, tiles=tiles, pipeline=pipeline, extra=lambda: index_list(lights))
 
 
 def resolve_torch(be, raw, out):
     """ftn_lightpass_resolve_device: raw [..., 8] sums -> out [..., 8] resolved floats, both float32 CUDA tensors, current stream."""
-    import torch
-    lib = _lib(be)
-    _check_tensor(raw, raw.shape)
-    if raw.shape[-1] != 8:
-        raise ValueError("the last dimension holds the 8 floats of a pixel")
-    _check_tensor(out, tuple(raw.shape))
-    stream = torch.cuda.current_stream(raw.device).cuda_stream
-    be.check(lib.ftn_lightpass_resolve_device(C.c_void_p(raw.data_ptr()), raw.numel() // 8, C.c_void_p(out.data_ptr()), C.c_void_p(stream)))
-    return out
+    return F.resolve_torch(PASS, be, raw, out)
 
 
 # ------------------------------------------------------------------ python -m fountain_amd.lightpass relight

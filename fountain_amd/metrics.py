@@ -31,7 +31,7 @@ import sys
 import numpy as np
 
 from . import _abi as A
-from ._nontwin import checked_lib, host_image, params_of, ptr, set_fields
+from ._nontwin import bind, host_image, params_of, ptr, set_fields
 from .api import default_backend
 
 RESULT_FIELDS = tuple(name for name, _ in A.ftn_metrics_result._fields_)
@@ -39,12 +39,7 @@ SUMS = ("SE", "AE", "REL", "SM", "SE_r", "SE_g", "SE_b", "SSIM")
 
 
 def _lib(be):
-    lib = checked_lib(be, "the measuring stage has no oracle twin: the reference compares no images", "metrics",
-                      "ftn_metrics_abi_version", A.FTN_METRICS_ABI_VERSION)
-    for name, (argtypes, restype) in A.METRICS_PROTOTYPES.items():
-        fn = getattr(lib, name)
-        fn.argtypes, fn.restype = argtypes, restype
-    return lib
+    return bind(be, A.EXTENSIONS["metrics"])
 
 
 class MetricsParams:
@@ -146,10 +141,8 @@ def report_line(r, ssim):
 
 def exr_size(path, be):
     """(w, h) of an OpenEXR file: ftn_exr_read with a null buffer; None where it cannot be read."""
-    f = be.lib.ftn_exr_read
-    f.argtypes = [C.c_char_p, C.c_void_p, C.c_void_p, C.c_void_p]
     w, h = C.c_uint32(), C.c_uint32()
-    if f(os.fsencode(path), C.cast(C.byref(w), C.c_void_p), C.cast(C.byref(h), C.c_void_p), None) != 0:
+    if be.lib.ftn_exr_read(os.fsencode(path), C.byref(w), C.byref(h), None) != 0:
         return None
     return w.value, h.value
 

@@ -13,20 +13,14 @@ import ctypes as C
 import numpy as np
 
 from . import _abi as A
-from ._nontwin import call_args as _call_args, check_tensor as _check_tensor, checked_lib
+from ._nontwin import bind, call_args as _call_args, check_array as _check_array, check_tensor as _check_tensor, current_stream, ptr, tptr
 from .api import Film
 
 CHANNELS = ("r", "g", "b", "Y")          # the 4 floats per pixel of the moments and of the resolved variance
 
 
 def _lib(be):
-    return checked_lib(be, "the moments pass has no oracle twin: the reference keeps no second moments", "moments", "ftn_moments_abi_version",
-                       A.FTN_MOMENTS_ABI_VERSION)
-
-
-def _check_array(a, shape, what):
-    if a.shape != shape or a.dtype != np.float32 or not a.flags.c_contiguous:
-        raise ValueError("%s must be a C-contiguous float32 array of shape %r" % (what, shape))
+    return bind(be, A.EXTENSIONS["moments"])
 
 
 def resolve(be, pixels, moments):
@@ -37,8 +31,7 @@ def resolve(be, pixels, moments):
     if pixels.shape != moments.shape or pixels.shape[-1] != 4:
         raise ValueError("pixels and moments must have the same shape [..., 4]")
     out = np.empty(pixels.shape, np.float32)
-    be.check(lib.ftn_moments_resolve(pixels.ctypes.data_as(C.c_void_p), moments.ctypes.data_as(C.c_void_p), C.c_size_t(pixels.size // 4),
-                                     out.ctypes.data_as(C.c_void_p)))
+    be.check(lib.ftn_moments_resolve(ptr(pixels), ptr(moments), pixels.size // 4, ptr(out)))
     return out
 
 
@@ -57,14 +50,13 @@ def render_moments(be, builder, cam, res, integrator, sampler, tiles=None, crop=
     _check_array(film.pixels, shape, "film.pixels")
     args, keep = _call_args(cam, film, integrator, sampler, tiles, pipeline, device, count_traffic)
     st = A.ftn_stats()
-    be.check(lib.ftn_render_moments(scene.handle, *args, film.pixels.ctypes.data_as(C.c_void_p), moments.ctypes.data_as(C.c_void_p), C.byref(st)))
+    be.check(lib.ftn_render_moments(scene.handle, *args, ptr(film.pixels), ptr(moments), C.byref(st)))
     return resolve(be, film.pixels, moments), film, moments, st.as_dict()
 
 
 def render_moments_torch(scene, cam, film, integrator, sampler, pixels, moments, tiles=None, pipeline=A.FTN_PIPELINE_AUTO):
     """ftn_render_moments_device into `pixels` (ftn_pixel) and `moments` (float32 CUDA tensors [H, W, 4], both added into) on the
     current stream of their device."""
-    import torch
     be = scene.be
     lib = _lib(be)
     shape = (film.height, film.width, 4)
@@ -74,21 +66,18 @@ def render_moments_torch(scene, cam, film, integrator, sampler, pixels, moments,
         raise ValueError("pixels and moments must be on the same device")
     args, keep = _call_args(cam, film, integrator, sampler, tiles, pipeline, pixels.device.index)
     st = A.ftn_stats()
-    stream = torch.cuda.current_stream(pixels.device).cuda_stream
-    be.check(lib.ftn_render_moments_device(scene.handle, *args, C.c_void_p(pixels.data_ptr()), C.c_void_p(moments.data_ptr()), C.c_void_p(stream),
-                                           C.byref(st)))
+    be.check(lib.ftn_render_moments_device(scene.handle, *args, tptr(pixels), tptr(moments),
+                                           C.c_void_p(current_stream(pixels)), C.byref(st)))
     return st.as_dict()
 
 
 def resolve_torch(be, pixels, moments, out):
     """ftn_moments_resolve_device: pixels, moments -> out, float32 CUDA tensors [..., 4], on the current stream."""
-    import torch
     lib = _lib(be)
     for t in (pixels, moments, out):
         _check_tensor(t, pixels.shape)
     if pixels.shape[-1] != 4:
         raise ValueError("the last dimension holds the 4 floats of a pixel")
-    stream = torch.cuda.current_stream(pixels.device).cuda_stream
-    be.check(lib.ftn_moments_resolve_device(C.c_void_p(pixels.data_ptr()), C.c_void_p(moments.data_ptr()), C.c_size_t(pixels.numel() // 4),
-                                            C.c_void_p(out.data_ptr()), C.c_void_p(stream)))
+    be.check(lib.ftn_moments_resolve_device(tptr(pixels), tptr(moments), pixels.numel() // 4,
+                                            tptr(out), C.c_void_p(current_stream(pixels))))
     return out

@@ -16,28 +16,17 @@ import ctypes as C
 
 import numpy as np
 
-from . import _abi as A
-from ._nontwin import call_args, check_tensor as _check_tensor, checked_lib, host_image, ptr
-from .api import Film
+from . import _abi as A, _firsthit as F
+from ._nontwin import bind, check_tensor as _check_tensor, current_stream, desc_of as _desc, host_image, ptr, tptr
 
 # mv8 channels: name -> slice of the 8 floats ftn_motion_resolve writes per pixel
 CHANNELS = {"prev_position": slice(0, 3), "prev_normal": slice(3, 6), "coverage": slice(6, 7), "weight": slice(7, 8)}
+PASS = F.FirstHitPass(A.EXTENSIONS["motion"], 8, 8,
+                      ("ftn_render_motion", "ftn_render_motion_device", "ftn_motion_resolve", "ftn_motion_resolve_device"), CHANNELS)
 
 
 def _lib(be):
-    lib = checked_lib(be, "the previous-position pass has no oracle twin: the reference renders single frames", "motion",
-                      "ftn_motion_abi_version", A.FTN_MOTION_ABI_VERSION)
-    for name, (argtypes, restype) in A.MOTION_PROTOTYPES.items():
-        fn = getattr(lib, name)
-        fn.argtypes, fn.restype = argtypes, restype
-    return lib
-
-
-def _desc(obj, typ, what):
-    d = obj if isinstance(obj, typ) else getattr(obj, "desc", None)
-    if not isinstance(d, typ):
-        raise TypeError("%s must be a %s or carry one as .desc" % (what, typ.__name__))
-    return d
+    return bind(be, PASS.ext)
 
 
 def descs_differ(a, b):
@@ -64,13 +53,7 @@ def descs_differ(a, b):
 
 def motion_resolve(be, raw):
     """ftn_motion_resolve: raw [..., 8] sums -> mv8 [..., 8]."""
-    lib = _lib(be)
-    raw = np.ascontiguousarray(raw, dtype=np.float32)
-    if raw.shape[-1] != 8:
-        raise ValueError("the last dimension holds the 8 floats of a pixel")
-    out = np.empty_like(raw)
-    be.check(lib.ftn_motion_resolve(ptr(raw), raw.size // 8, ptr(out)))
-    return out
+    return F.resolve_host(PASS, be, raw)
 
 
 def render_motion(be, builder, cam, res, sampler, tiles=None, crop=(0.0, 0.0, 1.0, 1.0), scene=None, prev_scene=None, raw=None,
@@ -78,45 +61,22 @@ def render_motion(be, builder, cam, res, sampler, tiles=None, crop=(0.0, 0.0, 1.
     """Shaped like gbuffer.render_gbuffer: create_scene (unless `scene` is given) + Film (unless `film` is given) + ftn_render_motion
     against `prev_scene` (required: the previous frame's scene).  `raw` ([H, W, 8] float32) is added into when given, else a zero buffer
     is.  Returns (mv8, raw sums, stats)."""
-    lib = _lib(be)
+    _lib(be)
     if prev_scene is None:
         raise ValueError("render_motion needs prev_scene, the previous frame's scene")
-    scene = scene or builder.create_scene()
-    film = film or Film(be, res, crop)
-    if raw is None:
-        raw = np.zeros((film.height, film.width, 8), np.float32)
-    if raw.shape != (film.height, film.width, 8) or raw.dtype != np.float32 or not raw.flags.c_contiguous:
-        raise ValueError("raw must be a C-contiguous float32 array of shape %r" % ((film.height, film.width, 8),))
-    args, keep = call_args(cam, film, None, sampler, tiles, pipeline, device)
-    st = A.ftn_stats()
-    be.check(lib.ftn_render_motion(scene.handle, prev_scene.handle, *args, ptr(raw), C.byref(st)))
-    return motion_resolve(be, raw), raw, st.as_dict()
+    raw, st = F.render_host(PASS, be, builder, cam, res, sampler, tiles=tiles, crop=crop, scene=scene, raw=raw, pipeline=pipeline, device=device, film=film,
+                            lead=(prev_scene.handle,))
+    return motion_resolve(be, raw), raw, st
 
 
 def render_motion_torch(scene, prev_scene, cam, film, sampler, out, tiles=None, pipeline=A.FTN_PIPELINE_AUTO):
     """ftn_render_motion_device into `out` (float32 CUDA tensor [H, W, 8], added into) on the current stream of its device."""
-    import torch
-    be = scene.be
-    lib = _lib(be)
-    _check_tensor(out, (film.height, film.width, 8))
-    args, keep = call_args(cam, film, None, sampler, tiles, pipeline, out.device.index)
-    st = A.ftn_stats()
-    stream = torch.cuda.current_stream(out.device).cuda_stream
-    be.check(lib.ftn_render_motion_device(scene.handle, prev_scene.handle, *args, C.c_void_p(out.data_ptr()), C.c_void_p(stream), C.byref(st)))
-    return st.as_dict()
+    return F.render_torch(PASS, scene, cam, film, sampler, out, tiles=tiles, pipeline=pipeline, lead=(prev_scene.handle,))
 
 
 def motion_resolve_torch(be, raw, out):
     """ftn_motion_resolve_device: raw [..., 8] sums -> out [..., 8], both float32 CUDA tensors, current stream."""
-    import torch
-    lib = _lib(be)
-    _check_tensor(raw, raw.shape)
-    if raw.shape[-1] != 8:
-        raise ValueError("the last dimension holds the 8 floats of a pixel")
-    _check_tensor(out, tuple(raw.shape))
-    stream = torch.cuda.current_stream(raw.device).cuda_stream
-    be.check(lib.ftn_motion_resolve_device(C.c_void_p(raw.data_ptr()), raw.numel() // 8, C.c_void_p(out.data_ptr()), C.c_void_p(stream)))
-    return out
+    return F.resolve_torch(PASS, be, raw, out)
 
 
 def _host_vectors(be, fn, mv8, gb12, camera, prev_camera, film, tail):
@@ -153,7 +113,6 @@ def motion_vectors_torch(be, mv8, gb12, camera, prev_camera, film, out):
         _check_tensor(t, (h, w, k))
         if t.device != mv8.device:
             raise ValueError("every tensor must live on the device of mv8")
-    stream = torch.cuda.current_stream(mv8.device).cuda_stream
-    be.check(lib.ftn_motion_vectors_device(C.c_void_p(mv8.data_ptr()), C.c_void_p(gb12.data_ptr()), C.byref(cam), C.byref(pcam), C.byref(fd), w, h,
-                                           C.c_void_p(out.data_ptr()), C.c_void_p(stream)))
+    be.check(lib.ftn_motion_vectors_device(tptr(mv8), tptr(gb12), C.byref(cam), C.byref(pcam), C.byref(fd), w, h,
+                                           tptr(out), C.c_void_p(current_stream(mv8))))
     return out

@@ -14,17 +14,13 @@ import ctypes as C
 import numpy as np
 
 from . import _abi as A
-from ._nontwin import checked_lib
+from ._nontwin import bind, ptr as _ptr
 from .api import default_backend
 
 
 def _lib(be):
     be = default_backend() if be is None or be.is_oracle else be
-    lib = checked_lib(be, "", "subdivision", "ftn_subdiv_abi_version", A.FTN_SUBDIV_ABI_VERSION)
-    for name, (argtypes, restype) in A.SUBDIV_PROTOTYPES.items():
-        fn = getattr(lib, name)
-        fn.argtypes, fn.restype = argtypes, restype
-    return be, lib
+    return be, bind(be, A.EXTENSIONS["subdiv"])
 
 
 def _cage(P, idx):
@@ -33,10 +29,6 @@ def _cage(P, idx):
     if P.ndim != 2 or P.shape[1] != 3 or idx.ndim != 2 or idx.shape[1] != 3:
         raise ValueError("expected P [n, 3] and indices [m, 3], got %r and %r" % (P.shape, idx.shape))
     return P, idx
-
-
-def _ptr(a):
-    return a.ctypes.data_as(C.c_void_p)
 
 
 def info(be, idx, n_vertices, levels):

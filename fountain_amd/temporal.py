@@ -34,12 +34,11 @@ import sys
 import numpy as np
 
 from . import _abi as A
-from ._nontwin import check_tensor, checked_lib, host_image, params_of, ptr
+from ._nontwin import bind, check_tensor, current_stream, desc_of as _desc, host_image, params_of, ptr, tptr
 
 
 def _lib(be):
-    return checked_lib(be, "temporal accumulation has no oracle twin: the reference renders single frames", "temporal", "ftn_temporal_abi_version",
-                       A.FTN_TEMPORAL_ABI_VERSION)
+    return bind(be, A.EXTENSIONS["temporal"])
 
 
 def _params(be, params):
@@ -49,13 +48,6 @@ def _params(be, params):
 def temporal_params(be, **fields):
     """ftn_temporal_params_default, then the given fields."""
     return _params(be, fields)
-
-
-def _desc(obj, typ, what):
-    d = obj if isinstance(obj, typ) else getattr(obj, "desc", None)
-    if not isinstance(d, typ):
-        raise TypeError("%s must be a %s or carry one as .desc" % (what, typ.__name__))
-    return d
 
 
 def _prev(prev):
@@ -85,8 +77,7 @@ def _host_frame(rgb, gb12, var4, prev):
 
 
 def _motion_lib(be):
-    from .motion import _lib as motion_lib
-    return motion_lib(be)
+    return bind(be, A.EXTENSIONS["motion"])
 
 
 def _host_call(be, fn, rgb, gb12, var4, camera, film, prev, params, tail, motion=None):
@@ -97,23 +88,21 @@ def _host_call(be, fn, rgb, gb12, var4, camera, film, prev, params, tail, motion
     hist, out, ovar = np.empty((h, w, 8), np.float32), np.empty_like(rgb), np.empty_like(var4)
     pc, pg, ph = (C.byref(prev[0]), ptr(prev[1]), ptr(prev[2])) if prev is not None else (None, None, None)
     if motion is None:
-        be.check(fn(ptr(rgb), ptr(gb12), ptr(var4), C.byref(cam), C.byref(fd), C.c_int32(w), C.c_int32(h), pc, pg, ph, C.byref(p),
-                    ptr(hist), ptr(out), ptr(ovar), *tail))
+        be.check(fn(ptr(rgb), ptr(gb12), ptr(var4), C.byref(cam), C.byref(fd), w, h, pc, pg, ph, C.byref(p), ptr(hist), ptr(out), ptr(ovar), *tail))
         return hist, out, ovar
     try:
         mv8 = host_image(motion, 8, rgb.shape[:2])
     except ValueError:
         raise ValueError("expected motion (mv8) %r, got %r" % (rgb.shape[:2] + (8,), np.shape(motion))) from None
     fn = getattr(_motion_lib(be), fn.__name__.replace("ftn_temporal_accumulate", "ftn_temporal_accumulate_motion"))
-    be.check(fn(ptr(rgb), ptr(gb12), ptr(var4), ptr(mv8), C.byref(cam), C.byref(fd), w, h, pc, pg, ph, C.byref(p), ptr(hist), ptr(out), ptr(ovar),
-                *(t.value for t in tail)))
+    be.check(fn(ptr(rgb), ptr(gb12), ptr(var4), ptr(mv8), C.byref(cam), C.byref(fd), w, h, pc, pg, ph, C.byref(p), ptr(hist), ptr(out), ptr(ovar), *tail))
     return hist, out, ovar
 
 
 def temporal_accumulate(be, rgb, gb12, var4, camera, film, prev=None, params=None, device=-1, motion=None):
     """ftn_temporal_accumulate (with `motion`, the frame's mv8: ftn_temporal_accumulate_motion): host arrays, accumulated on GPU `device`
     (-1 = the current one); returns (history, rgb, var4)."""
-    return _host_call(be, _lib(be).ftn_temporal_accumulate, rgb, gb12, var4, camera, film, prev, params, (C.c_int32(device),), motion)
+    return _host_call(be, _lib(be).ftn_temporal_accumulate, rgb, gb12, var4, camera, film, prev, params, (device,), motion)
 
 
 def temporal_accumulate_cpu(be, rgb, gb12, var4, camera, film, prev=None, params=None, motion=None):
@@ -143,18 +132,14 @@ def temporal_accumulate_torch(be, rgb, gb12, var4, camera, film, out_history, ou
         check_tensor(t, (h, w, k))
         if t.device != rgb.device:
             raise ValueError("every tensor must live on the device of rgb")
-    pc, pg, ph = (C.byref(_desc(prev[0], A.ftn_camera_desc, "the previous camera")), C.c_void_p(prev[1].data_ptr()), C.c_void_p(prev[2].data_ptr())) \
+    pc, pg, ph = (C.byref(_desc(prev[0], A.ftn_camera_desc, "the previous camera")), tptr(prev[1]), tptr(prev[2])) \
         if prev is not None else (None, None, None)
-    stream = torch.cuda.current_stream(rgb.device).cuda_stream
+    dp = lambda t: tptr(t)
+    rest = (C.byref(cam), C.byref(fd), w, h, pc, pg, ph, C.byref(p), tptr(out_history), tptr(out_rgb), tptr(out_var4), C.c_void_p(current_stream(rgb)))
     if motion is not None:
-        be.check(_motion_lib(be).ftn_temporal_accumulate_motion_device(
-            C.c_void_p(rgb.data_ptr()), C.c_void_p(gb12.data_ptr()), C.c_void_p(var4.data_ptr()), C.c_void_p(motion.data_ptr()), C.byref(cam), C.byref(fd),
-            w, h, pc, pg, ph, C.byref(p), C.c_void_p(out_history.data_ptr()), C.c_void_p(out_rgb.data_ptr()), C.c_void_p(out_var4.data_ptr()),
-            C.c_void_p(stream)))
-        return out_history, out_rgb, out_var4
-    be.check(lib.ftn_temporal_accumulate_device(C.c_void_p(rgb.data_ptr()), C.c_void_p(gb12.data_ptr()), C.c_void_p(var4.data_ptr()), C.byref(cam),
-                                                C.byref(fd), C.c_int32(w), C.c_int32(h), pc, pg, ph, C.byref(p), C.c_void_p(out_history.data_ptr()),
-                                                C.c_void_p(out_rgb.data_ptr()), C.c_void_p(out_var4.data_ptr()), C.c_void_p(stream)))
+        be.check(_motion_lib(be).ftn_temporal_accumulate_motion_device(tptr(rgb), tptr(gb12), tptr(var4), tptr(motion), *rest))
+    else:
+        be.check(lib.ftn_temporal_accumulate_device(tptr(rgb), tptr(gb12), tptr(var4), *rest))
     return out_history, out_rgb, out_var4
 
 

@@ -29,19 +29,14 @@ import sys
 import numpy as np
 
 from . import _abi as A
-from ._nontwin import check_tensor, check_workspace, checked_lib, host_image, params_of, ptr, set_fields
+from ._nontwin import bind, check_tensor, check_workspace, host_image, params_of, ptr, set_fields, tptr
 from .api import default_backend
 
 TILE = A.FTN_VECTORBLUR_MAX_RADIUS
 
 
 def _lib(be):
-    lib = checked_lib(be, "the vector-blur stage has no oracle twin: the reference renders single frames without a shutter", "vector-blur",
-                      "ftn_vectorblur_abi_version", A.FTN_VECTORBLUR_ABI_VERSION)
-    for name, (argtypes, restype) in A.VECTORBLUR_PROTOTYPES.items():
-        fn = getattr(lib, name)
-        fn.argtypes, fn.restype = argtypes, restype
-    return lib
+    return bind(be, A.EXTENSIONS["vectorblur"])
 
 
 class VectorBlurParams:
@@ -128,8 +123,7 @@ def vector_blur_device(be, rgb, motion, gb12, out_rgb, workspace, stream=None, p
             raise ValueError("every tensor must live on the device of rgb")
     check_workspace(workspace, workspace_size(be, w, h), rgb.device)
     s = (torch.cuda.current_stream(rgb.device) if stream is None else stream).cuda_stream
-    be.check(_lib(be).ftn_vectorblur_device(C.c_void_p(rgb.data_ptr()), C.c_void_p(motion.data_ptr()), C.c_void_p(gb12.data_ptr()) if gb12 is not None else None,
-                                            w, h, C.byref(p), C.c_void_p(out_rgb.data_ptr()), C.c_void_p(workspace.data_ptr()), C.c_void_p(s)))
+    be.check(_lib(be).ftn_vectorblur_device(tptr(rgb), tptr(motion), tptr(gb12), w, h, C.byref(p), tptr(out_rgb), tptr(workspace), C.c_void_p(s)))
     return out_rgb
 
 
