@@ -61,7 +61,7 @@ class Backend:
     def check(self, rc):
         if rc != 0:
             msg = self.fn("last_error")()
-            raise FountainError(rc, msg.decode() if msg else "")
+            raise FountainError(rc, msg.decode(errors="replace") if msg else "")
 
     def call(self, name, *args):
         self.check(self.fn(name)(*args))
@@ -617,10 +617,10 @@ class PbrtScene:
         self.handle = C.c_void_p()
         rc = be.lib.ftn_pbrt_load(os.fsencode(path), C.byref(self.handle))
         if rc != 0:
-            raise FountainError(rc, be.lib.ftn_pbrt_last_error().decode())
+            raise FountainError(rc, be.lib.ftn_pbrt_last_error().decode(errors="replace"))      # a message may quote bytes of the file
         self.desc = be.lib.ftn_pbrt_scene(self.handle).contents
         self.samples_per_pixel = be.lib.ftn_pbrt_samples_per_pixel(self.handle)
-        self.film_name = be.lib.ftn_pbrt_film_name(self.handle).decode()
+        self.film_name = be.lib.ftn_pbrt_film_name(self.handle).decode(errors="replace")
         self.camera = PerspectiveCamera.__new__(PerspectiveCamera)
         self.camera.be = be
         self.camera.desc = be.lib.ftn_pbrt_camera(self.handle).contents
@@ -654,7 +654,7 @@ def load_ply(path, backend=None):
     def call(*arrs):
         rc = be.lib.ftn_ply_load(os.fsencode(path), C.byref(nv), C.byref(nt), *arrs, C.byref(hn), C.byref(huv))
         if rc != 0:
-            raise FountainError(rc, be.lib.ftn_pbrt_last_error().decode())
+            raise FountainError(rc, be.lib.ftn_pbrt_last_error().decode(errors="replace"))      # a message may quote bytes of the file
     call(None, None, None, None)
     P = np.empty((nv.value, 3), np.float32)
     N = np.empty((nv.value, 3), np.float32)
@@ -843,7 +843,7 @@ class Film:
 
 
 def _io_error(be, rc):
-    return FountainError(rc, be.lib.ftn_imageio_last_error().decode())
+    return FountainError(rc, be.lib.ftn_imageio_last_error().decode(errors="replace"))
 
 
 def write_exr(path, rgb, backend=None):

@@ -14,6 +14,8 @@
 #include <cstdio>
 #include <zlib.h>
 #include <cstring>
+#include <new>
+#include <stdexcept>
 #include <string>
 #include <vector>
 
@@ -56,6 +58,7 @@ bool rle_decode(const unsigned char* in, size_t n_in, std::vector<unsigned char>
         const int c = (signed char)in[p++];
         if (c < 0) { const size_t k = (size_t)(-c); if (p + k > n_in) return false; tmp.insert(tmp.end(), in + p, in + p + k); p += k; }
         else { if (p >= n_in) return false; tmp.insert(tmp.end(), (size_t)c + 1, in[p]); p++; }
+        if (tmp.size() > n_out) return false;
     }
     if (tmp.size() != n_out) return false;
     unpredict(tmp, out);
@@ -69,6 +72,146 @@ bool zip_decode(const unsigned char* in, size_t n_in, std::vector<unsigned char>
     return true;
 }
 
+/* nothing unwinds across the C boundary: a failed allocation (or a size no allocation can have) is FTN_ERR_OUT_OF_MEMORY, anything
+ * else FTN_ERR_INTERNAL; the locals of the call, an open file among them, are released on the way */
+template <class F> int guarded(F&& f) {
+    try { return f(); }
+    catch (const std::bad_alloc&) { return io_fail(FTN_ERR_OUT_OF_MEMORY, "out of memory"); }
+    catch (const std::length_error&) { return io_fail(FTN_ERR_OUT_OF_MEMORY, "out of memory (a size no allocation can have)"); }
+    catch (const std::exception& e) { return io_fail(FTN_ERR_INTERNAL, e.what()); }
+}
+struct File {
+    FILE* f;
+    explicit File(FILE* f_) : f(f_) {}
+    ~File() { if (f) fclose(f); }
+    int close() { FILE* g = f; f = nullptr; return g ? fclose(g) : 0; }
+    File(const File&) = delete; File& operator=(const File&) = delete;
+};
+
+/* The one way the reader looks at a file's bytes: every read names the bytes it needs and fails when they are not there, so no
+ * length, count or string found in the file can move a read past the end of what the file (or one attribute of it) holds. */
+struct Cursor {
+    const unsigned char* b; size_t n, p;
+    size_t left() const { return n - p; }
+    bool bytes(size_t k, const unsigned char** out) { if (k > left()) return false; *out = b + p; p += k; return true; }
+    bool i32(int32_t* v) { const unsigned char* s; if (!bytes(4, &s)) return false; memcpy(v, s, 4); return true; }
+    bool u64(uint64_t* v) { const unsigned char* s; if (!bytes(8, &s)) return false; memcpy(v, s, 8); return true; }
+    bool cstr(std::string* s) {
+        const unsigned char* e = left() ? (const unsigned char*)memchr(b + p, 0, left()) : nullptr;
+        if (!e) return false;
+        s->assign((const char*)(b + p), (size_t)(e - (b + p))); p = (size_t)(e - b) + 1; return true;
+    }
+};
+
+/* The most pixels a file may declare (include/fountain_hip.h): 2^28, a 3 GiB RGB float image.  The data window of a corrupt file
+ * is any pair of int32 corners; without a cap the caller of the sizing call is told to allocate up to 2^64 pixels. */
+const uint64_t EXR_MAX_PIXELS = (uint64_t)1 << 28;
+/* deflate cannot shrink below 1 : 1032 and OpenEXR's RLE not below 1 : 64: a block that claims more is corrupt, and is refused
+ * before anything of the claimed size is allocated */
+const uint64_t EXR_MAX_RATIO = 1040;
+
+int exr_read(const char* path, uint32_t* w_out, uint32_t* h_out, float* rgb_out) {
+    if (!path) return io_fail(FTN_ERR_INVALID_ARGUMENT, "ftn_exr_read: bad arguments");
+    std::vector<unsigned char> buf;
+    {
+        File f(fopen(path, "rb"));
+        if (!f.f) return io_fail(FTN_ERR_INVALID_ARGUMENT, std::string("cannot open ") + path);
+        unsigned char tmp[65536]; size_t n; while ((n = fread(tmp, 1, sizeof(tmp), f.f)) > 0) buf.insert(buf.end(), tmp, tmp + n);
+    }
+    if (buf.size() < 8 || buf[0] != 0x76 || buf[1] != 0x2f || buf[2] != 0x31 || buf[3] != 0x01) return io_fail(FTN_ERR_INVALID_ARGUMENT, std::string(path) + ": not an OpenEXR file");
+    if (buf[5] & 0x1a) return io_fail(FTN_ERR_UNSUPPORTED, "tiled / deep / multi-part OpenEXR files are not supported");
+    if (buf[4] != 2 || (buf[5] & ~0x04) || buf[6] || buf[7]) return io_fail(FTN_ERR_INVALID_ARGUMENT, "OpenEXR version field is not version 2 with known flags");
+    Cursor c{buf.data(), buf.size(), 8};
+    struct Chan { std::string name; int type; };
+    std::vector<Chan> chans; int compression = -1; int32_t dw[4] = {0, 0, -1, -1};
+    /* the attributes every OpenEXR header has, each of its type and size (the four that say nothing about the pixels are only looked at
+     * that far): a file without one of them was not written as OpenEXR, or is no longer what was written */
+    static const struct { const char* name; const char* type; int32_t size; } required[] = {
+        {"channels", "chlist", -1}, {"compression", "compression", 1}, {"dataWindow", "box2i", 16}, {"displayWindow", "box2i", 16}, {"lineOrder", "lineOrder", 1},
+        {"pixelAspectRatio", "float", 4}, {"screenWindowCenter", "v2f", 8}, {"screenWindowWidth", "float", 4}};
+    unsigned have = 0;
+    for (;;) {
+        std::string name, type; int32_t size; const unsigned char* a;
+        if (!c.cstr(&name)) return io_fail(FTN_ERR_INVALID_ARGUMENT, "truncated OpenEXR header");
+        if (name.empty()) break;
+        if (!c.cstr(&type) || !c.i32(&size) || size < 0 || !c.bytes((size_t)size, &a)) return io_fail(FTN_ERR_INVALID_ARGUMENT, "truncated OpenEXR header");
+        Cursor at{a, (size_t)size, 0};                         /* an attribute is read through its own size, never past it */
+        for (unsigned k = 0; k < 8; k++) if (name == required[k].name) {
+            if (type != required[k].type || (required[k].size >= 0 && size != required[k].size) || (have & (1u << k)))
+                return io_fail(FTN_ERR_INVALID_ARGUMENT, "OpenEXR attribute " + name + " has the wrong type or size, or is given twice");
+            have |= 1u << k;
+        }
+        if (name == "channels") {
+            for (;;) {
+                Chan ch; int32_t t, sampling[2]; const unsigned char* lin;
+                if (!at.cstr(&ch.name)) return io_fail(FTN_ERR_INVALID_ARGUMENT, "corrupt OpenEXR channel list");
+                if (ch.name.empty()) break;
+                if (!at.i32(&t) || !at.bytes(4, &lin) || !at.i32(&sampling[0]) || !at.i32(&sampling[1]) || lin[0] > 1 || lin[1] || lin[2] || lin[3])
+                    return io_fail(FTN_ERR_INVALID_ARGUMENT, "corrupt OpenEXR channel list");
+                if (sampling[0] != 1 || sampling[1] != 1) return io_fail(FTN_ERR_UNSUPPORTED, "subsampled OpenEXR channels are not supported");
+                ch.type = t; chans.push_back(ch);
+            }
+            if (at.left()) return io_fail(FTN_ERR_INVALID_ARGUMENT, "corrupt OpenEXR channel list");
+        } else if (name == "compression") compression = a[0];
+        else if (name == "dataWindow") memcpy(dw, a, 16);
+        else if (name == "lineOrder") { if (a[0] > 1) return io_fail(FTN_ERR_INVALID_ARGUMENT, "OpenEXR scanline files are stored in increasing or decreasing y"); }   /* every block carries its own y */
+        else if (name == "displayWindow") { int32_t d[4]; memcpy(d, a, 16); if (d[2] < d[0] || d[3] < d[1]) return io_fail(FTN_ERR_INVALID_ARGUMENT, "OpenEXR displayWindow is empty"); }
+    }
+    for (unsigned k = 0; k < 8; k++) if (!(have & (1u << k))) return io_fail(FTN_ERR_INVALID_ARGUMENT, std::string("OpenEXR header has no ") + required[k].name + " attribute");
+    const int64_t w = (int64_t)dw[2] - dw[0] + 1, h = (int64_t)dw[3] - dw[1] + 1;
+    if (w <= 0 || h <= 0) return io_fail(FTN_ERR_INVALID_ARGUMENT, "OpenEXR file has no dataWindow");
+    if (compression < 0 || compression > 3) return io_fail(FTN_ERR_UNSUPPORTED, "only NO_COMPRESSION, RLE, ZIPS and ZIP OpenEXR scanline files are supported (not PIZ / PXR24 / B44 / DWA)");
+    if (w > (int64_t)0xffffffff || h > (int64_t)0xffffffff || (uint64_t)w > EXR_MAX_PIXELS / (uint64_t)h)
+        return io_fail(FTN_ERR_INVALID_ARGUMENT, "OpenEXR dataWindow holds more than 2^28 pixels");
+    const uint64_t lines_per_block = compression == 3 ? 16 : 1;
+    int ci[3] = {-1, -1, -1}; uint64_t row_bytes = 0; std::vector<uint64_t> ch_off(chans.size());
+    for (size_t k = 0; k < chans.size(); k++) {
+        ch_off[k] = row_bytes;
+        if (chans[k].type != 1 && chans[k].type != 2) return io_fail(FTN_ERR_UNSUPPORTED, "UINT OpenEXR channels are not supported");   /* read_exr panics */
+        row_bytes += (uint64_t)w * (chans[k].type == 2 ? 4 : 2);            /* w <= 2^28 and a channel costs 18 bytes of file: no overflow */
+        if (chans[k].name == "R") ci[0] = (int)k; else if (chans[k].name == "G") ci[1] = (int)k; else if (chans[k].name == "B") ci[2] = (int)k;
+    }
+    if (ci[0] < 0 || ci[1] < 0 || ci[2] < 0) return io_fail(FTN_ERR_INVALID_ARGUMENT, "OpenEXR file lacks R, G or B");
+    /* the offset table and every block header are checked by the sizing call as well: a size it reports belongs to a file whose blocks
+     * lie inside the file and cover every scanline of the window exactly once */
+    const uint64_t n_blocks = ((uint64_t)h + lines_per_block - 1) / lines_per_block;
+    if (n_blocks > c.left() / 8) return io_fail(FTN_ERR_INVALID_ARGUMENT, "truncated OpenEXR offset table");
+    std::vector<unsigned char> raw, seen((size_t)n_blocks, 0);
+    for (uint64_t b = 0; b < n_blocks; b++) {
+        uint64_t off; c.u64(&off);
+        if (off > buf.size() || buf.size() - off < 8) return io_fail(FTN_ERR_INVALID_ARGUMENT, "truncated OpenEXR scanline");
+        Cursor blk{buf.data(), buf.size(), (size_t)off};
+        int32_t y, n; const unsigned char* data;
+        blk.i32(&y); blk.i32(&n);
+        const int64_t rel = (int64_t)y - dw[1];
+        if (n < 0 || !blk.bytes((size_t)n, &data) || rel < 0 || rel >= h || (uint64_t)rel % lines_per_block) return io_fail(FTN_ERR_INVALID_ARGUMENT, "corrupt OpenEXR scanline");
+        if (seen[(size_t)((uint64_t)rel / lines_per_block)]++) return io_fail(FTN_ERR_INVALID_ARGUMENT, "OpenEXR scanline stored twice (and another one never)");
+        const uint64_t lines = std::min<uint64_t>(lines_per_block, (uint64_t)(h - rel));
+        const uint64_t raw_bytes = row_bytes * lines;
+        const bool packed = compression != 0 && (uint64_t)n < raw_bytes;          /* a block that does not shrink is stored raw */
+        if (packed) { if (raw_bytes > ((uint64_t)n + 16) * EXR_MAX_RATIO) return io_fail(FTN_ERR_INVALID_ARGUMENT, "corrupt compressed OpenEXR block"); }
+        else if ((uint64_t)n != raw_bytes) return io_fail(FTN_ERR_INVALID_ARGUMENT, "unexpected OpenEXR block size");
+        if (!rgb_out) continue;
+        if (packed) {
+            const bool ok = compression == 1 ? rle_decode(data, (size_t)n, raw, (size_t)raw_bytes) : zip_decode(data, (size_t)n, raw, (size_t)raw_bytes);
+            if (!ok) return io_fail(FTN_ERR_INVALID_ARGUMENT, "corrupt compressed OpenEXR block");
+            data = raw.data();
+        }
+        for (uint64_t ly = 0; ly < lines; ly++) {
+            float* dst = rgb_out + ((size_t)rel + (size_t)ly) * (size_t)w * 3;
+            for (int k = 0; k < 3; k++) {
+                const unsigned char* src = data + (size_t)(ly * row_bytes + ch_off[ci[k]]);
+                if (chans[ci[k]].type == 2) for (int64_t x = 0; x < w; x++) memcpy(&dst[3 * x + k], src + 4 * x, 4);
+                else for (int64_t x = 0; x < w; x++) { uint16_t hv; memcpy(&hv, src + 2 * x, 2); dst[3 * x + k] = half_to_float(hv); }
+            }
+        }
+    }
+    /* n_blocks distinct blocks, each on its own multiple of lines_per_block inside the window: every scanline was written once */
+    if (w_out) *w_out = (uint32_t)w;
+    if (h_out) *h_out = (uint32_t)h;
+    return FTN_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -76,7 +219,7 @@ extern "C" {
 const char* ftn_imageio_last_error(void) { return g_io_err.c_str(); }
 
 /* write_exr (src/imageio/exr.rs:47-87): rgb = 3 floats per pixel, row-major, w*h pixels */
-int ftn_exr_write(const char* path, const float* rgb, uint32_t w, uint32_t h) {
+static int exr_write(const char* path, const float* rgb, uint32_t w, uint32_t h) {
     if (!path || !rgb || w == 0 || h == 0) return io_fail(FTN_ERR_INVALID_ARGUMENT, "ftn_exr_write: bad arguments");
     std::vector<unsigned char> hd;
     const unsigned char magic[8] = {0x76, 0x2f, 0x31, 0x01, 2, 0, 0, 0};
@@ -96,26 +239,29 @@ int ftn_exr_write(const char* path, const float* rgb, uint32_t w, uint32_t h) {
     d.clear(); put_f32(d, 0.0f); put_f32(d, 0.0f); put_attr(hd, "screenWindowCenter", "v2f", d);
     d.clear(); put_f32(d, 1.0f); put_attr(hd, "screenWindowWidth", "float", d);
     hd.push_back(0);
-    FILE* f = fopen(path, "wb");
-    if (!f) return io_fail(FTN_ERR_INVALID_ARGUMENT, std::string("cannot create ") + path);
     const size_t row_bytes = (size_t)w * 12, block = 8 + row_bytes;
     std::vector<uint64_t> offs(h);
     for (uint32_t y = 0; y < h; y++) offs[y] = hd.size() + (size_t)h * 8 + (size_t)y * block;
-    bool ok = fwrite(hd.data(), 1, hd.size(), f) == hd.size() && fwrite(offs.data(), 8, h, f) == h;
     std::vector<float> row((size_t)w * 3);
+    File file(fopen(path, "wb")); FILE* f = file.f;
+    if (!f) return io_fail(FTN_ERR_INVALID_ARGUMENT, std::string("cannot create ") + path);
+    bool ok = fwrite(hd.data(), 1, hd.size(), f) == hd.size() && fwrite(offs.data(), 8, h, f) == h;
     for (uint32_t y = 0; y < h && ok; y++) {
         const float* src = rgb + (size_t)y * w * 3;
         for (uint32_t x = 0; x < w; x++) { row[x] = src[3 * x + 2]; row[w + x] = src[3 * x + 1]; row[2 * (size_t)w + x] = src[3 * x]; }
         const int32_t hdr2[2] = {(int32_t)y, (int32_t)row_bytes};
         ok = fwrite(hdr2, 4, 2, f) == 2 && fwrite(row.data(), 4, row.size(), f) == row.size();
     }
-    ok = (fclose(f) == 0) && ok;
+    ok = (file.close() == 0) && ok;
     return ok ? FTN_OK : io_fail(FTN_ERR_INTERNAL, std::string("short write to ") + path);
+}
+int ftn_exr_write(const char* path, const float* rgb, uint32_t w, uint32_t h) {
+    return guarded([&] { return exr_write(path, rgb, w, h); });
 }
 
 /* include/fountain_hip_idmatte.h: any number of named FLOAT channels and string attributes (the Cryptomatte layers of idmatte.py) */
-int ftn_exr_write_channels(const char* path, int32_t w, int32_t h, int32_t n_channels, const char* const* names, const float* const* planes,
-                           int32_t n_attrs, const char* const* attr_names, const char* const* attr_values) {
+static int exr_write_channels(const char* path, int32_t w, int32_t h, int32_t n_channels, const char* const* names, const float* const* planes,
+                              int32_t n_attrs, const char* const* attr_names, const char* const* attr_values) {
     if (!path || !names || !planes || w <= 0 || h <= 0 || n_channels <= 0 || n_attrs < 0 || (n_attrs > 0 && (!attr_names || !attr_values)))
         return io_fail(FTN_ERR_INVALID_ARGUMENT, "ftn_exr_write_channels: bad arguments");
     std::vector<int32_t> order((size_t)n_channels);
@@ -154,92 +300,28 @@ int ftn_exr_write_channels(const char* path, int32_t w, int32_t h, int32_t n_cha
     d.clear(); put_f32(d, 1.0f); put_attr(hd, "screenWindowWidth", "float", d);
     for (int32_t a = 0; a < n_attrs; a++) { d.assign(attr_values[a], attr_values[a] + strlen(attr_values[a])); put_attr(hd, attr_names[a], "string", d); }
     hd.push_back(0);
-    FILE* f = fopen(path, "wb");
-    if (!f) return io_fail(FTN_ERR_INVALID_ARGUMENT, std::string("cannot create ") + path);
     const size_t block = 8 + row_bytes;
     std::vector<uint64_t> offs((size_t)h);
     for (int32_t y = 0; y < h; y++) offs[(size_t)y] = hd.size() + (size_t)h * 8 + (size_t)y * block;
+    File file(fopen(path, "wb")); FILE* f = file.f;
+    if (!f) return io_fail(FTN_ERR_INVALID_ARGUMENT, std::string("cannot create ") + path);
     bool ok = fwrite(hd.data(), 1, hd.size(), f) == hd.size() && fwrite(offs.data(), 8, (size_t)h, f) == (size_t)h;
     for (int32_t y = 0; y < h && ok; y++) {
         const int32_t hdr2[2] = {y, (int32_t)row_bytes};
         ok = fwrite(hdr2, 4, 2, f) == 2;
         for (size_t c = 0; c < order.size() && ok; c++) ok = fwrite(planes[order[c]] + (size_t)y * (size_t)w, 4, (size_t)w, f) == (size_t)w;
     }
-    ok = (fclose(f) == 0) && ok;
+    ok = (file.close() == 0) && ok;
     return ok ? FTN_OK : io_fail(FTN_ERR_INTERNAL, std::string("short write to ") + path);
+}
+int ftn_exr_write_channels(const char* path, int32_t w, int32_t h, int32_t n_channels, const char* const* names, const float* const* planes,
+                           int32_t n_attrs, const char* const* attr_names, const char* const* attr_values) {
+    return guarded([&] { return exr_write_channels(path, w, h, n_channels, names, planes, n_attrs, attr_names, attr_values); });
 }
 
 /* read_exr (src/imageio/exr.rs:11-45): first call with rgb_out == NULL for the size */
 int ftn_exr_read(const char* path, uint32_t* w_out, uint32_t* h_out, float* rgb_out) {
-    if (!path) return io_fail(FTN_ERR_INVALID_ARGUMENT, "ftn_exr_read: bad arguments");
-    FILE* f = fopen(path, "rb");
-    if (!f) return io_fail(FTN_ERR_INVALID_ARGUMENT, std::string("cannot open ") + path);
-    std::vector<unsigned char> buf;
-    { unsigned char tmp[65536]; size_t n; while ((n = fread(tmp, 1, sizeof(tmp), f)) > 0) buf.insert(buf.end(), tmp, tmp + n); }
-    fclose(f);
-    if (buf.size() < 8 || buf[0] != 0x76 || buf[1] != 0x2f || buf[2] != 0x31 || buf[3] != 0x01) return io_fail(FTN_ERR_INVALID_ARGUMENT, std::string(path) + ": not an OpenEXR file");
-    if (buf[5] & 0x1a) return io_fail(FTN_ERR_UNSUPPORTED, "tiled / deep / multi-part OpenEXR files are not supported");
-    size_t p = 8;
-    struct Chan { std::string name; int type; };
-    std::vector<Chan> chans; int compression = -1, line_order = 0; int32_t dw[4] = {0, 0, -1, -1};
-    auto cstr = [&](std::string* s) { size_t e = p; while (e < buf.size() && buf[e]) e++; if (e >= buf.size()) return false; s->assign((const char*)&buf[p], e - p); p = e + 1; return true; };
-    for (;;) {
-        std::string name, type;
-        if (!cstr(&name)) return io_fail(FTN_ERR_INVALID_ARGUMENT, "truncated OpenEXR header");
-        if (name.empty()) break;
-        if (!cstr(&type) || p + 4 > buf.size()) return io_fail(FTN_ERR_INVALID_ARGUMENT, "truncated OpenEXR header");
-        int32_t size; memcpy(&size, &buf[p], 4); p += 4;
-        if (size < 0 || p + (size_t)size > buf.size()) return io_fail(FTN_ERR_INVALID_ARGUMENT, "truncated OpenEXR header");
-        const size_t a = p; p += (size_t)size;
-        if (name == "channels") {
-            size_t q = a;
-            while (q < a + size && buf[q]) { Chan c; while (buf[q]) c.name.push_back((char)buf[q++]); q++; int32_t t; memcpy(&t, &buf[q], 4); c.type = t; q += 16; chans.push_back(c); }
-        } else if (name == "compression") compression = buf[a];
-        else if (name == "dataWindow") memcpy(dw, &buf[a], 16);
-        else if (name == "lineOrder") line_order = buf[a];
-    }
-    const int64_t w = (int64_t)dw[2] - dw[0] + 1, h = (int64_t)dw[3] - dw[1] + 1;
-    if (w <= 0 || h <= 0) return io_fail(FTN_ERR_INVALID_ARGUMENT, "OpenEXR file has no dataWindow");
-    if (compression < 0 || compression > 3) return io_fail(FTN_ERR_UNSUPPORTED, "only NO_COMPRESSION, RLE, ZIPS and ZIP OpenEXR scanline files are supported (not PIZ / PXR24 / B44 / DWA)");
-    const int64_t lines_per_block = compression == 3 ? 16 : 1;
-    if (w_out) *w_out = (uint32_t)w;
-    if (h_out) *h_out = (uint32_t)h;
-    if (!rgb_out) return FTN_OK;
-    int ci[3] = {-1, -1, -1}; size_t row_bytes = 0; std::vector<size_t> ch_off(chans.size());
-    for (size_t c = 0; c < chans.size(); c++) {
-        ch_off[c] = row_bytes;
-        if (chans[c].type != 1 && chans[c].type != 2) return io_fail(FTN_ERR_UNSUPPORTED, "UINT OpenEXR channels are not supported");   /* read_exr panics */
-        row_bytes += (size_t)w * (chans[c].type == 2 ? 4 : 2);
-        if (chans[c].name == "R") ci[0] = (int)c; else if (chans[c].name == "G") ci[1] = (int)c; else if (chans[c].name == "B") ci[2] = (int)c;
-    }
-    if (ci[0] < 0 || ci[1] < 0 || ci[2] < 0) return io_fail(FTN_ERR_INVALID_ARGUMENT, "OpenEXR file lacks R, G or B");
-    (void)line_order;                                       /* every block carries its own y */
-    std::vector<unsigned char> raw;
-    const int64_t n_blocks = (h + lines_per_block - 1) / lines_per_block;
-    if (p + (size_t)n_blocks * 8 > buf.size()) return io_fail(FTN_ERR_INVALID_ARGUMENT, "truncated OpenEXR offset table");
-    for (int64_t b = 0; b < n_blocks; b++) {
-        uint64_t off; memcpy(&off, &buf[p + (size_t)b * 8], 8);
-        if (off + 8 > buf.size()) return io_fail(FTN_ERR_INVALID_ARGUMENT, "truncated OpenEXR scanline");
-        int32_t y, n; memcpy(&y, &buf[off], 4); memcpy(&n, &buf[off + 4], 4);
-        if (n < 0 || off + 8 + (size_t)n > buf.size() || y < dw[1] || y > dw[3]) return io_fail(FTN_ERR_INVALID_ARGUMENT, "corrupt OpenEXR scanline");
-        const int64_t lines = std::min<int64_t>(lines_per_block, (int64_t)dw[3] - y + 1);
-        const size_t raw_bytes = row_bytes * (size_t)lines;
-        const unsigned char* data = &buf[off + 8];
-        if (compression != 0 && (size_t)n < raw_bytes) {          /* a block that does not shrink is stored raw */
-            const bool ok = compression == 1 ? rle_decode(data, (size_t)n, raw, raw_bytes) : zip_decode(data, (size_t)n, raw, raw_bytes);
-            if (!ok) return io_fail(FTN_ERR_INVALID_ARGUMENT, "corrupt compressed OpenEXR block");
-            data = raw.data();
-        } else if ((size_t)n != raw_bytes) return io_fail(FTN_ERR_INVALID_ARGUMENT, "unexpected OpenEXR block size");
-        for (int64_t ly = 0; ly < lines; ly++) {
-            float* dst = rgb_out + (size_t)(y + ly - dw[1]) * (size_t)w * 3;
-            for (int k = 0; k < 3; k++) {
-                const unsigned char* src = data + (size_t)ly * row_bytes + ch_off[ci[k]];
-                if (chans[ci[k]].type == 2) for (int64_t x = 0; x < w; x++) memcpy(&dst[3 * x + k], src + 4 * x, 4);
-                else for (int64_t x = 0; x < w; x++) { uint16_t hv; memcpy(&hv, src + 2 * x, 2); dst[3 * x + k] = half_to_float(hv); }
-            }
-        }
-    }
-    return FTN_OK;
+    return guarded([&] { return exr_read(path, w_out, h_out, rgb_out); });
 }
 
 }  // extern "C"

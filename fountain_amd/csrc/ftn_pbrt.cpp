@@ -19,7 +19,9 @@
 #include <cstring>
 #include <fstream>
 #include <map>
+#include <new>
 #include <sstream>
+#include <stdexcept>
 #include <string>
 #include <vector>
 
@@ -32,18 +34,25 @@ struct Tok { enum Kind { END, WORD, STR, NUM, LB, RB } kind; std::string text; d
 
 struct Lexer {
     std::string src; size_t p = 0;
+    size_t start = 0;                   /* where the token returned last begins in src */
+    bool unterminated = false;          /* a string without its closing quote ran to the end of the text */
     Tok next() {
         for (;;) {
             while (p < src.size() && isspace((unsigned char)src[p])) p++;
             if (p < src.size() && src[p] == '#') { while (p < src.size() && src[p] != '\n') p++; continue; }
             break;
         }
-        Tok t; t.num = 0;
+        Tok t; t.num = 0; start = p;
         if (p >= src.size()) { t.kind = Tok::END; return t; }
         char c = src[p];
         if (c == '[') { p++; t.kind = Tok::LB; return t; }
         if (c == ']') { p++; t.kind = Tok::RB; return t; }
-        if (c == '"') { size_t e = src.find('"', p + 1); if (e == std::string::npos) e = src.size(); t.kind = Tok::STR; t.text = src.substr(p + 1, e - p - 1); p = e + 1; return t; }
+        if (c == '"') {
+            size_t e = src.find('"', p + 1);
+            t.kind = Tok::STR;
+            if (e == std::string::npos) { unterminated = true; t.text = src.substr(p + 1); p = src.size(); return t; }
+            t.text = src.substr(p + 1, e - p - 1); p = e + 1; return t;
+        }
         size_t s = p;
         while (p < src.size() && !isspace((unsigned char)src[p]) && src[p] != '[' && src[p] != ']' && src[p] != '"' && src[p] != '#') p++;
         t.text = src.substr(s, p - s);
@@ -79,19 +88,34 @@ struct ftn_pbrt {
 
 namespace {
 
-int fail(ftn_pbrt* S, int code, const std::string& m) { S->error = m; return code; }
+/* a message may quote the file: its control bytes (a NUL would end the C string there) are shown as '?' */
+int fail(ftn_pbrt* S, int code, const std::string& m) { S->error = m; for (char& c : S->error) if ((unsigned char)c < 0x20) c = '?'; return code; }
 
 bool parse_params(Lexer& L, Tok& t, ParamSet* out, std::string* err) {
     /* "type name" value | [values]  ... until the next directive word */
     while (t.kind == Tok::STR) {
         std::istringstream ss(t.text); Param p; ss >> p.type >> p.name;
         if (p.name.empty()) { *err = "malformed parameter declaration '" + t.text + "'"; return false; }
+        {   /* the parameter types of the format (the reference's parser knows no others): a misspelt type is not a float */
+            static const char* const types[] = {"integer", "float", "point2", "vector2", "point3", "vector3", "point", "vector", "normal", "normal3", "bool", "string",
+                                                "texture", "rgb", "color", "xyz", "spectrum", "blackbody"};
+            bool known = false; for (const char* ty : types) known = known || p.type == ty;
+            if (!known) { *err = "unknown parameter type in '" + t.text + "'"; return false; }
+        }
         t = L.next();
         std::vector<Tok> vals;
-        if (t.kind == Tok::LB) { for (t = L.next(); t.kind != Tok::RB && t.kind != Tok::END; t = L.next()) vals.push_back(t); t = L.next(); }
-        else { vals.push_back(t); t = L.next(); }
+        if (t.kind == Tok::LB) {
+            for (t = L.next(); t.kind != Tok::RB && t.kind != Tok::END; t = L.next()) vals.push_back(t);
+            if (t.kind != Tok::RB) { *err = "unterminated [ in the value of '" + p.name + "'"; return false; }
+            t = L.next();
+        } else { vals.push_back(t); t = L.next(); }
         for (const Tok& v : vals) {
-            if (p.type == "integer") p.i.push_back((int)v.num);
+            if (p.type == "integer") {
+                /* a value outside int (1e300, -nan, +inf) has no conversion, and a token that is no number (a bare nan or inf lexes as a
+                 * word) has no value: refused, not cast and not read as 0 */
+                if (v.kind != Tok::NUM || !(v.num >= -2147483648.0 && v.num <= 2147483647.0)) { *err = "integer parameter '" + p.name + "' has a value outside the 32-bit integers: " + v.text; return false; }
+                p.i.push_back((int)v.num);
+            }
             else if (p.type == "bool") p.b.push_back(v.text == "true" ? 1 : 0);
             else if (p.type == "string" || p.type == "texture") p.s.push_back(v.text);
             else p.f.push_back((float)v.num);
@@ -112,6 +136,11 @@ int lookup_texture(ftn_pbrt* S, const std::string& name, int* idx, bool* is_floa
     if (b != S->float_textures.end()) { *idx = b->second; *is_float = true; return FTN_OK; }
     return fail(S, FTN_ERR_INVALID_ARGUMENT, "TextureError: " + name);
 }
+/* the texture a "texture" parameter names; one without a value (`"texture Kd" []`) names none and is refused wherever it is looked up */
+int lookup_texture(ftn_pbrt* S, const Param& p, int* idx, bool* is_float) {
+    if (p.s.empty()) return fail(S, FTN_ERR_INVALID_ARGUMENT, "empty texture parameter '" + p.name + "'");
+    return lookup_texture(S, p.s[0], idx, is_float);
+}
 /* make_param_set resolves every "texture" parameter up front (pbrt.rs:114-131): an unknown name fails the statement */
 int check_texture_params(ftn_pbrt* S, const ParamSet& ps) {
     for (const auto& kv : ps) if (kv.second.type == "texture") { int i; bool f; if (kv.second.s.empty()) return fail(S, FTN_ERR_INVALID_ARGUMENT, "empty texture parameter"); int rc = lookup_texture(S, kv.second.s[0], &i, &f); if (rc) return rc; }
@@ -123,14 +152,14 @@ int get_rgb(ftn_pbrt* S, const ParamSet& ps, const char* n, const float def[3], 
     auto it = ps.find(n);
     out[0] = def[0]; out[1] = def[1]; out[2] = def[2]; *tex = -1;
     if (it == ps.end()) return FTN_OK;
-    if (it->second.type == "texture") { int i; bool f; int rc = lookup_texture(S, it->second.s[0], &i, &f); if (rc) return rc; if (!f) *tex = i; return FTN_OK; }
+    if (it->second.type == "texture") { int i; bool f; int rc = lookup_texture(S, it->second, &i, &f); if (rc) return rc; if (!f) *tex = i; return FTN_OK; }
     if (is_spectrum(it->second) && it->second.f.size() >= 3) { out[0] = it->second.f[0]; out[1] = it->second.f[1]; out[2] = it->second.f[2]; }
     return FTN_OK;
 }
 int get_ftex(ftn_pbrt* S, const ParamSet& ps, const char* n, float def, float* out, int32_t* tex) {
     auto it = ps.find(n); *out = def; *tex = -1;
     if (it == ps.end()) return FTN_OK;
-    if (it->second.type == "texture") { int i; bool f; int rc = lookup_texture(S, it->second.s[0], &i, &f); if (rc) return rc; if (f) *tex = i; return FTN_OK; }
+    if (it->second.type == "texture") { int i; bool f; int rc = lookup_texture(S, it->second, &i, &f); if (rc) return rc; if (f) *tex = i; return FTN_OK; }
     if (it->second.type == "float" && !it->second.f.empty()) *out = it->second.f[0];
     return FTN_OK;
 }
@@ -147,7 +176,7 @@ int texture_or_const(ftn_pbrt* S, const ParamSet& ps, const char* n, bool is_flo
     auto it = ps.find(n);
     if (it == ps.end()) return fail(S, FTN_ERR_INVALID_ARGUMENT, std::string("ParamError: missing ") + n);
     if (it->second.type == "texture") {
-        int i; bool f; int rc = lookup_texture(S, it->second.s[0], &i, &f); if (rc) return rc;
+        int i; bool f; int rc = lookup_texture(S, it->second, &i, &f); if (rc) return rc;
         if (f != is_float) return fail(S, FTN_ERR_INVALID_ARGUMENT, std::string("ParamError: texture for ") + n + " has the wrong output type");
         *out = i; return FTN_OK;
     }
@@ -164,27 +193,69 @@ int load_ply(ftn_pbrt* S, const std::string& path, Mesh* m) {
     if (!f) return fail(S, FTN_ERR_INVALID_ARGUMENT, "cannot open " + path);
     std::string line; std::getline(f, line);
     if (line.substr(0, 3) != "ply") return fail(S, FTN_ERR_INVALID_ARGUMENT, path + ": not a PLY file");
-    bool binary = false; size_t nv = 0, nf = 0; std::string cur; std::vector<std::string> vprops, vtypes; std::string cnt_t = "uchar", idx_t = "int";
+    bool binary = false, ended = false, has_format = false, seen_v = false, seen_f = false, has_list = false; size_t nv = 0, nf = 0; std::string cur; std::vector<std::string> vprops, vtypes; std::string cnt_t = "uchar", idx_t = "int";
+    /* a count is a plain decimal number: "-1" and "1e14" are not read as whatever strtoull makes of them */
+    auto count = [&](std::istringstream& ss, size_t* out) { std::string w; ss >> w; if (w.empty() || w.size() > 18 || w.find_first_not_of("0123456789") != std::string::npos) return false; *out = (size_t)strtoull(w.c_str(), nullptr, 10); return true; };
     while (std::getline(f, line)) {
         if (!line.empty() && line.back() == '\r') line.pop_back();
         std::istringstream ss(line); std::string w; ss >> w;
-        if (w == "format") { ss >> w; if (w == "binary_little_endian") binary = true; else if (w != "ascii") return fail(S, FTN_ERR_UNSUPPORTED, "PLY format " + w); }
-        else if (w == "element") { ss >> cur; if (cur == "vertex") ss >> nv; else if (cur == "face") ss >> nf; }
-        else if (w == "property") {
+        if (w == "format") {
+            std::string ver; ss >> w >> ver;
+            if (w == "binary_little_endian") binary = true; else if (w != "ascii") return fail(S, FTN_ERR_UNSUPPORTED, "PLY format " + w);
+            if (ver != "1.0") return fail(S, FTN_ERR_UNSUPPORTED, "PLY format version " + ver);
+            has_format = true;
+        } else if (w == "element") {
+            /* the body is read as the vertices, then the faces: an element this reader does not decode may only follow them */
+            size_t n = 0; ss >> cur;
+            if (!count(ss, &n)) return fail(S, FTN_ERR_INVALID_ARGUMENT, path + ": malformed PLY element count");
+            if (cur == "vertex") { if (seen_v || seen_f) return fail(S, FTN_ERR_INVALID_ARGUMENT, path + ": PLY element vertex given twice or after the faces"); seen_v = true; nv = n; }
+            else if (cur == "face") { if (seen_f) return fail(S, FTN_ERR_INVALID_ARGUMENT, path + ": PLY element face given twice"); seen_f = true; nf = n; }
+            else if (n && !seen_f) return fail(S, FTN_ERR_UNSUPPORTED, "PLY element " + cur + " before the faces");
+        } else if (w == "property") {
             std::string ty; ss >> ty;
-            if (cur == "vertex") { std::string name; ss >> name; vtypes.push_back(ty); vprops.push_back(name); }
-            else if (cur == "face" && ty == "list") { std::string name; ss >> cnt_t >> idx_t >> name; }
-        } else if (w == "end_header") break;
+            if (cur == "vertex") {
+                if (ty == "list") return fail(S, FTN_ERR_UNSUPPORTED, "PLY list property inside element vertex");
+                std::string name; ss >> name; vtypes.push_back(ty); vprops.push_back(name);
+            } else if (cur == "face") {
+                /* a face is its vertex list and nothing else: any other property would sit between the records this reader strides over */
+                std::string name;
+                if (ty != "list" || has_list) return fail(S, FTN_ERR_UNSUPPORTED, "PLY face property other than one vertex index list");
+                ss >> cnt_t >> idx_t >> name; has_list = true;
+                if (name != "vertex_indices" && name != "vertex_index") return fail(S, FTN_ERR_UNSUPPORTED, "PLY face list " + name);
+            }
+        } else if (w == "end_header") { ended = true; break; }
+        else if (!w.empty() && w != "comment" && w != "obj_info") return fail(S, FTN_ERR_INVALID_ARGUMENT, path + ": unknown PLY header line '" + w + "'");
     }
+    if (!ended) return fail(S, FTN_ERR_INVALID_ARGUMENT, path + ": PLY header has no end_header");
+    if (!has_format) return fail(S, FTN_ERR_INVALID_ARGUMENT, path + ": PLY header has no format line");
+    if (nf && !has_list) return fail(S, FTN_ERR_INVALID_ARGUMENT, path + ": PLY faces without a vertex index list");
     auto col = [&](const char* n) { for (size_t i = 0; i < vprops.size(); i++) if (vprops[i] == n) return (int)i; return -1; };
     const int cx = col("x"), cy = col("y"), cz = col("z"), cnx = col("nx"), cny = col("ny"), cnz = col("nz"), cu = col("u"), cv = col("v");
     if (cx < 0 || cy < 0 || cz < 0) return fail(S, FTN_ERR_INVALID_ARGUMENT, "Ply file is missing vertex coordinates");
     for (const std::string& t : vtypes) if (t != "float" && t != "float32") return fail(S, FTN_ERR_UNSUPPORTED, "PLY vertex property type " + t);
     const bool hn = cnx >= 0 && cny >= 0 && cnz >= 0, huv = cu >= 0 && cv >= 0;
+    /* the face list as this reader decodes it: a 1-byte or 4-byte count, 4-byte indices (a binary file of any other type would be
+     * decoded at the wrong stride; an ASCII file is numbers whatever it calls them) */
+    const bool cnt1 = cnt_t == "uchar" || cnt_t == "uint8";
+    if (binary && nf) {
+        if (!cnt1 && cnt_t != "int" && cnt_t != "int32" && cnt_t != "uint" && cnt_t != "uint32") return fail(S, FTN_ERR_UNSUPPORTED, "PLY face count type " + cnt_t);
+        if (idx_t != "int" && idx_t != "int32" && idx_t != "uint" && idx_t != "uint32") return fail(S, FTN_ERR_UNSUPPORTED, "PLY vertex index type " + idx_t);
+    }
+    /* the counts against the bytes the file still has, before anything is sized by them: a binary vertex is 4 bytes a property and a
+     * face 12 and its count; an ASCII number is at least one character and its separator */
+    const std::streamoff body = f.tellg();
+    f.seekg(0, std::ios::end);
+    const std::streamoff end = f.tellg();
+    f.seekg(body);
+    if (body < 0 || end < body || !f) return fail(S, FTN_ERR_INVALID_ARGUMENT, path + ": truncated PLY");
+    const size_t left = (size_t)(end - body) + 1 /* the last ASCII number needs no separator */, ncol = vprops.size();
+    const size_t vbytes = binary ? 4 * ncol : 2 * ncol, fbytes = binary ? (cnt1 ? 13 : 16) : 8;
+    if (nv > left / vbytes || nf > (left - nv * vbytes) / fbytes) return fail(S, FTN_ERR_INVALID_ARGUMENT, path + ": truncated PLY (the header counts more than the file holds)");
     m->P.resize(3 * nv); if (hn) m->N.resize(3 * nv); if (huv) m->UV.resize(2 * nv);
     std::vector<float> row(vprops.size());
     for (size_t i = 0; i < nv; i++) {
         if (binary) f.read((char*)row.data(), row.size() * 4); else for (float& x : row) f >> x;
+        if (!f) return fail(S, FTN_ERR_INVALID_ARGUMENT, path + ": truncated PLY");
         m->P[3 * i] = row[cx]; m->P[3 * i + 1] = row[cy]; m->P[3 * i + 2] = row[cz];
         if (hn) { m->N[3 * i] = row[cnx]; m->N[3 * i + 1] = row[cny]; m->N[3 * i + 2] = row[cnz]; }
         if (huv) { m->UV[2 * i] = row[cu]; m->UV[2 * i + 1] = row[cv]; }
@@ -193,13 +264,18 @@ int load_ply(ftn_pbrt* S, const std::string& path, Mesh* m) {
     for (size_t i = 0; i < nf; i++) {
         int n = 0; int v[3] = {0, 0, 0};
         if (binary) {
-            if (cnt_t == "uchar" || cnt_t == "uint8") { unsigned char c; f.read((char*)&c, 1); n = c; } else { int c; f.read((char*)&c, 4); n = c; }
+            if (cnt1) { unsigned char c = 0; f.read((char*)&c, 1); n = c; } else { int c = 0; f.read((char*)&c, 4); n = c; }
+            if (!f) return fail(S, FTN_ERR_INVALID_ARGUMENT, path + ": truncated PLY");
             if (n != 3) return fail(S, FTN_ERR_UNSUPPORTED, "Face with unsupported vertex count found");
             f.read((char*)v, 12);
-        } else { f >> n; if (n != 3) return fail(S, FTN_ERR_UNSUPPORTED, "Face with unsupported vertex count found"); f >> v[0] >> v[1] >> v[2]; }
-        for (int k = 0; k < 3; k++) m->idx.push_back((uint32_t)v[k]);
+        } else { f >> n; if (!f) return fail(S, FTN_ERR_INVALID_ARGUMENT, path + ": truncated PLY"); if (n != 3) return fail(S, FTN_ERR_UNSUPPORTED, "Face with unsupported vertex count found"); f >> v[0] >> v[1] >> v[2]; }
+        /* any read that failed, at the end of the file or before it: the face is not in the file */
+        if (!f) return fail(S, FTN_ERR_INVALID_ARGUMENT, path + ": truncated PLY");
+        for (int k = 0; k < 3; k++) {
+            if (v[k] < 0 || (size_t)v[k] >= nv) return fail(S, FTN_ERR_INVALID_ARGUMENT, "vertex index out of range");      /* negative, or a uint above 2^31, or >= nv */
+            m->idx.push_back((uint32_t)v[k]);
+        }
     }
-    if (!f && !f.eof()) return fail(S, FTN_ERR_INVALID_ARGUMENT, path + ": truncated PLY");
     return FTN_OK;
 }
 
@@ -222,7 +298,7 @@ int add_material(ftn_pbrt* S, const std::string& name, const ParamSet& ps, int* 
             auto it = ps.find(n);
             if (it == ps.end()) return fail(S, FTN_ERR_INVALID_ARGUMENT, "metal needs eta and k (constructors.rs:215-216)");
             if (it->second.type == "texture") {
-                int i; bool f; if ((rc = lookup_texture(S, it->second.s[0], &i, &f))) return rc;
+                int i; bool f; if ((rc = lookup_texture(S, it->second, &i, &f))) return rc;
                 if (f) return fail(S, FTN_ERR_INVALID_ARGUMENT, std::string("ParamError: texture for ") + n + " has the wrong output type");
                 *slot = i;
             } else if (is_spectrum(it->second) && it->second.f.size() >= 3) { dst[0] = it->second.f[0]; dst[1] = it->second.f[1]; dst[2] = it->second.f[2]; }
@@ -230,7 +306,7 @@ int add_material(ftn_pbrt* S, const std::string& name, const ParamSet& ps, int* 
         }
         float rough; int32_t trough; if ((rc = get_ftex(S, ps, "roughness", 0.01f, &rough, &trough))) return rc;
         auto present = [&](const char* n) { auto it = ps.find(n); if (it == ps.end()) return false; if (it->second.type == "float") return true;
-                                            if (it->second.type == "texture") { int i; bool f; return lookup_texture(S, it->second.s[0], &i, &f) == FTN_OK && f; } return false; };
+                                            if (it->second.type == "texture") { int i; bool f; return lookup_texture(S, it->second, &i, &f) == FTN_OK && f; } return false; };
         if (present("uroughness") && present("vroughness")) { if ((rc = get_ftex(S, ps, "uroughness", 0.0f, &m.s1, &mt.s1)) || (rc = get_ftex(S, ps, "vroughness", 0.0f, &m.s2, &mt.s2))) return rc; }
         else { m.s1 = rough; m.s2 = rough; mt.s1 = trough; mt.s2 = trough; }
         m.remap_roughness = getb(ps, "remaproughness", true) ? 1 : 0;
@@ -327,39 +403,61 @@ int read_file(const std::string& path, std::string* out) {
     std::stringstream ss; ss << f.rdbuf(); *out = ss.str(); return 0;
 }
 
-int parse(ftn_pbrt* S, const std::string& path) {
-    std::string src;
-    if (read_file(path, &src)) return fail(S, FTN_ERR_INVALID_ARGUMENT, "cannot open " + path);
-    /* parse_with_includes: textual Include before evaluation */
-    for (size_t pos; (pos = src.find("Include")) != std::string::npos;) {
-        size_t q0 = src.find('"', pos), q1 = q0 == std::string::npos ? q0 : src.find('"', q0 + 1);
-        if (q1 == std::string::npos) break;
-        std::string inc, name = src.substr(q0 + 1, q1 - q0 - 1);
-        if (read_file(S->base_dir + "/" + name, &inc)) return fail(S, FTN_ERR_INVALID_ARGUMENT, "cannot open include " + name);
-        src = src.substr(0, pos) + inc + src.substr(q1 + 1);
+/* parse_with_includes: an `Include "file"` statement is replaced by the text of the file (relative to the scene file, at any depth)
+ * before evaluation.  Only the directive is: the word inside a comment or a string is text.  A file that is already being expanded
+ * (a cycle) and a nesting deeper than MAX_INCLUDE_DEPTH are refused. */
+const size_t MAX_INCLUDE_DEPTH = 16, MAX_EXPANDED_BYTES = (size_t)1 << 30;
+int expand_includes(ftn_pbrt* S, const std::string& path, std::vector<std::string>* open, std::string* out) {
+    for (const std::string& o : *open) if (o == path) return fail(S, FTN_ERR_INVALID_ARGUMENT, "Include cycle through " + path);
+    if (open->size() > MAX_INCLUDE_DEPTH) return fail(S, FTN_ERR_INVALID_ARGUMENT, "Include statements nested deeper than 16");
+    Lexer L;
+    if (read_file(path, &L.src)) return fail(S, FTN_ERR_INVALID_ARGUMENT, (open->empty() ? "cannot open " : "cannot open include ") + path);
+    open->push_back(path);
+    size_t copied = 0;
+    for (Tok t = L.next(); t.kind != Tok::END; t = L.next()) {
+        if (t.kind != Tok::WORD || t.text != "Include") continue;
+        const size_t at = L.start;
+        t = L.next();
+        if (t.kind != Tok::STR || L.unterminated) return fail(S, FTN_ERR_INVALID_ARGUMENT, "Include: expected a quoted file name");
+        out->append(L.src, copied, at - copied); copied = L.p;
+        int rc = expand_includes(S, S->base_dir + "/" + t.text, open, out); if (rc) return rc;
+        if (out->size() > MAX_EXPANDED_BYTES) return fail(S, FTN_ERR_INVALID_ARGUMENT, "Include statements expand to more than 1 GiB of text");
     }
+    if (L.unterminated) return fail(S, FTN_ERR_INVALID_ARGUMENT, "unterminated string in " + path);
+    out->append(L.src, copied, std::string::npos);
+    open->pop_back();
+    return FTN_OK;
+}
+
+int parse(ftn_pbrt* S, const std::string& path) {
+    std::string src; int rc;
+    { std::vector<std::string> open; if ((rc = expand_includes(S, path, &open, &src))) return rc; }
     Lexer L; L.src = src;
     Tok t = L.next();
-    bool world = false;
+    bool world = false; std::vector<char> nest;      /* the open AttributeBegin ('A') and TransformBegin ('T') blocks, innermost last */
     ftn_transform_identity(&S->header_tf); ftn_transform_identity(&S->camera_tf);
     const float d05[3] = {0.5f, 0.5f, 0.5f};
-    int rc;
     while (t.kind != Tok::END) {
         if (t.kind != Tok::WORD) return fail(S, FTN_ERR_INVALID_ARGUMENT, "expected a directive, got '" + t.text + "'");
         const std::string w = t.text; t = L.next();
         if (is_transform_word(w)) { if ((rc = do_transform(S, w, L, t, world ? &S->tf.back() : &S->header_tf))) return rc; continue; }
         if (w == "WorldBegin") {
-            world = true;
+            world = true; nest.clear();
             S->tf.assign(1, ftn_transform()); ftn_transform_identity(&S->tf[0]);
             ParamSet none; int mat; if ((rc = add_material(S, "matte", none, &mat))) return rc;      /* default material (pbrt.rs:88-96) */
             S->gs.assign(1, GState{mat, -1, false});
             continue;
         }
+        /* before WorldBegin there is no graphics state and no transform stack: only the header statements of PbrtHeader::exec_stmt
+         * (pbrt.rs:507-532) and the transforms above are statements there */
+        if (!world && !(w == "Camera" || w == "Sampler" || w == "Film" || w == "PixelFilter" || w == "Integrator" || w == "Accelerator"))
+            return fail(S, w == "ObjectBegin" || w == "ObjectEnd" || w == "MakeNamedMedium" || w == "MediumInterface" ? FTN_ERR_UNSUPPORTED : FTN_ERR_INVALID_ARGUMENT, w + " outside the world block");
         if (w == "WorldEnd") break;
-        if (w == "AttributeBegin") { S->gs.push_back(S->gs.back()); S->tf.push_back(S->tf.back()); continue; }
-        if (w == "AttributeEnd") { if (S->gs.size() < 2) return fail(S, FTN_ERR_INVALID_ARGUMENT, "unbalanced AttributeEnd"); S->gs.pop_back(); S->tf.pop_back(); continue; }
-        if (w == "TransformBegin") { S->tf.push_back(S->tf.back()); continue; }
-        if (w == "TransformEnd") { if (S->tf.size() < 2) return fail(S, FTN_ERR_INVALID_ARGUMENT, "unbalanced TransformEnd"); S->tf.pop_back(); continue; }
+        /* an End closes the Begin of its own kind: `AttributeBegin TransformEnd AttributeEnd` would pop the transform stack empty */
+        if (w == "AttributeBegin") { S->gs.push_back(S->gs.back()); S->tf.push_back(S->tf.back()); nest.push_back('A'); continue; }
+        if (w == "AttributeEnd") { if (S->gs.size() < 2 || nest.empty() || nest.back() != 'A') return fail(S, FTN_ERR_INVALID_ARGUMENT, "unbalanced AttributeEnd"); S->gs.pop_back(); S->tf.pop_back(); nest.pop_back(); continue; }
+        if (w == "TransformBegin") { S->tf.push_back(S->tf.back()); nest.push_back('T'); continue; }
+        if (w == "TransformEnd") { if (S->tf.size() < 2 || nest.empty() || nest.back() != 'T') return fail(S, FTN_ERR_INVALID_ARGUMENT, "unbalanced TransformEnd"); S->tf.pop_back(); nest.pop_back(); continue; }
         if (w == "ReverseOrientation") { S->gs.back().rev = true; continue; }
         if (w == "ObjectBegin" || w == "ObjectEnd" || w == "MakeNamedMedium" || w == "MediumInterface")
             return fail(S, FTN_ERR_UNSUPPORTED, w + " is unimplemented!() in the reference (pbrt.rs:196-201, :242-247)");
@@ -459,6 +557,7 @@ int parse(ftn_pbrt* S, const std::string& path) {
                 if (it->second.i.size() % 3) return fail(S, FTN_ERR_INVALID_ARGUMENT, "indices is not a multiple of 3");
                 if (ip->second.f.size() % 3) return fail(S, FTN_ERR_INVALID_ARGUMENT, "P is not a multiple of 3");
                 const int levels = geti(ps, "levels", geti(ps, "nlevels", 3));
+                if (levels < 0 || levels > FTN_SUBDIV_MAX_LEVELS) return fail(S, FTN_ERR_INVALID_ARGUMENT, "loopsubdiv: levels must be 0..10");     /* it indexes info below */
                 std::vector<uint32_t> cage; for (int v : it->second.i) cage.push_back((uint32_t)v);
                 const int32_t nv = (int32_t)(ip->second.f.size() / 3), nf = (int32_t)(cage.size() / 3);
                 ftn_subdiv_info info;
@@ -473,6 +572,7 @@ int parse(ftn_pbrt* S, const std::string& path) {
         } else return fail(S, FTN_ERR_INVALID_ARGUMENT, "unknown directive " + w);
         (void)d05;
     }
+    if (L.unterminated) return fail(S, FTN_ERR_INVALID_ARGUMENT, "unterminated string");
     if (!world) return fail(S, FTN_ERR_INVALID_ARGUMENT, "no WorldBegin");
     /* header objects: make_camera / make_sampler / make_film (pbrt.rs:426-505) */
     const int xres = geti(S->film_params, "xresolution", 640), yres = geti(S->film_params, "yresolution", 480);
@@ -513,17 +613,31 @@ int parse(ftn_pbrt* S, const std::string& path) {
 
 thread_local std::string g_pbrt_err;
 
+/* nothing unwinds across the C boundary: a failed allocation (or a size no allocation can have) is FTN_ERR_OUT_OF_MEMORY, anything else
+ * FTN_ERR_INTERNAL */
+template <class F> int guarded(F&& f) {
+    try { return f(); }
+    catch (const std::bad_alloc&) { g_pbrt_err = "out of memory"; return FTN_ERR_OUT_OF_MEMORY; }
+    catch (const std::length_error&) { g_pbrt_err = "out of memory (a size no allocation can have)"; return FTN_ERR_OUT_OF_MEMORY; }
+    catch (const std::exception& e) { g_pbrt_err = e.what(); return FTN_ERR_INTERNAL; }
+}
+
 }  // namespace
 
 extern "C" {
 
 int ftn_pbrt_load(const char* path, ftn_pbrt** out) {
     if (!path || !out) return FTN_ERR_INVALID_ARGUMENT;
-    ftn_pbrt* S = new ftn_pbrt();
-    std::string p(path); size_t sl = p.find_last_of('/');
-    S->base_dir = sl == std::string::npos ? "." : p.substr(0, sl);
-    int rc = parse(S, p);
-    if (rc) { g_pbrt_err = S->error; delete S; return rc; }
+    ftn_pbrt* S = nullptr;
+    int rc = guarded([&] {
+        S = new ftn_pbrt();
+        std::string p(path); size_t sl = p.find_last_of('/');
+        S->base_dir = sl == std::string::npos ? "." : p.substr(0, sl);
+        int r = parse(S, p);
+        if (r) g_pbrt_err = S->error;
+        return r;
+    });
+    if (rc) { delete S; return rc; }       /* what was built goes with the refusal */
     *out = S; return FTN_OK;
 }
 void ftn_pbrt_destroy(ftn_pbrt* s) { delete s; }
@@ -550,18 +664,22 @@ int ftn_pbrt_filter(const ftn_pbrt* s, ftn_filter_desc* out) {
 }
 /* PLY reader on its own (constructors.rs:94-190): fills caller arrays after a sizing call with NULL outputs */
 int ftn_ply_load(const char* path, uint32_t* n_vertices, uint32_t* n_triangles, float* P, float* N, float* UV, uint32_t* indices, int* has_normals, int* has_uvs) {
-    ftn_pbrt tmp; Mesh m;
-    int rc = load_ply(&tmp, path, &m);
-    if (rc) { g_pbrt_err = tmp.error; return rc; }
-    if (n_vertices) *n_vertices = (uint32_t)(m.P.size() / 3);
-    if (n_triangles) *n_triangles = (uint32_t)(m.idx.size() / 3);
-    if (has_normals) *has_normals = m.N.empty() ? 0 : 1;
-    if (has_uvs) *has_uvs = m.UV.empty() ? 0 : 1;
-    if (P) memcpy(P, m.P.data(), m.P.size() * 4);
-    if (N && !m.N.empty()) memcpy(N, m.N.data(), m.N.size() * 4);
-    if (UV && !m.UV.empty()) memcpy(UV, m.UV.data(), m.UV.size() * 4);
-    if (indices) memcpy(indices, m.idx.data(), m.idx.size() * 4);
-    return FTN_OK;
+    if (!path) { g_pbrt_err = "ftn_ply_load: null path"; return FTN_ERR_INVALID_ARGUMENT; }
+    return guarded([&]() -> int {
+        ftn_pbrt tmp; Mesh m;
+        int rc = load_ply(&tmp, path, &m);
+        if (rc) { g_pbrt_err = tmp.error; return rc; }
+        if (m.P.size() / 3 > 0xffffffffu || m.idx.size() / 3 > 0xffffffffu) { g_pbrt_err = "PLY mesh too large for 32-bit counts"; return FTN_ERR_UNSUPPORTED; }
+        if (n_vertices) *n_vertices = (uint32_t)(m.P.size() / 3);
+        if (n_triangles) *n_triangles = (uint32_t)(m.idx.size() / 3);
+        if (has_normals) *has_normals = m.N.empty() ? 0 : 1;
+        if (has_uvs) *has_uvs = m.UV.empty() ? 0 : 1;
+        if (P && !m.P.empty()) memcpy(P, m.P.data(), m.P.size() * 4);
+        if (N && !m.N.empty()) memcpy(N, m.N.data(), m.N.size() * 4);
+        if (UV && !m.UV.empty()) memcpy(UV, m.UV.data(), m.UV.size() * 4);
+        if (indices && !m.idx.empty()) memcpy(indices, m.idx.data(), m.idx.size() * 4);
+        return FTN_OK;
+    });
 }
 
 }  // extern "C"

@@ -62,7 +62,7 @@ class Filter:
         desc = A.ftn_filter_desc()
         rc = _lib(parsed.be).ftn_pbrt_filter(parsed.handle, C.byref(desc))
         if rc < 0:
-            raise FountainError(rc, parsed.be.lib.ftn_pbrt_last_error().decode())
+            raise FountainError(rc, parsed.be.lib.ftn_pbrt_last_error().decode(errors="replace"))
         return cls.from_desc(parsed.be, desc) if rc else None
 
     @property

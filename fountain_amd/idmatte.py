@@ -249,7 +249,7 @@ def write_channels(path, planes, attrs=None, be=None):
     h, w = arrs[0].shape
     rc = lib.ftn_exr_write_channels(path.encode(), w, h, len(arrs), strings(names), ptrs, len(attrs), strings(list(attrs)), strings(list(attrs.values())))
     if rc != 0:
-        raise FountainError(rc, be.lib.ftn_imageio_last_error().decode())
+        raise FountainError(rc, be.lib.ftn_imageio_last_error().decode(errors="replace"))
 
 
 def write_cryptomatte(path, layers, be=None):

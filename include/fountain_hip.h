@@ -424,7 +424,14 @@ int ftn_render_device(const ftn_scene* scene, const ftn_camera_desc* camera, con
  * (src/loaders/pbrt.rs:426-532) and PbrtSceneBuilder::exec_stmt (pbrt.rs:178-330) with the defaults of
  * src/loaders/constructors.rs:38-359.  Include files and `Shape "plymesh"` resolve relative to the scene file.  Statements the
  * reference leaves unimplemented!() and non-constant textures return FTN_ERR_UNSUPPORTED; Integrator / PixelFilter / Accelerator
- * are ignored as in the reference (pbrt.rs:528-530).  The descriptors stay owned by the handle.                           */
+ * are ignored as in the reference (pbrt.rs:528-530).  The descriptors stay owned by the handle.
+ * A file is arbitrary bytes, and the call returns whatever they are ("File readers"): FTN_OK and a handle, or
+ * FTN_ERR_INVALID_ARGUMENT / FTN_ERR_UNSUPPORTED / FTN_ERR_OUT_OF_MEMORY, no handle, nothing kept, and a message in
+ * ftn_pbrt_last_error().  Refused among others: any statement but Camera / Sampler / Film / PixelFilter / Integrator / Accelerator
+ * and the transforms before WorldBegin; an AttributeEnd or TransformEnd that does not close a Begin of its own kind; a string or a [
+ * that is never closed; an "integer" value that is not finite or not a 32-bit integer; a "texture" parameter without a value; an
+ * Include of a file that is being included already, nested deeper than 16, or expanding to more than 1 GiB.  `Include` is a statement
+ * only where it stands as one: inside a comment or a string it is text.                                                    */
 typedef struct ftn_pbrt ftn_pbrt;
 int ftn_pbrt_load(const char* path, ftn_pbrt** out);
 void ftn_pbrt_destroy(ftn_pbrt* p);
@@ -435,7 +442,13 @@ int ftn_pbrt_samples_per_pixel(const ftn_pbrt* p);            /* Sampler "pixels
 const char* ftn_pbrt_film_name(const ftn_pbrt* p);            /* Film "filename"                               */
 const char* ftn_pbrt_last_error(void);                        /* message of the last failed ftn_pbrt_load / ftn_ply_load on this thread */
 /* make_triangle_mesh_from_ply's reader (constructors.rs:94-190): ASCII or binary_little_endian, float x y z [nx ny nz] [u v],
- * triangle faces only.  Call once with NULL arrays for the counts, then with arrays of 3*nv / 3*nv / 2*nv floats and 3*nt indices. */
+ * triangle faces only.  Call once with NULL arrays for the counts, then with arrays of 3*nv / 3*nv / 2*nv floats and 3*nt indices.
+ * On FTN_OK every element of the arrays the file has (P, indices, N / UV when flagged) was read from the file and every index is below
+ * n_vertices.  Refused (INVALID_ARGUMENT or UNSUPPORTED, message in ftn_pbrt_last_error()): any read that fails, at the end of the file
+ * or before it ("truncated PLY"); counts the remaining bytes cannot hold (checked before anything is allocated); a header without
+ * format 1.0, end_header or known keywords; vertex not before face, or another element before them; a `list` inside vertex, any face
+ * property but one vertex_indices list; in a binary file a list count that is not uchar / int / uint or indices that are not int / uint;
+ * a negative or out-of-range index.                                                                                        */
 int ftn_ply_load(const char* path, uint32_t* n_vertices, uint32_t* n_triangles, float* P, float* N, float* UV,
                  uint32_t* indices, int* has_normals, int* has_uvs);
 
@@ -450,7 +463,16 @@ int ftn_film_resolve_device(const void* device_pixels, size_t n_pixels, void* de
 /* write_exr / read_exr (src/imageio/exr.rs:11-87): scanline OpenEXR, FLOAT channels R G B, layer "image"; rgb is row-major,
  * 3 floats per pixel.  The writer emits NO_COMPRESSION blocks (the reference's `exr` crate writes RLE: same samples, same layer);
  * the reader accepts NO_COMPRESSION, RLE, ZIPS and ZIP scanline files with FLOAT or HALF channels.  ftn_exr_read with rgb_out == NULL only
- * reports the size.                                                                                                        */
+ * reports the size.
+ * The reader takes arbitrary bytes ("File readers").  On FTN_OK the size is the data window's and every one of the
+ * width * height * 3 floats was written from the file; both calls check the whole structure, so a size the sizing call reports
+ * belongs to a file the filling call can only refuse for a corrupt compressed block.  CAP: a data window of more than 2^28 pixels
+ * (3 GiB of RGB floats) is refused.  Also refused (FTN_ERR_INVALID_ARGUMENT, or FTN_ERR_UNSUPPORTED for what OpenEXR allows and this
+ * reader does not decode; message in ftn_imageio_last_error()): a header, attribute, channel list, offset table or block that ends
+ * before what it declares; one of the eight attributes every OpenEXR header has missing, twice, or of another type or size; offsets
+ * and block sizes outside the file; a block that is not on its multiple of the block height inside the window, or stored twice -- every
+ * scanline is covered exactly once; a packed block claiming more than 1040 times its size.  All four entry points turn a failed
+ * allocation into FTN_ERR_OUT_OF_MEMORY and any other C++ exception into FTN_ERR_INTERNAL.                                */
 int ftn_exr_write(const char* path, const float* rgb, uint32_t width, uint32_t height);
 int ftn_exr_read(const char* path, uint32_t* width, uint32_t* height, float* rgb_out);
 const char* ftn_imageio_last_error(void);

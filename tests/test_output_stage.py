@@ -10,6 +10,8 @@ import pytest
 from fountain_amd import FountainError, PbrtScene, SceneBuilder, read_exr, write_exr
 from fountain_amd import _abi as A
 
+from _corrupt_files import exr_file          # the RLE, ZIPS and ZIP packers: _corrupt_files.py builds its corrupt OpenEXR files with them too
+
 
 def _independent_exr_read(path):
     b = open(path, "rb").read()
@@ -55,28 +57,6 @@ def test_exr_writer_layout_and_bits(ftn, tmp_path):
     assert np.array_equal(back.view(np.uint32), img.view(np.uint32))
 
 
-def _rle_block(raw):
-    """OpenEXR RLE: de-interleave into two halves, delta-predict, then run-length encode (runs as literals here and there)."""
-    n = len(raw)
-    t = bytes(raw[0::2]) + bytes(raw[1::2])
-    d = bytearray(n); d[0] = t[0]
-    for i in range(1, n):
-        d[i] = (t[i] - t[i - 1] + 128) & 255
-    out, i = bytearray(), 0
-    while i < n:
-        j = i
-        while j + 1 < n and d[j + 1] == d[i] and j - i < 126:
-            j += 1
-        if j - i >= 2:
-            out += struct.pack("b", j - i) + bytes([d[i]]); i = j + 1
-        else:
-            k = i
-            while k < n and k - i < 127 and not (k + 2 < n and d[k] == d[k + 1] == d[k + 2]):
-                k += 1
-            out += struct.pack("b", -(k - i)) + bytes(d[i:k]); i = k
-    return bytes(out)
-
-
 @pytest.mark.parametrize("half", [False, True])
 def test_exr_reader_rle_and_half(ftn, tmp_path, half):
     """The file kind the reference's own writer produces (RLE scanlines), plus HALF channels (read_exr's F16 arm)."""
@@ -86,25 +66,9 @@ def test_exr_reader_rle_and_half(ftn, tmp_path, half):
     img[2:5] = 0.25                                            # long runs
     if half:
         img = img.astype(np.float16).astype(np.float32)
-    def attr(name, typ, data):
-        return name.encode() + b"\0" + typ.encode() + b"\0" + struct.pack("<i", len(data)) + data
-    chl = b"".join(c.encode() + b"\0" + struct.pack("<iB3xii", 1 if half else 2, 0, 1, 1) for c in "BGR") + b"\0"
-    box = struct.pack("<4i", 0, 0, w - 1, h - 1)
-    hdr = bytes([0x76, 0x2f, 0x31, 0x01, 2, 0, 0, 0]) + attr("channels", "chlist", chl) + attr("compression", "compression", b"\1") + \
-        attr("dataWindow", "box2i", box) + attr("displayWindow", "box2i", box) + attr("lineOrder", "lineOrder", b"\0") + \
-        attr("pixelAspectRatio", "float", struct.pack("<f", 1)) + attr("screenWindowCenter", "v2f", struct.pack("<2f", 0, 0)) + \
-        attr("screenWindowWidth", "float", struct.pack("<f", 1)) + b"\0"
-    blocks = []
-    for y in range(h):
-        raw = b"".join(img[y, :, "RGB".index(c)].astype("<f2" if half else "<f4").tobytes() for c in "BGR")
-        comp = _rle_block(raw)
-        data = comp if len(comp) < len(raw) else raw           # OpenEXR stores the raw block when compression does not help
-        blocks.append(struct.pack("<ii", y, len(data)) + data)
-    off, offs = len(hdr) + 8 * h, []
-    for blk in blocks:
-        offs.append(off); off += len(blk)
+    data = exr_file(img, 1, half)                              # one RLE block a scanline (stored raw where RLE does not help)
     path = tmp_path / "r.exr"
-    path.write_bytes(hdr + struct.pack("<%dQ" % h, *offs) + b"".join(blocks))
+    path.write_bytes(data)
     got = read_exr(str(path), ftn)
     assert np.array_equal(got.view(np.uint32), img.view(np.uint32))
 
@@ -112,33 +76,11 @@ def test_exr_reader_rle_and_half(ftn, tmp_path, half):
 @pytest.mark.parametrize("comp,lines", [(2, 1), (3, 16)])
 def test_exr_reader_zip(ftn, tmp_path, comp, lines):
     """ZIPS (one scanline per block) and ZIP (16 per block, the last one short): the usual encodings of PBRT scenes' EXR textures"""
-    import zlib
     w, h = 21, 37
     rng = np.random.default_rng(comp)
     img = (rng.random((h, w, 3)) * np.linspace(0.1, 4, w)[None, :, None]).astype(np.float32)
-    def attr(name, typ, data):
-        return name.encode() + b"\0" + typ.encode() + b"\0" + struct.pack("<i", len(data)) + data
-    chl = b"".join(c.encode() + b"\0" + struct.pack("<iB3xii", 2, 0, 1, 1) for c in "BGR") + b"\0"
-    box = struct.pack("<4i", 0, 0, w - 1, h - 1)
-    hdr = bytes([0x76, 0x2f, 0x31, 0x01, 2, 0, 0, 0]) + attr("channels", "chlist", chl) + attr("compression", "compression", bytes([comp])) + \
-        attr("dataWindow", "box2i", box) + attr("displayWindow", "box2i", box) + attr("lineOrder", "lineOrder", b"\0") + \
-        attr("pixelAspectRatio", "float", struct.pack("<f", 1)) + attr("screenWindowCenter", "v2f", struct.pack("<2f", 0, 0)) + \
-        attr("screenWindowWidth", "float", struct.pack("<f", 1)) + b"\0"
-    blocks = []
-    for y0 in range(0, h, lines):
-        raw = b"".join(img[y, :, "RGB".index(c)].astype("<f4").tobytes() for y in range(y0, min(y0 + lines, h)) for c in "BGR")
-        t = bytes(raw[0::2]) + bytes(raw[1::2])                                      # two halves
-        d = bytearray(len(t)); d[0] = t[0]
-        for i in range(1, len(t)):
-            d[i] = (t[i] - t[i - 1] + 128) & 255                                     # byte predictor
-        z = zlib.compress(bytes(d))
-        data = z if len(z) < len(raw) else raw
-        blocks.append(struct.pack("<ii", y0, len(data)) + data)
-    off, offs = len(hdr) + 8 * len(blocks), []
-    for blk in blocks:
-        offs.append(off); off += len(blk)
     path = tmp_path / "z.exr"
-    path.write_bytes(hdr + struct.pack("<%dQ" % len(blocks), *offs) + b"".join(blocks))
+    path.write_bytes(exr_file(img, comp))
     got = read_exr(str(path), ftn)
     assert np.array_equal(got.view(np.uint32), img.view(np.uint32))
 
@@ -152,14 +94,17 @@ def test_exr_errors(ftn, tmp_path):
     assert e.value.code == A.FTN_ERR_INVALID_ARGUMENT
 
 
+MAPNAME_SCENE = ('Camera "perspective"\nWorldBegin\nRotate 30 0 1 0\n'
+                 'LightSource "infinite" "string mapname" "sky.exr" "rgb scale" [2.5 9 9]\nShape "sphere"\nWorldEnd\n')
+
+
 def test_infinite_light_mapname(ftn, tmp_path):
     """make_infinite_area_light with "mapname" (constructors.rs:339-359 -> load_mipmap imageio/mod.rs:81-106): EXR texels * scale[0]."""
     from test_pbrt_loader import assert_same_desc
     rng = np.random.default_rng(2)
     tex = rng.random((8, 8, 3)).astype(np.float32)
     write_exr(str(tmp_path / "sky.exr"), tex, ftn)
-    (tmp_path / "s.pbrt").write_text('Camera "perspective"\nWorldBegin\nRotate 30 0 1 0\n'
-                                      'LightSource "infinite" "string mapname" "sky.exr" "rgb scale" [2.5 9 9]\nShape "sphere"\nWorldEnd\n')
+    (tmp_path / "s.pbrt").write_text(MAPNAME_SCENE)
     ps = PbrtScene(str(tmp_path / "s.pbrt"), ftn)
     b = SceneBuilder(ftn)
     b.rotate(30, (0, 1, 0))

@@ -342,6 +342,15 @@ def _same_film(px, ref, n_spill, what):
     assert np.allclose(px, ref, rtol=2e-6, atol=1e-7), what
 
 
+PLYMESH_SCENE = (
+    'Film "image" "integer xresolution" [ 72 ] "integer yresolution" [ 56 ]\nSampler "random" "integer pixelsamples" 4\n'
+    'LookAt 28 -28 14  0 0 -2  0 0 1\nCamera "perspective" "float fov" 40\nWorldBegin\n'
+    'LightSource "infinite" "rgb L" [0.9 1.0 1.2]\n'
+    'AttributeBegin\n  Material "metal" "rgb eta" [0.2 0.92 1.1] "rgb k" [3.9 2.45 2.14] "float roughness" 0.1\n  Rotate 20 0 0 1\n  Shape "plymesh" "string filename" "cube.ply"\nAttributeEnd\n'
+    'AttributeBegin\n  Material "matte" "rgb Kd" [0.5 0.5 0.5]\n  Shape "trianglemesh" "integer indices" [0 1 2 0 2 3] "point P" [-60 -60 -9.99  60 -60 -9.99  60 60 -9.99  -60 60 -9.99]\nAttributeEnd\n'
+    'WorldEnd\n')
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("pipeline", [A.FTN_PIPELINE_MEGAKERNEL, A.FTN_PIPELINE_WAVEFRONT])
 @pytest.mark.parametrize("which", ["furnace", "cornell", "plymesh"])
@@ -360,13 +369,7 @@ def test_parsed_scene_files_render_like_the_oracle(gpu, orc_det, tmp_path, which
     else:
         P, N, F = scenes.rounded_cube_mesh()
         _write_ply(str(tmp_path / "cube.ply"), P, N, None, F, True)
-        (tmp_path / "s.pbrt").write_text(
-            'Film "image" "integer xresolution" [ 72 ] "integer yresolution" [ 56 ]\nSampler "random" "integer pixelsamples" 4\n'
-            'LookAt 28 -28 14  0 0 -2  0 0 1\nCamera "perspective" "float fov" 40\nWorldBegin\n'
-            'LightSource "infinite" "rgb L" [0.9 1.0 1.2]\n'
-            'AttributeBegin\n  Material "metal" "rgb eta" [0.2 0.92 1.1] "rgb k" [3.9 2.45 2.14] "float roughness" 0.1\n  Rotate 20 0 0 1\n  Shape "plymesh" "string filename" "cube.ply"\nAttributeEnd\n'
-            'AttributeBegin\n  Material "matte" "rgb Kd" [0.5 0.5 0.5]\n  Shape "trianglemesh" "integer indices" [0 1 2 0 2 3] "point P" [-60 -60 -9.99  60 -60 -9.99  60 60 -9.99  -60 60 -9.99]\nAttributeEnd\n'
-            'WorldEnd\n')
+        (tmp_path / "s.pbrt").write_text(PLYMESH_SCENE)
         ps = PbrtScene(str(tmp_path / "s.pbrt"), gpu)
         b = SceneBuilder(orc_det)
         b.light_source("infinite", L=(0.9, 1.0, 1.2))
