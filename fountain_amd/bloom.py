@@ -22,6 +22,7 @@ import sys
 import numpy as np
 
 from . import _abi as A
+from ._cli import beside, refuse
 from ._nontwin import bind, host_image, params_of, ptr, set_fields
 from .api import default_backend
 
@@ -142,16 +143,13 @@ def main(argv=None):
         ap.add_argument(short, dest=dest, type=int if short == "--levels" else float, default=None)
     ap.add_argument("--karis", dest="bloom_karis", action="store_true")
     opts = ap.parse_args(argv)
-    out = opts.output or (opts.image[:-4] if opts.image.endswith(".exr") else opts.image) + "_bloom.exr"
+    out = opts.output or beside(opts.image, "_bloom.exr")
     if not out.endswith(".exr"):
-        print("error: the output must be an .exr file", file=sys.stderr)
-        return 2
+        return refuse("the output must be an .exr file")
     if opts.strength is not None and not 0.0 <= opts.strength <= 1.0:
-        print("error: --strength must be in [0, 1]", file=sys.stderr)
-        return 2
+        return refuse("--strength must be in [0, 1]")
     if value_refusal(opts, "--"):
-        print("error: %s" % value_refusal(opts, "--"), file=sys.stderr)
-        return 2
+        return refuse(value_refusal(opts, "--"))
     be = default_backend()
     p = params_from_arguments(be, opts, opts.strength)
     write_exr(out, bloom(be, read_exr(opts.image, be), p, device=opts.gpu), be)

@@ -26,6 +26,7 @@ import sys
 import numpy as np
 
 from . import _abi as A
+from ._cli import beside, refuse
 from ._nontwin import bind, host_image, params_of, ptr, set_fields
 from .api import default_backend
 
@@ -202,15 +203,12 @@ def main(argv=None):
     B.add_arguments(ap)
     opts = ap.parse_args(argv)
     if B.refusal(opts):
-        print("error: %s" % B.refusal(opts), file=sys.stderr)
-        return 2
-    out = opts.output or (opts.image[:-4] if opts.image.endswith(".exr") else opts.image) + ".png"
+        return refuse(B.refusal(opts))
+    out = opts.output or beside(opts.image, ".png")
     if not out.endswith(".png"):
-        print("error: the output must be a .png file", file=sys.stderr)
-        return 2
+        return refuse("the output must be a .png file")
     if opts.gamma is not None and opts.transfer != "gamma":
-        print("error: --gamma belongs to --transfer gamma", file=sys.stderr)
-        return 2
+        return refuse("--gamma belongs to --transfer gamma")
     be = default_backend()
     p = params_from_arguments(be, opts)
     img = read_exr(opts.image, be)

@@ -26,6 +26,7 @@ import sys
 import numpy as np
 
 from . import _abi as A
+from ._cli import refuse
 from ._nontwin import bind, call_args, check_tensor as _check_tensor, current_stream, ptr, tptr
 from .api import Film, FountainError, default_backend
 
@@ -341,8 +342,7 @@ def main(argv=None):
     try:
         mask = file_select(opts.file, opts.layer, opts.select, be=be)
     except (OSError, ValueError, KeyError) as e:
-        print("error: %s" % e, file=sys.stderr)
-        return 2
+        return refuse(e)
     write_exr(opts.output, np.repeat(mask[..., None], 3, axis=-1), be)
     return 0
 

@@ -23,6 +23,7 @@ import sys
 import numpy as np
 
 from . import _abi as A, _firsthit as F
+from ._cli import refuse
 from ._nontwin import bind, check_tensor as _check_tensor, current_stream, host_image, index_list, ptr, tptr
 
 # resolved channels: name -> slice of the 8 floats ftn_lightpass_resolve writes per pixel
@@ -163,22 +164,18 @@ def main(argv=None):
     try:
         lights = [_parse_light(t) for t in opts.light]
     except ValueError as e:
-        print("error: --light takes G=FILE:r,g,b with three finite gains, not %s" % e, file=sys.stderr)
-        return 2
+        return refuse("--light takes G=FILE:r,g,b with three finite gains, not %s" % e)
     if not 1 <= len(lights) <= A.FTN_LIGHTPASS_MAX_GROUPS or len({n for n, _, _ in lights}) != len(lights):
-        print("error: relight takes 1 to %d groups of different names" % A.FTN_LIGHTPASS_MAX_GROUPS, file=sys.stderr)
-        return 2
+        return refuse("relight takes 1 to %d groups of different names" % A.FTN_LIGHTPASS_MAX_GROUPS)
     if not opts.output.endswith(".exr"):
-        print("error: the output must be an .exr file", file=sys.stderr)
-        return 2
+        return refuse("the output must be an .exr file")
     from .api import default_backend, read_exr, write_exr
     be = default_backend()
     albedo = read_exr(opts.albedo, be)
     images = [(read_exr(path, be), gain) for _, path, gain in lights]
     for (name, path, _), (img, _) in zip(lights, images):
         if img.shape != albedo.shape:
-            print("error: %s is %d x %d, the albedo %d x %d" % (path, img.shape[1], img.shape[0], albedo.shape[1], albedo.shape[0]), file=sys.stderr)
-            return 2
+            return refuse("%s is %d x %d, the albedo %d x %d" % (path, img.shape[1], img.shape[0], albedo.shape[1], albedo.shape[0]))
     write_exr(opts.output, relight_files(be, albedo, images), be)
     print("relight: %s from %d groups (%s)" % (opts.output, len(lights), ", ".join(n for n, _, _ in lights)), file=sys.stderr)
     return 0

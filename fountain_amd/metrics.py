@@ -31,6 +31,7 @@ import sys
 import numpy as np
 
 from . import _abi as A
+from ._cli import refuse
 from ._nontwin import bind, host_image, params_of, ptr, set_fields
 from .api import default_backend
 
@@ -183,31 +184,27 @@ def main(argv=None):
     ap.add_argument("--gpu", type=int, default=0)
     ap.add_argument("--fail-above", action="append", default=None, metavar="NAME=VALUE", help="exit with 1 when the metric exceeds the value or is NaN")
     opts = ap.parse_args(argv)
-
-    def usage(msg):
-        print("error: %s" % msg, file=sys.stderr)
-        return 2
     try:
         thresholds = parse_thresholds(opts.fail_above)
     except ValueError as e:
-        return usage(e)
+        return refuse(e)
     for name, v in (("--error-map", opts.error_map), ("--ssim-map", opts.ssim_map), ("--tile-map", opts.tile_map)):
         if v is not None and not v.endswith(".exr"):
-            return usage("%s must name an .exr file" % name)
+            return refuse("%s must name an .exr file" % name)
     if opts.ssim_map and not opts.ssim:
-        return usage("--ssim-map belongs to --ssim")
+        return refuse("--ssim-map belongs to --ssim")
     for name, v in (("--peak", opts.peak), ("--rel-eps", opts.rel_eps)):
         if v is not None and not 0.0 < v < float("inf"):
-            return usage("%s takes a finite value above 0" % name)
+            return refuse("%s takes a finite value above 0" % name)
     be = default_backend()
     sizes = [exr_size(path, be) for path in (opts.test, opts.ref)]
     for path, size in zip((opts.test, opts.ref), sizes):
         if size is None:
-            return usage("%s is not a readable OpenEXR file" % path)
+            return refuse("%s is not a readable OpenEXR file" % path)
     if sizes[0] != sizes[1]:
-        return usage("the images differ in size: %d x %d against %d x %d" % (sizes[0] + sizes[1]))
+        return refuse("the images differ in size: %d x %d against %d x %d" % (sizes[0] + sizes[1]))
     if opts.ssim and min(sizes[0]) < A.FTN_METRICS_SSIM_TAPS:
-        return usage("--ssim needs images of at least 11 x 11 pixels")
+        return refuse("--ssim needs images of at least 11 x 11 pixels")
     fields = {k: v for k, v in (("peak", opts.peak), ("rel_eps", opts.rel_eps)) if v is not None}
     p = MetricsParams(be, ssim=opts.ssim, **fields)
     test, ref = read_exr(opts.test, be), read_exr(opts.ref, be)
@@ -215,7 +212,7 @@ def main(argv=None):
     try:
         r = compare_cpu(be, test, ref, p, **want) if opts.cpu else compare(be, test, ref, p, device=opts.gpu, **want)
     except FountainError as e:
-        return usage(e)
+        return refuse(e)
     w, h = sizes[0]
     grey = lambda plane: np.repeat(np.asarray(plane, np.float32)[:, :, None], 3, axis=2)
     if opts.error_map:

@@ -34,6 +34,7 @@ import sys
 import numpy as np
 
 from . import _abi as A
+from ._cli import beside, refuse
 from ._nontwin import bind, check_tensor, current_stream, desc_of as _desc, host_image, params_of, ptr, tptr
 
 
@@ -178,20 +179,17 @@ class TemporalAccumulator:
 
 def motion_path(filename, k):
     """out.exr, k -> out_<k>_motion.exr (--dynamic)"""
-    base = filename[:-4] if filename.endswith(".exr") else filename
-    return "%s_%d_motion.exr" % (base, k)
+    return beside(filename, "_%d_motion.exr" % k)
 
 
 def blurred_path(filename, k):
     """out.exr, k -> out_<k>_blurred.exr (--dynamic --vector-blur)"""
-    base = filename[:-4] if filename.endswith(".exr") else filename
-    return "%s_%d_blurred.exr" % (base, k)
+    return beside(filename, "_%d_blurred.exr" % k)
 
 
 def frame_paths(filename, k):
     """out.exr, k -> (out_<k>.exr, out_<k>_accumulated.exr, out_<k>_denoised_guided.exr)"""
-    base = filename[:-4] if filename.endswith(".exr") else filename
-    return "%s_%d.exr" % (base, k), "%s_%d_accumulated.exr" % (base, k), "%s_%d_denoised_guided.exr" % (base, k)
+    return tuple(beside(filename, "_%d%s.exr" % (k, s)) for s in ("", "_accumulated", "_denoised_guided"))
 
 
 def main(argv=None):
@@ -214,21 +212,15 @@ def main(argv=None):
                          "for this share of the frame interval, 0..1 (default 0.5)")
     opts = ap.parse_args(argv)
     if opts.vector_blur is not None and not opts.dynamic:
-        print("error: --vector-blur belongs to --dynamic: a static scene's frames carry no motion vectors", file=sys.stderr)
-        return 2
+        return refuse("--vector-blur belongs to --dynamic: a static scene's frames carry no motion vectors")
     if opts.vector_blur is not None and opts.vector_blur is not True and not 0.0 <= opts.vector_blur <= 1.0:
-        print("error: --vector-blur takes a shutter in [0, 1]", file=sys.stderr)
-        return 2
+        return refuse("--vector-blur takes a shutter in [0, 1]")
     if opts.dynamic and len(opts.scene_files) < 2:
-        print("error: --dynamic needs at least two frames: a frame's motion is against the frame before it", file=sys.stderr)
-        return 2
+        return refuse("--dynamic needs at least two frames: a frame's motion is against the frame before it")
     if opts.samples is not None and opts.samples < 2:
-        print("error: temporal accumulation needs at least 2 samples per pixel: a pixel's variance is unknown below that (here %d)" % opts.samples,
-              file=sys.stderr)
-        return 2
+        return refuse("temporal accumulation needs at least 2 samples per pixel: a pixel's variance is unknown below that (here %d)" % opts.samples)
     if opts.alpha_min is not None and not 0.0 <= opts.alpha_min <= 1.0:
-        print("error: --alpha-min must be in 0..1", file=sys.stderr)
-        return 2
+        return refuse("--alpha-min must be in 0..1")
     from .api import PathIntegrator, PbrtScene, RandomSampler, default_backend, write_exr
     from .denoise import denoise_guided
     from .gbuffer import CHANNELS, render_gbuffer
@@ -238,12 +230,10 @@ def main(argv=None):
     first = frames[0]
     spp = opts.samples or first.samples_per_pixel
     if spp < 2:
-        print("error: temporal accumulation needs at least 2 samples per pixel: a pixel's variance is unknown below that (here %d)" % spp, file=sys.stderr)
-        return 2
+        return refuse("temporal accumulation needs at least 2 samples per pixel: a pixel's variance is unknown below that (here %d)" % spp)
     for f, name in zip(frames[1:], opts.scene_files[1:]):
         if bytes(f._film_desc) != bytes(first._film_desc):
-            print("error: %s has another film than %s: the frames of a sequence share resolution and crop" % (name, opts.scene_files[0]), file=sys.stderr)
-            return 2
+            return refuse("%s has another film than %s: the frames of a sequence share resolution and crop" % (name, opts.scene_files[0]))
     filename = opts.image_name or first.film_name
     if ".exr" not in filename:
         raise SystemExit("output must be an .exr file")
@@ -252,8 +242,7 @@ def main(argv=None):
         for k in range(1, len(frames)):
             why = descs_differ(frames[k].desc, frames[k - 1].desc)
             if why:
-                print("error: --dynamic: the scenes of %s and %s do not correspond: %s" % (opts.scene_files[k], opts.scene_files[k - 1], why), file=sys.stderr)
-                return 2
+                return refuse("--dynamic: the scenes of %s and %s do not correspond: %s" % (opts.scene_files[k], opts.scene_files[k - 1], why))
     scene = first.create_scene(device=opts.gpu)
     prev_scene = None
     radiance = PathIntegrator.new(opts.max_depth, opts.rr_threshold)

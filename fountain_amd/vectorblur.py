@@ -29,6 +29,7 @@ import sys
 import numpy as np
 
 from . import _abi as A
+from ._cli import beside, refuse
 from ._nontwin import bind, check_tensor, check_workspace, host_image, params_of, ptr, set_fields, tptr
 from .api import default_backend
 
@@ -162,14 +163,12 @@ def main(argv=None):
     ap.add_argument("--taps", type=int, default=None, metavar="N", help="taps per pixel, 1..64 (default 16)")
     ap.add_argument("--max-radius", type=float, default=None, metavar="R", help="the longest half blur in pixels, up to 16 (default 16)")
     opts = ap.parse_args(argv)
-    out = opts.output or (opts.image[:-4] if opts.image.endswith(".exr") else opts.image) + "_blurred.exr"
+    out = opts.output or beside(opts.image, "_blurred.exr")
     if not out.endswith(".exr"):
-        print("error: the output must be an .exr file", file=sys.stderr)
-        return 2
+        return refuse("the output must be an .exr file")
     why = value_refusal(opts.shutter, opts.taps, opts.max_radius)
     if why:
-        print("error: %s" % why, file=sys.stderr)
-        return 2
+        return refuse(why)
     be = default_backend()
     p = VectorBlurParams(be, **{k: v for k, v in (("shutter", opts.shutter), ("taps", opts.taps), ("max_radius", opts.max_radius)) if v is not None})
     rgb = read_exr(opts.image, be)
@@ -177,8 +176,7 @@ def main(argv=None):
     depth = read_exr(opts.depth, be) if opts.depth else None
     for name, a in ((opts.motion, motion), (opts.depth, depth)):
         if a is not None and a.shape != rgb.shape:
-            print("error: %s is %d x %d, %s is %d x %d" % (name, a.shape[1], a.shape[0], opts.image, rgb.shape[1], rgb.shape[0]), file=sys.stderr)
-            return 2
+            return refuse("%s is %d x %d, %s is %d x %d" % (name, a.shape[1], a.shape[0], opts.image, rgb.shape[1], rgb.shape[0]))
     gb12 = None if depth is None else gb12_from_depth(depth[..., 0])
     write_exr(out, vector_blur(be, rgb, motion[..., :2], gb12, p, device=opts.gpu), be)
     print("vector blur: %s (shutter %.6g, %d taps)" % (out, p.desc.shutter, p.desc.taps), file=sys.stderr)
